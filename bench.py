@@ -552,6 +552,45 @@ def self_launch(n):
     return rc
 
 
+DUMP_SAMPLE = 1 << 21  # dofs written by --dump-outputs: 3 float64 arrays of this length = 48 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(d, solver, stats, dist, rank):
+    """--dump-outputs: the Newton update (VEC_UPDATE) and assembled rhs (VEC_RHS) of the last timed step at a fixed seeded sample
+    of global dofs (global id: 3 * global u node + component, then 3 * n_unodes_global + global p node, the id of the one-context
+    run), so that two builds -- and runs on different rank counts -- compare entry for entry.  Every rank fills the sampled dofs
+    it owns; a sum over ranks (every dof has one owner) gathers them on rank 0, which writes the files."""
+    import numpy as np
+    from openifem_amd import capi
+    t = solver.partition_tables()
+    nuo, npo = t["n_unodes_owned"], t["n_pnodes_owned"]
+    gid = np.concatenate([(t["l2g_u"][:nuo, None] * 3 + np.arange(3)[None, :]).ravel(), 3 * t["n_unodes_global"] + t["l2g_p"][:npo]])
+    n_global = 3 * int(t["n_unodes_global"]) + int(t["n_pnodes_global"])
+    if n_global <= DUMP_SAMPLE:
+        idx = np.arange(n_global, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_global, DUMP_SAMPLE, replace=False))
+    order = np.argsort(gid)
+    pos = np.minimum(np.searchsorted(gid[order], idx), len(gid) - 1)
+    hit = gid[order][pos] == idx
+    vals = np.zeros((2, len(idx)))
+    for row, vec in enumerate((capi.VEC_UPDATE, capi.VEC_RHS)):
+        v = np.zeros(len(gid))
+        assert solver.L.ifem_vec_get(solver.ctx, vec, v.ctypes.data_as(C.c_void_p)) == 0
+        vals[row, hit] = v[order[pos[hit]]]
+    if dist:
+        import torch
+        tv = torch.from_numpy(vals)
+        dist.all_reduce(tv, op=dist.ReduceOp.SUM)
+        vals = tv.numpy()
+    if rank == 0:
+        os.makedirs(d, exist_ok=True)
+        for name, a in (("update", vals[0]), ("rhs", vals[1]), ("dof_index", idx.astype(np.float64)),
+                        ("solve_stats", np.array([stats.fgmres_iters, stats.fgmres_res], dtype=np.float64))):
+            np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -579,6 +618,10 @@ def main():
     ap.add_argument("--mg-min-cells", type=int, default=0, help="multigrid levels: a direction is halved only while it keeps this many cells per rank (0: the host mirror's default, 4)")
     ap.add_argument("--fgmres-rel", type=float, default=None, help="test aid: relative tolerance of the outer FGMRES (reference and default: 1e-4)")
     ap.add_argument("--dump-update", default=None, help="test aid: every rank writes its owned entries of the last Newton update and their global lattice ids to <path>.rank<r>.npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (channel3d, insim) as DIR/<name>.npy: the Newton "
+                         "update and the assembled rhs at a fixed seeded sample of global dofs (dof_index), and the outer FGMRES "
+                         "iterations and residual (solve_stats); at most 2^21 sampled dofs (48 MB)")
     ap.add_argument("--verbosity", dest="verbose", type=int, default=0)
     ap.add_argument("--outer-mf", type=int, default=None, help="experiment: apply the u-u block of the OUTER operator matrix-free too")
     ap.add_argument("--workload", default="channel3d", choices=["channel3d", "cylinder2d", "cylinder2d_scnsim", "cylinder3d"],
@@ -592,6 +635,10 @@ def main():
                     help="insim (default, the BASELINE metric): one Newton iteration of MPI::InsIM; insimex: one steady-state "
                          "time step of MPI::InsIMEX (rhs-only assembly + solve), reported as a side measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "channel3d" or args.solver != "insim"):
+        ap.error("--dump-outputs covers the flagship path only (--workload channel3d --solver insim)")
 
     # the CPU baseline leg pins one OpenMP thread per physical core (read by libgomp when the oracle library loads) -- only when
     # the job owns the machine: with an affinity mask or a cgroup quota smaller than the core count, places outside the allowance
@@ -714,6 +761,8 @@ def main():
         asm_kernel_ms += solver.timing().assemble_kernel_ms  # HIP events around the cell kernel on the context stream
     fence()
     elapsed = time.time() - t0
+    if args.dump_outputs:  # before anything else touches the vectors of the last timed step
+        dump_outputs(args.dump_outputs, solver, last, dist, rank)
     comm = solver.comm_stats(reset=True)  # exchanges / all-reduces of the K timed steps (all multigrid levels)
     # the TRUE residual of the last timed solve, recomputed with the assembled operator (collective; outside the timed region)
     true_res, rhs_norm = solver.true_residual()

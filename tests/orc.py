@@ -61,7 +61,28 @@ def lib(native=False):
         subprocess.check_call(["make", "-C", _ODIR], stdout=subprocess.DEVNULL)
     if _lib is None:
         _lib = _bind(C.CDLL(path))
+        _cap_threads(_lib)
     return _lib
+
+
+def cpu_allowance():
+    """CPUs this process may really use: the affinity mask, lowered to the cgroup CPU quota when there is one"""
+    n = len(os.sched_getaffinity(0))
+    try:
+        q, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if q != "max":
+            n = min(n, max(1, int(float(q) / float(per))))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
+def _cap_threads(L):
+    """OpenMP sizes its team by the affinity mask, which ignores a cgroup CPU quota: on a host whose mask is far larger than
+    the quota, every parallel region of the oracle would oversubscribe the few CPUs it may use (the time-stepping tests run
+    thousands of small regions).  An explicit OMP_NUM_THREADS, or n_threads of a call's options, still wins."""
+    if "OMP_NUM_THREADS" not in os.environ:
+        L.omp_set_num_threads(cpu_allowance())
 
 
 def _bind(L):

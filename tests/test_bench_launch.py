@@ -95,3 +95,80 @@ def test_stdout_line_is_compact_and_parses(fat):
     assert {"value", "unit", "cores", "kind"} <= set(o["cpu_baseline"])
     assert o["value_cold"] == rec["value_cold"] and o["value_sustained"] == rec["value_sustained"]
     assert "kernels" not in o["roofline"] and "cylinder_workloads" not in o and "fsi_inputs" not in o
+
+
+class _FakeRank:
+    """what bench.dump_outputs reads of a solver: the partition tables and the owned entries of VEC_UPDATE / VEC_RHS"""
+
+    def __init__(self, l2g_u, l2g_p, ngu, ngp, glob_update, glob_rhs):
+        import ctypes as C
+        import numpy as np
+        from openifem_amd import capi
+        self.t = {"l2g_u": np.asarray(l2g_u, np.int64), "l2g_p": np.asarray(l2g_p, np.int64), "n_unodes_owned": len(l2g_u),
+                  "n_pnodes_owned": len(l2g_p), "n_unodes_global": ngu, "n_pnodes_global": ngp}
+        gid = np.concatenate([(self.t["l2g_u"][:, None] * 3 + np.arange(3)).ravel(), 3 * ngu + self.t["l2g_p"]])
+        owned = {capi.VEC_UPDATE: glob_update[gid], capi.VEC_RHS: glob_rhs[gid]}
+        self.ctx = None
+
+        class _L:
+            @staticmethod
+            def ifem_vec_get(ctx, vec, ptr):
+                C.memmove(ptr, owned[vec].ctypes.data, owned[vec].nbytes)
+                return 0
+        self.L = _L
+
+    def partition_tables(self):
+        return self.t
+
+
+def _dump_two_ranks(tmp_path, monkeypatch, ngu, ngp, sample):
+    """bench.dump_outputs on two fake ranks (u and p nodes dealt out in a scrambled order), summed as the all-reduce sums them"""
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", sample)
+    n = 3 * ngu + ngp
+    rng = np.random.default_rng(5)
+    upd, rhs = rng.standard_normal(n), rng.standard_normal(n)
+    pu, pp = rng.permutation(ngu), rng.permutation(ngp)
+    ranks = [_FakeRank(pu[:ngu // 3], pp[:ngp // 2], ngu, ngp, upd, rhs), _FakeRank(pu[ngu // 3:], pp[ngp // 2:], ngu, ngp, upd, rhs)]
+    stats = types.SimpleNamespace(fgmres_iters=3, fgmres_res=1.5e-5)
+    parts = []
+    for r, s in enumerate(ranks):
+        bench.dump_outputs(str(tmp_path / f"r{r}"), s, stats, None, 0)
+        parts.append({k: np.load(tmp_path / f"r{r}" / f"{k}.npy") for k in ("update", "rhs", "dof_index", "solve_stats")})
+    return upd, rhs, parts
+
+
+def test_dump_outputs_gathers_the_sampled_global_dofs(tmp_path, monkeypatch):
+    import numpy as np
+    upd, rhs, parts = _dump_two_ranks(tmp_path, monkeypatch, ngu=50, ngp=20, sample=64)
+    idx = parts[0]["dof_index"]
+    assert all(p[k].dtype == np.float64 for p in parts for k in p)
+    assert len(idx) == 64 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 170
+    np.testing.assert_array_equal(parts[1]["dof_index"], idx)  # the sample depends on the global size alone
+    i = idx.astype(np.int64)
+    np.testing.assert_array_equal(parts[0]["update"] + parts[1]["update"], upd[i])
+    np.testing.assert_array_equal(parts[0]["rhs"] + parts[1]["rhs"], rhs[i])
+    assert np.count_nonzero(parts[0]["update"]) + np.count_nonzero(parts[1]["update"]) == 64  # every sampled dof has one owner
+    np.testing.assert_array_equal(parts[0]["solve_stats"], [3, 1.5e-5])
+
+
+def test_dump_outputs_writes_everything_below_the_sample_size(tmp_path, monkeypatch):
+    import numpy as np
+    upd, rhs, parts = _dump_two_ranks(tmp_path, monkeypatch, ngu=10, ngp=4, sample=1 << 21)
+    np.testing.assert_array_equal(parts[0]["dof_index"], np.arange(34))
+    np.testing.assert_array_equal(parts[0]["update"] + parts[1]["update"], upd)
+    np.testing.assert_array_equal(parts[0]["rhs"] + parts[1]["rhs"], rhs)
+
+
+def test_dump_outputs_stays_under_64_mb():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 3 * 8 * bench.DUMP_SAMPLE + 16 <= 64 << 20
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0", "--warmup", "0"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr

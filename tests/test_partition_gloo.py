@@ -1,8 +1,13 @@
 """world_size-2 (and 4) CPU tests of the multi-GPU host logic over torch.distributed/gloo (no GPU):
-the block partition, ownership, ghost numbering and halo plans the RCCL path consumes."""
+the block partition, ownership, ghost numbering and halo plans the RCCL path consumes.
+
+The ranks are threads of the test process, each with its own gloo process group over one in-process store: a process per
+rank would map the HIP runtime (torch and the library link it) once per rank, and a box with a GPU bounds how many
+processes may hold it at once."""
+import datetime
 import os
-import socket
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -10,24 +15,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, P, reps, dim, q):
+def _worker(rank, world, store, P, reps, dim, res):
     try:
         sys.path.insert(0, ROOT)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import torch
         import torch.distributed as dist
         from openifem_amd import host
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        pg = dist.ProcessGroupGloo(store, rank, world, datetime.timedelta(seconds=240))
         p1 = (2.0, 0.2, 0.2)[:dim]
         cylinder = reps == "cylinder"
         if cylinder:  # unstructured mesh cut into strips (partition_unstructured)
@@ -48,7 +43,7 @@ def _worker(rank, world, port, P, reps, dim, q):
         for key, no, ng in (("l2g_u", nUo, t["n_unodes_global"]), ("l2g_p", nPo, t["n_pnodes_global"])):
             cnt = torch.zeros(ng, dtype=torch.int64)
             cnt[torch.from_numpy(t[key][:no])] += 1
-            dist.all_reduce(cnt)
+            pg.allreduce([cnt]).wait()
             assert int(cnt.min()) == 1 and int(cnt.max()) == 1, f"{key}: ownership is not a partition"
         # (b) halo exchange through the send/recv plans reproduces f(global id) on the ghosts
         for which, l2g, no, nl, bs in (("u", t["l2g_u"], nUo, nUl, dim), ("p", t["l2g_p"], nPo, nPl, 1)):
@@ -62,9 +57,9 @@ def _worker(rank, world, port, P, reps, dim, q):
                 rbuf = torch.zeros((rp[k + 1] - rp[k], bs), dtype=torch.float64)
                 bufs.append((k, rbuf))
                 if sbuf.numel():
-                    reqs.append(dist.isend(sbuf, int(nb)))
+                    reqs.append(pg.send([sbuf], int(nb), 0))
                 if rbuf.numel():
-                    reqs.append(dist.irecv(rbuf, int(nb)))
+                    reqs.append(pg.recv([rbuf], int(nb), 0))
             for r in reqs:
                 r.wait()
             for k, rbuf in bufs:
@@ -87,9 +82,9 @@ def _worker(rank, world, port, P, reps, dim, q):
                 rbuf = torch.zeros(int(rp[k + 1] - rp[k]), dtype=torch.float64)
                 bufs.append((k, rbuf))
                 if sbuf.numel():
-                    reqs.append(dist.isend(sbuf, int(nb)))
+                    reqs.append(pg.send([sbuf], int(nb), 0))
                 if rbuf.numel():
-                    reqs.append(dist.irecv(rbuf, int(nb)))
+                    reqs.append(pg.recv([rbuf], int(nb), 0))
             for r in reqs:
                 r.wait()
             for k, rbuf in bufs:
@@ -108,11 +103,10 @@ def _worker(rank, world, port, P, reps, dim, q):
             mine = torch.zeros(m.n_cells, dtype=torch.int64)
             for r in vc.reshape(len(vc), -1):
                 mine[key[tuple(np.round(r, 12))]] = 1
-            dist.all_reduce(mine)
+            pg.allreduce([mine]).wait()
             assert int(mine.min()) >= 1
-            dist.barrier()
-            dist.destroy_process_group()
-            q.put((rank, "ok"))
+            pg.barrier().wait()
+            res[rank] = "ok"
             return
         # (c) local connectivity maps to the global lattice connectivity; every global cell touching an owned node is local
         from boxmesh import BoxMesh
@@ -133,27 +127,24 @@ def _worker(rank, world, port, P, reps, dim, q):
         gl = set((t["l2g_u"][d // dim] * dim + d % dim).tolist())
         local_all = set((t["l2g_u"][:, None] * dim + np.arange(dim)[None, :]).ravel().tolist())
         assert gl == (set(d0.tolist()) & local_all)
-        dist.barrier()
-        dist.destroy_process_group()
-        q.put((rank, "ok"))
+        pg.barrier().wait()
+        res[rank] = "ok"
     except Exception as e:  # noqa
         import traceback
-        q.put((rank, traceback.format_exc()))
+        res[rank] = traceback.format_exc()
 
 
 @pytest.mark.parametrize("world,P,reps,dim", [(2, (2, 1, 1), (4, 2, 2), 3), (4, (2, 2, 1), (4, 4, 2), 3), (2, (2, 1), (6, 3), 2),
                                                (4, (2, 2, 1), (8, 6, 3), 3), (2, (2, 1, 1), "cylinder", 2), (3, (3, 1, 1), "cylinder", 2),
                                                (8, (2, 2, 2), (4, 4, 4), 3)])
 def test_block_partition_over_gloo(world, P, reps, dim):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, P, reps, dim, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-    for rank, msg in res:
+    import torch.distributed as dist
+    store = dist.HashStore()
+    res = [None] * world
+    th = [threading.Thread(target=_worker, args=(r, world, store, P, reps, dim, res), daemon=True) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    for rank, msg in enumerate(res):
         assert msg == "ok", f"rank {rank}: {msg}"
