@@ -576,7 +576,7 @@ int ifem_imex_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero,
   IFEM_API_BEGIN
   if (!p || p->dt <= 0) throw Error(IFEM_E_BADPARAM, "bad ifem_ins_params");
   auto t0 = std::chrono::steady_clock::now();
-  launch_ins_assemble_ex(ctx, p, use_nonzero, 1, assemble_system);
+  launch_ins_assemble_ex(ctx, p, use_nonzero, 1, assemble_system ? AsmMode::Full : AsmMode::Rhs);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->timing.assemble_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   IFEM_API_END
@@ -604,7 +604,7 @@ int ifem_imex_step(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_op
   IFEM_API_BEGIN
   if (!p || p->dt <= 0) throw Error(IFEM_E_BADPARAM, "bad ifem_ins_params");
   v_zero(ctx, ctx->n_local, ctx->vec[IFEM_VEC_UPDATE].p); // solution_time_increment = 0
-  launch_ins_assemble_ex(ctx, p, apply_nonzero, 1, assemble_system);
+  launch_ins_assemble_ex(ctx, p, apply_nonzero, 1, assemble_system ? AsmMode::Full : AsmMode::Rhs);
   const int rc = imex_solve_impl(ctx, p, o, apply_nonzero, stats);
   if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
   copy_owned(ctx, IFEM_VEC_PRESENT, IFEM_VEC_UPDATE, 1.0, 1.0); // present_solution += solution_time_increment
@@ -787,7 +787,7 @@ int ifem_uu_block_diag(ifem_ctx *ctx, int which, double *host_out) {
     IFEM_HIP_CHECK(hipMemcpyAsync(host_out, ctx->bjac.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     IFEM_HIP_CHECK(hipMemcpyAsync(ctx->bjac.p, keep.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    ctx->bjac_f32_valid = false;
+    bjac_written(ctx);
   } else {
     IFEM_HIP_CHECK(hipMemcpyAsync(host_out, ctx->bjac.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -900,7 +900,9 @@ int ifem_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, dou
   for (int64_t i = 0; i < n; ++i) rowptr[i + 1] += rowptr[i];
   if (!col || !val) return IFEM_OK;
   auto cA = ctx->Auu.col.download(s), cT = ctx->Bt.col.download(s), cB = ctx->B.col.download(s), cM = ctx->Mp.col.download(s);
-  auto vA = ctx->Auu.val.download(s), vT = ctx->Bt.val.download(s), vB = ctx->B.val.download(s), vM = ctx->Mp.val.download(s);
+  std::vector<double> vA;
+  if (which == 0) vA = stored_uu(ctx).download(s);
+  auto vT = ctx->Bt.val.download(s), vB = ctx->B.val.download(s), vM = ctx->Mp.val.download(s);
   auto dM = ctx->diagMu.download(s);
   for (int64_t A = 0; A < ctx->nUo; ++A) {
     const int64_t rs = rpA[A], len = rpA[A + 1] - rs, ts = rpT[A], tlen = rpT[A + 1] - ts;
@@ -959,7 +961,8 @@ int ifem_export_rows(ifem_ctx *ctx, int which, int64_t row0, int64_t nrows, int6
     if (col && val) {
       const int64_t b0 = rpA[0], b1 = rpA[A1 - A0], t0 = rpT[0], t1 = rpT[A1 - A0];
       auto cA = download_range(ctx->Auu.col, b0, b1 - b0, s);
-      auto vA = download_range(ctx->Auu.val, b0 * bs, (b1 - b0) * bs, s);
+      std::vector<double> vA;
+      if (which == 0) vA = download_range(stored_uu(ctx), b0 * bs, (b1 - b0) * bs, s);
       auto cT = download_range(ctx->Bt.col, t0, t1 - t0, s);
       auto vT = download_range(ctx->Bt.val, t0 * dim, (t1 - t0) * dim, s);
       auto dM = download_range(ctx->diagMu, A0 * dim, (A1 - A0) * dim, s);

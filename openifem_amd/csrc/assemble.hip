@@ -16,7 +16,8 @@
 
 namespace ifem {
 
-static void assemble_epilogue(ifem_ctx *ctx, int use_nonzero);
+static void assemble_epilogue(ifem_ctx *ctx, int use_nonzero, bool mass);
+static void level_geometry_epilogue(ifem_ctx *ctx, int use_nonzero, bool mass);
 static void ifem_ctx_unconstrained_geometry(ifem_ctx *ctx, const ifem_ins_params *p);
 void launch_ins_assemble2_kernel(ifem_ctx *ctx, const AsmArgs &A);
 bool launch_ins_assemble3_kernel(ifem_ctx *ctx, const AsmArgs &A);
@@ -55,9 +56,6 @@ __global__ void k_mask_b(int64_t n_rows, const int64_t *__restrict__ rp, const i
     }
   }
 }
-// assemblies with an unchanged (and never yet changed) constrained-dof set after which the unconstrained copies of B / B^T / S_m are given
-// back: the second cached assembly.  A run whose set does change later (FSI: every time step) re-integrates them once and keeps them from then on.
-constexpr int kGeoKeep = 2;
 static void masked_geometry_blocks(ifem_ctx *ctx, int use_nonzero) {
   KScope ks(ctx, IFEM_KC_SCHUR_SETUP, 16.0 * double(ctx->B.val.n + ctx->Bt.val.n));
   const int w = use_nonzero ? 1 : 0;
@@ -65,53 +63,50 @@ static void masked_geometry_blocks(ifem_ctx *ctx, int use_nonzero) {
   hipStream_t s = ctx->stream;
   const int64_t nu = ctx->Bt.n_rows, np = ctx->B.n_rows;
   if (ctx->dim == 3) {
-    if (nu) hipLaunchKernelGGL((k_mask_bt<3>), dim3(unsigned((nu * 32 + 255) / 256)), dim3(256), 0, s, nu, ctx->Bt.rowptr.p, flags, ctx->Bt0.p, ctx->Bt.val.p);
-    if (np) hipLaunchKernelGGL((k_mask_b<3>), dim3(unsigned((np * 32 + 255) / 256)), dim3(256), 0, s, np, ctx->B.rowptr.p, ctx->B.col.p, flags, ctx->B0.p, ctx->B.val.p);
+    if (nu) hipLaunchKernelGGL((k_mask_bt<3>), dim3(unsigned((nu * 32 + 255) / 256)), dim3(256), 0, s, nu, ctx->Bt.rowptr.p, flags, ctx->geo.Bt0.p, ctx->Bt.val.p);
+    if (np) hipLaunchKernelGGL((k_mask_b<3>), dim3(unsigned((np * 32 + 255) / 256)), dim3(256), 0, s, np, ctx->B.rowptr.p, ctx->B.col.p, flags, ctx->geo.B0.p, ctx->B.val.p);
   } else {
-    if (nu) hipLaunchKernelGGL((k_mask_bt<2>), dim3(unsigned((nu * 32 + 255) / 256)), dim3(256), 0, s, nu, ctx->Bt.rowptr.p, flags, ctx->Bt0.p, ctx->Bt.val.p);
-    if (np) hipLaunchKernelGGL((k_mask_b<2>), dim3(unsigned((np * 32 + 255) / 256)), dim3(256), 0, s, np, ctx->B.rowptr.p, ctx->B.col.p, flags, ctx->B0.p, ctx->B.val.p);
+    if (nu) hipLaunchKernelGGL((k_mask_bt<2>), dim3(unsigned((nu * 32 + 255) / 256)), dim3(256), 0, s, nu, ctx->Bt.rowptr.p, flags, ctx->geo.Bt0.p, ctx->Bt.val.p);
+    if (np) hipLaunchKernelGGL((k_mask_b<2>), dim3(unsigned((np * 32 + 255) / 256)), dim3(256), 0, s, np, ctx->B.rowptr.p, ctx->B.col.p, flags, ctx->geo.B0.p, ctx->B.val.p);
   }
 }
 
-void launch_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) { launch_ins_assemble_ex(ctx, p, use_nonzero, 0, 1); }
-void launch_ins_assemble_geometry(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) { launch_ins_assemble_ex(ctx, p, use_nonzero, 0, 2); }
+void launch_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) { launch_ins_assemble_ex(ctx, p, use_nonzero, 0, AsmMode::Full); }
+void launch_ins_assemble_geometry(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) { launch_ins_assemble_ex(ctx, p, use_nonzero, 0, AsmMode::LevelGeometry); }
 
 // imex = 1: InsIMEX::assemble (mpi_insimex.cpp:150-355): every field comes from the present solution, the matrix has no
-// convective terms; assemble_system = 0 integrates the right-hand side only and leaves the matrices untouched;
-// assemble_system = 2 (internal): B, B^T, M_p, diag(M_u) only -- a multigrid level of the pressure Schur complement
-void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, int assemble_system) {
+// convective terms.  AsmMode (kernels.hpp): what the launch integrates.
+void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode) {
   hipStream_t s = ctx->stream;
   const int dim = ctx->dim;
-  const bool geo_only = assemble_system >= 2; // 3: the same without constraints (pristine blocks)
-  if (assemble_system == 2) {
-    const int64_t key = ctx->flag_id[use_nonzero ? 1 : 0];
-    // a multigrid level is asked once per preconditioner application: it counts ASSEMBLIES of the finest level (its version stamp)
+  const bool full = mode == AsmMode::Full, level = mode == AsmMode::LevelGeometry, unconstrained = mode == AsmMode::Unconstrained;
+  const bool matrices = mode != AsmMode::Rhs;
+  const bool geo_only = level || unconstrained;
+  // B, B^T, M_p and diag(M_u) (ctx.hpp::GeoCache): an assembly whose constrained-dof set equals that of the previous one (zero_ and
+  // nonzero_constraints of make_constraints list the same dofs) keeps them (bit-identical to re-integrating them) and integrates A_uu and
+  // the right-hand side only.  ifem_tuning::geo_cache = 0 switches it off for full assemblies; a multigrid level keeps its blocks unless
+  // geo_cache = 2 and counts ASSEMBLIES of the finest level (its version stamp), not the preconditioner applications that ask.
+  const int64_t geo_key = ctx->flag_id[use_nonzero ? 1 : 0];
+  bool skip_geo = false;
+  if (level) {
     const ifem_ctx *f0 = ctx;
     while (f0->mg_fine) f0 = f0->mg_fine;
-    const bool new_assembly = uint64_t(f0->asm_version) != ctx->geo_seen_asm;
-    ctx->geo_seen_asm = uint64_t(f0->asm_version);
-    if (ctx->geo_valid && ctx->geo_key == key && ctx->tune.geo_cache != 2) { // still the blocks of this constrained-dof set
-      if (new_assembly && ++ctx->geo_unchanged == kGeoKeep && ctx->geo0_valid && ctx->geo_set_changes == 0) { // its unconstrained copies go the way of the finest level's (below)
-        ctx->B0.release(); ctx->Bt0.release(); ctx->Sm0.release();
-        ctx->geo0_valid = false; ctx->sm0_valid = false;
-      }
-      return;
-    }
-    if (ctx->geo_valid) ctx->geo_set_changes++;
-    ctx->geo_unchanged = 0;
+    const bool new_assembly = uint64_t(f0->asm_version) != ctx->geo.seen_asm;
+    ctx->geo.seen_asm = uint64_t(f0->asm_version);
+    if (ctx->geo.reuse(geo_key, ctx->tune.geo_cache != 2, new_assembly)) return;
   }
   // ifem_tuning::stored_uu = 0: the velocity-velocity block is never stored.  The cell kernel integrates the right-hand side (and,
   // through the geometry path, B / B^T / M_p / diag(M_u)); A_uu is applied matrix-free in fp64 by the outer operator (the same
   // operator to 1e-13, test_matrix_free_uu_apply_equals_assembled_block) and its node-block diagonal comes from the cell integrals.
   // An assembly with inhomogeneous constraint values needs the element matrix columns (distribute_local_to_global moves K g into the
   // right-hand side): that one -- the first Newton iteration of a step with non-zero boundary values -- takes the stored path.
-  const bool mf_only = assemble_system == 1 && ctx->tune.stored_uu == 0 && !(use_nonzero && ctx->inhom_any[1]);
-  if (assemble_system == 1 && ctx->tune.stored_uu == 0 && ctx->hang.active)
+  const bool mf_only = full && ctx->tune.stored_uu == 0 && !(use_nonzero && ctx->inhom_any[1]);
+  if (full && ctx->tune.stored_uu == 0 && ctx->hang.active)
     throw Error(IFEM_E_BADPARAM, "stored_uu = 0 with hanging-node constraints is not supported");
-  if (assemble_system == 1 && !mf_only) ensure_auu_values(ctx);
-  if (assemble_system == 1) ctx->uu_is_stored = !mf_only;
-  if (!assemble_system && !ctx->assembled) throw Error(IFEM_E_BADPARAM, "rhs-only assembly before any matrix assembly");
-  if (assemble_system == 1) { // state the matrix-free A_uu needs to reproduce this matrix (apply_mf.hip)
+  if (full && !mf_only) ensure_auu_values(ctx);
+  if (full) ctx->uu_is_stored = !mf_only;
+  if (mode == AsmMode::Rhs && !ctx->assembled) throw Error(IFEM_E_BADPARAM, "rhs-only assembly before any matrix assembly");
+  if (full) { // state the matrix-free A_uu needs to reproduce this matrix (apply_mf.hip)
     const size_t nu = size_t(dim) * size_t(ctx->nUl);
     if (ctx->mf_eval.n != nu) ctx->mf_eval.alloc(nu);
     if (imex) IFEM_HIP_CHECK(hipMemsetAsync(ctx->mf_eval.p, 0, nu * sizeof(double), s)); // no convection in the IMEX matrix
@@ -120,60 +115,39 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
     ctx->mf_valid = true;
     ctx->mf_noconv = imex != 0;
     ctx->asm_version++;
+    skip_geo = ctx->geo.reuse(geo_key, ctx->tune.geo_cache == 1, true);
   }
-  // B, B^T, M_p and diag(M_u) depend on the mesh and on WHICH dofs are constrained, not on the solution, the parameters
-  // or the inhomogeneities: an assembly whose constrained-dof set equals that of the previous one (zero_ and
-  // nonzero_constraints of make_constraints list the same dofs) keeps them (bit-identical to re-integrating
-  // them) and integrates A_uu and the right-hand side only.  ifem_tuning::geo_cache = 0 switches it off.
-  const int64_t geo_key = ctx->flag_id[use_nonzero ? 1 : 0];
-  bool skip_geo = ctx->tune.geo_cache == 1 && assemble_system && assemble_system != 3 && ctx->geo_valid && ctx->geo_key == geo_key;
-  // the unconstrained copies of B / B^T / S_m (19 + 4 GB at 128^3) only serve a CHANGE of the constrained-dof set (FSI steps): a run
-  // whose set has NEVER changed and has stood still for a few assemblies (pure-fluid runs) gives them back; a context that has seen
-  // a change (an FSI run: a new set every time step, several Newton assemblies in between) keeps them -- releasing them there would
-  // repeat a hipFree / hipMalloc / geometry launch every time step
-  if (assemble_system == 1) {
-    if (!skip_geo && ctx->geo_valid && ctx->geo_key != geo_key) ctx->geo_set_changes++;
-    ctx->geo_unchanged = skip_geo ? ctx->geo_unchanged + 1 : 0;
-    if (ctx->geo_unchanged == kGeoKeep && ctx->geo0_valid && ctx->geo_set_changes == 0) {
-      ctx->B0.release(); ctx->Bt0.release(); ctx->Sm0.release();
-      ctx->geo0_valid = false; ctx->sm0_valid = false;
-    }
-  }
+  bool mass = false; // M_p and diag(M_u) re-integrated by this assembly
   // A NEW constrained-dof set (every FSI step): the blocks are masked copies of the unconstrained ones, which are integrated
   // once per mesh (one geometry-only launch of the cell kernel without constraints); M_p and diag(M_u) do not depend on
   // the set at all.  Same values as re-integrating them under the new set (the kept entries are the same sums).
-  if (assemble_system && assemble_system != 3 && !skip_geo && ctx->tune.geo_cache) {
-    if (!ctx->geo0_valid) {
+  if ((full || level) && !skip_geo && ctx->tune.geo_cache) {
+    if (!ctx->geo.b0_valid) {
       ifem_ctx_unconstrained_geometry(ctx, p);
-      ctx->geo0_valid = true;
+      ctx->geo.b0_valid = true;
+      mass = true;
     }
     masked_geometry_blocks(ctx, use_nonzero);
-    ctx->geo_valid = true; ctx->geo_key = geo_key;
+    ctx->geo.valid = true; ctx->geo.key = geo_key;
     skip_geo = true;
-    if (geo_only) { // a multigrid level of S_m: nothing else to integrate
-      dinv_setup(ctx);
-      ctx->bbt_f32_valid = false;
-      ctx->sm_valid = false; ctx->sm_key = geo_key;
-      ctx->asm_constraint_set = use_nonzero ? 1 : 0;
-      return;
-    }
+    if (level) { level_geometry_epilogue(ctx, use_nonzero, mass); return; } // nothing else to integrate
   }
   // system_matrix = 0; mass_matrix = 0; system_rhs = 0  (:163-165)
   {
-  KScope ks_fill(ctx, IFEM_KC_ZERO_FILL, 8.0 * ((assemble_system && !geo_only && !mf_only ? double(ctx->Auu.val.n) : 0.0) + double(ctx->vec[IFEM_VEC_RHS].n) +
-                                                (assemble_system && !skip_geo ? double(ctx->Bt.val.n + ctx->B.val.n + ctx->Mp.val.n + ctx->diagMu.n) : 0.0)));
-  if (assemble_system) {
+  KScope ks_fill(ctx, IFEM_KC_ZERO_FILL, 8.0 * ((matrices && !geo_only && !mf_only ? double(ctx->Auu.val.n) : 0.0) + double(ctx->vec[IFEM_VEC_RHS].n) +
+                                                (matrices && !skip_geo ? double(ctx->Bt.val.n + ctx->B.val.n + ctx->Mp.val.n + ctx->diagMu.n) : 0.0)));
+  if (matrices) {
     // (a hand-written fill kernel with 16-byte non-temporal stores measures the same 15 ms for the 78 GB at 128^3)
     if (!geo_only && !mf_only) IFEM_HIP_CHECK(hipMemsetAsync(ctx->Auu.val.p, 0, ctx->Auu.val.n * sizeof(double), s));
     if (!skip_geo) {
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->Bt.val.p, 0, ctx->Bt.val.n * sizeof(double), s));
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->B.val.p, 0, ctx->B.val.n * sizeof(double), s));
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->Mp.val.p, 0, ctx->Mp.val.n * sizeof(double), s));
-      ctx->mp_f32_valid = false;
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->diagMu.p, 0, ctx->diagMu.n * sizeof(double), s));
+      mass = true;
     }
   }
-  if (ctx->want_shat && assemble_system) {
+  if (ctx->want_shat && matrices) {
     if (ctx->Shat.n != (size_t)ctx->Auu.nnzb) ctx->Shat.alloc((size_t)ctx->Auu.nnzb);
     IFEM_HIP_CHECK(hipMemsetAsync(ctx->Shat.p, 0, ctx->Shat.n * sizeof(double), s));
   }
@@ -190,7 +164,6 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   A.diagMu = ctx->diagMu.p; A.rhs = ctx->vec[IFEM_VEC_RHS].p;
   A.v_s = ctx->want_shat ? ctx->Shat.p : nullptr;
   const int w = use_nonzero ? 1 : 0;
-  const bool unconstrained = assemble_system == 3; // internal: the mesh-only blocks (ifem_ctx_unconstrained_geometry)
   A.is_c = (ctx->has_c[w] && !unconstrained) ? ctx->is_c[w].p : nullptr;
   A.cval = (ctx->has_c[w] && !unconstrained) ? ctx->cval[w].p : nullptr;
   A.use_inhom = (use_nonzero && ctx->has_c[1] && !unconstrained) ? 1 : 0;
@@ -199,7 +172,7 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   A.debug_skip = ctx->tune.asm_skip;
   A.xcd_swizzle = ctx->tune.xcd_swizzle;
   A.eval = ctx->vec[imex ? IFEM_VEC_PRESENT : IFEM_VEC_EVAL].p; A.present = ctx->vec[IFEM_VEC_PRESENT].p;
-  A.imex = imex; A.rhs_only = assemble_system && !mf_only ? 0 : 1;
+  A.imex = imex; A.rhs_only = matrices && !mf_only ? 0 : 1;
   if (mf_only && !skip_geo) throw Error(IFEM_E_BADPARAM, "stored_uu = 0 needs ifem_tuning::geo_cache >= 1 (the geometry blocks come from their own launch)");
   A.fsi_acc = ctx->indicator.p ? ctx->vec[IFEM_VEC_FSI_ACC].p : nullptr;
   A.mu = p->viscosity; A.rho = p->rho; A.gamma = p->grad_div; A.inv_dt = 1.0 / p->dt;
@@ -223,15 +196,9 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   }
   IFEM_HIP_CHECK(hipEventRecord(ctx->ev1, s));
   if (unconstrained) return; // the caller copies the blocks away
-  if (assemble_system) { ctx->geo_valid = true; ctx->geo_key = geo_key; }
-  if (geo_only) { // what the Schur complement of this level needs: 1/diag(M_u); S_m is stale if the blocks were re-integrated
-    dinv_setup(ctx);
-    ctx->bbt_f32_valid = false;
-    ctx->sm_valid = false; ctx->sm_key = geo_key;
-    ctx->asm_constraint_set = use_nonzero ? 1 : 0;
-    return;
-  }
-  if (assemble_system) assemble_epilogue(ctx, use_nonzero);
+  if (matrices) { ctx->geo.valid = true; ctx->geo.key = geo_key; }
+  if (level) { level_geometry_epilogue(ctx, use_nonzero, mass); return; }
+  if (full) assemble_epilogue(ctx, use_nonzero, mass);
   else {
     IFEM_HIP_CHECK(hipEventSynchronize(ctx->ev1));
     float ms = 0;
@@ -243,16 +210,23 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
 
 // B, B^T, M_p, diag(M_u) of the mesh alone: one geometry-only launch with no constraint set, B / B^T copied away
 static void ifem_ctx_unconstrained_geometry(ifem_ctx *ctx, const ifem_ins_params *p) {
-  launch_ins_assemble_ex(ctx, p, 0, 0, 3);
+  launch_ins_assemble_ex(ctx, p, 0, 0, AsmMode::Unconstrained);
   hipStream_t s = ctx->stream;
-  if (ctx->B0.n != ctx->B.val.n) ctx->B0.alloc(ctx->B.val.n);
-  if (ctx->Bt0.n != ctx->Bt.val.n) ctx->Bt0.alloc(ctx->Bt.val.n);
-  if (ctx->B.val.n) IFEM_HIP_CHECK(hipMemcpyAsync(ctx->B0.p, ctx->B.val.p, ctx->B.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  if (ctx->Bt.val.n) IFEM_HIP_CHECK(hipMemcpyAsync(ctx->Bt0.p, ctx->Bt.val.p, ctx->Bt.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  ctx->mp_f32_valid = false;
+  GeoCache &g = ctx->geo;
+  if (g.B0.n != ctx->B.val.n) g.B0.alloc(ctx->B.val.n);
+  if (g.Bt0.n != ctx->Bt.val.n) g.Bt0.alloc(ctx->Bt.val.n);
+  if (ctx->B.val.n) IFEM_HIP_CHECK(hipMemcpyAsync(g.B0.p, ctx->B.val.p, ctx->B.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (ctx->Bt.val.n) IFEM_HIP_CHECK(hipMemcpyAsync(g.Bt0.p, ctx->Bt.val.p, ctx->Bt.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
-static void assemble_epilogue(ifem_ctx *ctx, int use_nonzero) {
+// a multigrid level of S_m: what its Schur complement needs is 1/diag(M_u); S_m is stale if the blocks are another set's
+static void level_geometry_epilogue(ifem_ctx *ctx, int use_nonzero, bool mass) {
+  dinv_setup(ctx);
+  geometry_written(ctx, ctx->flag_id[use_nonzero ? 1 : 0], mass);
+  ctx->asm_constraint_set = use_nonzero ? 1 : 0;
+}
+
+static void assemble_epilogue(ifem_ctx *ctx, int use_nonzero, bool mass) {
   dinv_setup(ctx);
   if (!ctx->uu_is_stored) { ctx->asm_constraint_set = use_nonzero ? 1 : 0; uu_block_diag_mf(ctx); }
   else bjac_setup(ctx);
@@ -262,16 +236,9 @@ static void assemble_epilogue(ifem_ctx *ctx, int use_nonzero) {
   ctx->timing.assemble_kernel_ms = ms;
   ctx->assembled = true;
   ctx->has_app = false;
-  ctx->auu_f32_valid = false;
-  ctx->bbt_f32_valid = false;
-  // S_m = B diag(M_u)^-1 B^T depends only on the mesh and on WHICH dofs are constrained (not on the solution):
-  // keep it across assemblies until the constraint set changes (the reference rebuilds it every solve(); same values)
-  {
-    const int64_t key = ctx->flag_id[use_nonzero ? 1 : 0];
-    if (key != ctx->sm_key || ctx->tune.geo_cache != 1) { ctx->sm_valid = false; ctx->sm_key = key; }
-  }
+  uu_written(ctx);
+  geometry_written(ctx, ctx->flag_id[use_nonzero ? 1 : 0], mass);
   ctx->shat_valid = ctx->want_shat;
-  ctx->shat_aux_valid = false;
   ctx->asm_constraint_set = use_nonzero ? 1 : 0;
 }
 

@@ -468,17 +468,10 @@ void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonz
   else if (dim == 3 && ctx->kv == 1) launch_scns_t<3, 1>(ctx, A);
   else if (dim == 3 && ctx->kv == 2) launch_scns_t<3, 2>(ctx, A);
   else throw Error(IFEM_E_BADPARAM, "unsupported (dim, kv)");
+  scns_assembled(ctx);
   bjac_setup(ctx);
   ctx->assembled = true;
   ctx->has_app = true;
-  ctx->mf_valid = false;
-  ctx->auu_f32_valid = false;
-  ctx->bbt_f32_valid = false;
-  ctx->sm_valid = false; ctx->sm_key = -1;
-  ctx->shat_valid = false;
-  ctx->tpp_valid = false; ctx->tpp_ilu.factored = false;
-  ctx->b2_valid = false; ctx->pvv_ilu.factored = false; ctx->b2_ilu.factored = false;
-  ctx->geo_valid = false; // B / B^T now hold the SUPG-stabilised blocks
   ctx->asm_constraint_set = use_nonzero ? 1 : 0;
   hanging_condense_rhs(ctx, use_nonzero);
 }

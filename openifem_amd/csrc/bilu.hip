@@ -491,9 +491,10 @@ void rowsum_abs_inv(ifem_ctx *ctx, double *out) {
   const int64_t n = ctx->nUo;
   if (!n) return;
   KScope ks(ctx, IFEM_KC_TPP, double(ctx->Auu.val.n) * 8.0);
+  const double *A = stored_uu(ctx).p;
   const dim3 g(unsigned((n * 8 + 255) / 256)), b(256);
-  if (ctx->dim == 3) hipLaunchKernelGGL((k_rowsum_abs_inv<3>), g, b, 0, ctx->stream, n, ctx->Auu.rowptr.p, ctx->Auu.val.p, out);
-  else hipLaunchKernelGGL((k_rowsum_abs_inv<2>), g, b, 0, ctx->stream, n, ctx->Auu.rowptr.p, ctx->Auu.val.p, out);
+  if (ctx->dim == 3) hipLaunchKernelGGL((k_rowsum_abs_inv<3>), g, b, 0, ctx->stream, n, ctx->Auu.rowptr.p, A, out);
+  else hipLaunchKernelGGL((k_rowsum_abs_inv<2>), g, b, 0, ctx->stream, n, ctx->Auu.rowptr.p, A, out);
 }
 
 } // namespace ifem

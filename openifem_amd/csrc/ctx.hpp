@@ -76,6 +76,14 @@ struct DBuf { // owning device buffer
   }
 };
 
+// Lazily refreshed single-precision copy of a double array (the preconditioner-only consumers stream it): `refresh` converts the
+// source when the copy is stale; the invalidation events at the end of this file mark it stale when the source is rewritten
+struct F32Copy : DBuf<float> {
+  bool valid = false;
+  void stale() { valid = false; }
+  void refresh(const DBuf<double> &src, hipStream_t s, unsigned grid = 8192); // linalg.hip (k_to_f32)
+};
+
 // Row-planar block-CSR: row r owns blocks [rowptr[r], rowptr[r+1]); entry e (of BS per block) of the k-th
 // block of the row lives at val[BS*rowptr[r] + e*len_r + k].  Consecutive lanes (k) read consecutive
 // doubles for every e: fully coalesced without LDS staging.  BS = dim*dim (A_uu), dim (B, B^T) or 1.
@@ -284,6 +292,40 @@ struct Tabs3 {
 // permp[8] (the same for the pressure nodes) | srow[32] (position of the row's first block inside a 64-byte segment, in doubles) | padding
 constexpr int kAsm3Rec = 1024, kAsm3Hdr = 128;
 
+// B, B^T, M_p and diag(M_u) depend on the mesh and on WHICH dofs are constrained, nothing else (assemble.hip): the blocks of the last
+// constrained-dof set stay until the set changes.  The same blocks integrated WITHOUT any constraint (functions of the mesh alone) are
+// kept once built: the blocks of a new set are masked copies of them instead of a re-integration (M_p and diag(M_u) do not depend on
+// the set), and S_m of a new set is the S_m of these copies with the rows that touch a constrained dof recomputed (linalg.hip::schur_numeric).
+struct GeoCache {
+  // assemblies with an unchanged (and never yet changed) constrained-dof set after which the unconstrained copies (19 + 4 GB at 128^3) are
+  // given back: they only serve a CHANGE of the set.  A run whose set does change later (FSI: every time step) re-integrates them once and
+  // keeps them from then on -- releasing them there would repeat a hipFree / hipMalloc / geometry launch every time step.
+  static constexpr int kKeep = 2;
+  bool valid = false; // B, B^T, M_p, diag(M_u) hold the blocks of constrained-dof set `key`
+  int64_t key = -1;
+  DBuf<double> B0, Bt0, Sm0; // unconstrained B / B^T, S_m of them
+  bool b0_valid = false, sm0_valid = false;
+  int unchanged = 0;       // consecutive assemblies that kept the cached blocks
+  int set_changes = 0;     // times the constrained-dof set changed while blocks were cached
+  uint64_t seen_asm = 0;   // a multigrid level: the finest level's asm_version its `unchanged` last counted
+  int64_t refresh_stamp = -1; // a coarse multigrid level: the finest level's assembly its blocks were last refreshed for (geo_cache = 2)
+  // An assembly asks for the blocks of set `k`: true when the cached ones are still those (`may_reuse`: the caching mode allows it).
+  // `count`: the request belongs to a new assembly (a multigrid level is asked once per preconditioner application) -- the kKeep-th such
+  // hit of a run whose set never changed gives the unconstrained copies back.
+  bool reuse(int64_t k, bool may_reuse, bool count) {
+    if (!(may_reuse && valid && key == k)) {
+      if (valid && key != k) ++set_changes;
+      unchanged = 0;
+      return false;
+    }
+    if (count && ++unchanged == kKeep && b0_valid && set_changes == 0) {
+      B0.release(); Bt0.release(); Sm0.release();
+      b0_valid = sm0_valid = false;
+    }
+    return true;
+  }
+};
+
 } // namespace ifem
 
 struct ifem_ctx {
@@ -317,14 +359,11 @@ struct ifem_ctx {
   ifem_tuning tune{};    // ifem_set_tuning
   ifem::PlanarCsr Sm;  // mass_schur(1,1) = B diag(M_u)^-1 B^T, explicit (single rank only; empty otherwise)
   bool sm_valid = false;
-  ifem::DBuf<float> B_f32, Bt_f32; // single-precision copies for the matrix-free S_m of the approximate-preconditioner kinds
-  bool bbt_f32_valid = false;
+  int64_t sm_key = -1; // the constrained-dof set S_m was formed for
+  ifem::F32Copy B_f32, Bt_f32; // single-precision copies for the matrix-free S_m of the approximate-preconditioner kinds
   ifem::DBuf<double> xs_ext; // [halo.n_s_cols] input of the distributed S_m SpMV: owned entries + 2-deep far nodes
-  ifem::DBuf<float> Sm_f32; // single-precision copy of the S_m values for its SpMV (approximate-preconditioner kinds)
-  bool sm_f32_valid = false;
-  ifem::DBuf<float> Mp_f32; // the same for M_p (CG(M_p) of the preconditioner)
-  bool mp_f32_valid = false;
-  int64_t sm_key = -1;
+  ifem::F32Copy Sm_f32; // single-precision copy of the S_m values for its SpMV (approximate-preconditioner kinds)
+  ifem::F32Copy Mp_f32; // the same for M_p (CG(M_p) of the preconditioner)
   // identity of the constrained-dof SET of each AffineConstraints object (which dofs, not their values): B, B^T, M_p,
   // diag(M_u) and S_m depend on nothing else, so zero_ / nonzero_constraints with the same lines share one cache entry and
   // re-making identical constraints (time-dependent boundary values) keeps it
@@ -333,24 +372,11 @@ struct ifem_ctx {
   std::vector<uint8_t> seen_scratch; // ifem_set_constraints: duplicate detection over the local dofs, all zero between calls
   // scalar velocity operator S^ = mu K + rho C(u) + rho/dt M on the A_uu block pattern (IFEM_AINV_SCALAR_*)
   ifem::DBuf<double> Shat, shat_dinv;
-  ifem::DBuf<float> Shat_f32;
-  bool want_shat = false, shat_valid = false, shat_aux_valid = false;
+  ifem::F32Copy Shat_f32;
+  bool want_shat = false, shat_valid = false, shat_dinv_valid = false;
   int asm_constraint_set = 0;
-  bool geo_valid = false; // B, B^T, M_p, diag(M_u) hold the blocks of constraint set geo_key (assemble.hip)
-  int64_t geo_key = -1;
-  // the same blocks integrated WITHOUT any constraint (functions of the mesh alone), kept once built: the blocks of a new
-  // constrained-dof set are masked copies of them instead of a re-integration (M_p and diag(M_u) do not depend on the set)
-  ifem::DBuf<double> B0, Bt0;
-  bool geo0_valid = false;
-  int geo_unchanged = 0; // consecutive assemblies OF THE FINEST LEVEL that kept the cached blocks (assemble.hip: the copies are released at kGeoKeep = 2 ...)
-  int geo_set_changes = 0; // ... unless the constrained-dof set has ever changed after the first assembly (an FSI run): then they stay
-  uint64_t geo_seen_asm = 0; // a multigrid level: the finest level's asm_version its geo_unchanged last counted
-  // S_m of the unconstrained blocks (same mesh-only idea): a constrained-dof set only changes the rows whose B row touches a
-  // constrained dof, so S_m of a new set = this copy with those rows recomputed (linalg.hip::schur_numeric)
-  ifem::DBuf<double> Sm0;
-  bool sm0_valid = false;
+  ifem::GeoCache geo; // the geometry blocks of the last constrained-dof set and their unconstrained copies (assemble.hip)
   ifem::DBuf<int32_t> sm_rows;
-  int64_t geo_refresh_stamp = -1; // a coarse multigrid level: the finest level's assembly its blocks were last refreshed for
   ifem::Hanging hang; // hanging-node lines (hanging.hip)
   ifem::FsiState fsi; // solid + scratch of the device-side FSI inputs (fsi.hip)
   // multigrid (ifem_mg_attach): the next coarser level (not owned) and the pressure transfers to it; per-level state of
@@ -364,7 +390,7 @@ struct ifem_ctx {
   ifem::DBuf<uint8_t> mg_Pu_mask, mg_Ru_mask; // per weight 8 bytes: {column | components dropped by the Dirichlet flags of the two levels << 29, weight as float} (mg.hip::mg_csr_mask)
   bool uu_is_stored = true;                   // the last full assembly scattered A_uu (false: ifem_tuning::stored_uu = 0 took the matrix-free path)
   bool inhom_any[2] = {false, false};         // constraint object `which` carries a non-zero inhomogeneity somewhere (any rank)
-  uint64_t graph_epoch = 0;                   // bumped by ifem_set_tuning / ifem_set_profiling / ifem_mg_attach: part of every hipGraph replay key
+  uint64_t graph_epoch = 0;                   // bumped by ifem_set_tuning / ifem_set_profiling / ifem_mg_attach: solver.hip::graph_run adds it to every replay key
   int64_t mg_mask_key[2] = {-1, -1};          // constrained-dof sets (flag ids of this level and the coarser one) of the masks
   ifem::DBuf<double> sm_dinv, mg_vec[6], mgu_vec[5];
   ifem::DBuf<float> mguf_vec[5]; // single-precision level vectors of the A_uu V-cycle (solver.hip)
@@ -393,13 +419,12 @@ struct ifem_ctx {
   bool mf_valid = false;
   bool mf_noconv = false; // the assembled matrix has no convective terms (InsIMEX): the operator skips the second field group
   double mf_ms_total = 0;
-  ifem::DBuf<float> Auu_f32;   // single-precision copy of Auu.val for the inner (preconditioner-only) solver
-  bool auu_f32_valid = false, last_spmv_f32 = false;
+  ifem::F32Copy Auu_f32;   // single-precision copy of Auu.val for the inner (preconditioner-only) solver
+  bool last_spmv_f32 = false;
   ifem::DBuf<double> diagMu;   // diag of mass (0,0), per velocity dof (owned)
   ifem::DBuf<double> dinvMu;   // 1/diagMu
   ifem::DBuf<double> bjac;     // inverse diagonal node blocks of A_uu [nUo][dim*dim]
-  ifem::DBuf<float> bjac_f32;  // single-precision copy for the inner solver (built on first use after bjac_setup)
-  bool bjac_f32_valid = false;
+  ifem::F32Copy bjac_f32;  // single-precision copy for the inner solver (built on first use after bjac_setup)
   // scatter maps: position of the column inside the row, 0xFFFF = row not owned here
   ifem::DBuf<uint16_t> posUU, posUP, posPU, posPP;
   ifem::DBuf<int32_t> uu_diag_pos; // position of the diagonal block in every owned A_uu row (setup.hip::ensure_auu_values)
@@ -478,5 +503,55 @@ inline KScope::~KScope() {
   if (!k) return;
   if (--k->depth > 0) return;
   (void)hipEventRecord(k->ev[e1], s);
+}
+} // namespace ifem
+
+namespace ifem {
+// The stored A_uu values, for every reader outside the assembly: refused when no assembly stored them or the last full assembly
+// took the matrix-free path (ifem_tuning::stored_uu = 0) -- the array then still holds an older matrix.
+inline const DBuf<double> &stored_uu(const ifem_ctx *c) {
+  if (c->Auu.val.n == 0 || !c->uu_is_stored)
+    throw Error(IFEM_E_BADPARAM, "A_uu has no stored values (ifem_tuning::stored_uu = 0, or no assembly yet): this operation needs the block CSR");
+  return c->Auu.val;
+}
+
+// ---- Invalidation events: what goes stale when a writer rewrites device data.  Every writer names its write through one of these;
+// the derived data they list are rebuilt by their readers (F32Copy::refresh, shat_refresh, schur_numeric / sm_ensure, ...).
+
+// A_uu written: its stored values, or the matrix-free operator state of a stored_uu = 0 assembly.  The scalar operator S^ is
+// integrated by the same cell kernel: its Jacobi scaling and single-precision copy go with it.
+inline void uu_written(ifem_ctx *c) {
+  c->Auu_f32.stale();
+  c->Shat_f32.stale();
+  c->shat_dinv_valid = false;
+}
+// the inverse node blocks `bjac` written
+inline void bjac_written(ifem_ctx *c) { c->bjac_f32.stale(); }
+// an assembly left B, B^T, M_p, diag(M_u) holding the blocks of constrained-dof set `key` (re-integrated, masked or kept; `mass`: M_p
+// was re-integrated).  The single-precision copies of B / B^T are re-made once per assembly; S_m stays while the set stays
+// (ifem_tuning::geo_cache = 1; the reference rebuilds it every solve(), same values).
+inline void geometry_written(ifem_ctx *c, int64_t key, bool mass) {
+  c->B_f32.stale(); c->Bt_f32.stale();
+  if (mass) c->Mp_f32.stale();
+  if (key != c->sm_key || c->tune.geo_cache != 1) { c->sm_valid = false; c->sm_key = key; }
+}
+// S_m formed for the present blocks (explicit values, or the diagonal of its operator form)
+inline void sm_written(ifem_ctx *c) {
+  c->sm_valid = true;
+  c->Sm_f32.stale();
+  c->sm_version++;
+}
+// an SCnsIM assembly: A_uu, B and B^T hold the SUPG-stabilised blocks (the geometry cache no longer describes them), App is new.
+// S_m, the matrix-free and scalar operators of the INS assembly, T_pp and the three ILU(0) factorisations are stale.
+inline void scns_assembled(ifem_ctx *c) {
+  uu_written(c);
+  c->uu_is_stored = true;
+  c->B_f32.stale(); c->Bt_f32.stale();
+  c->sm_valid = false; c->sm_key = -1;
+  c->geo.valid = false;
+  c->mf_valid = false;
+  c->shat_valid = false;
+  c->tpp_valid = false; c->tpp_ilu.factored = false;
+  c->b2_valid = false; c->pvv_ilu.factored = false; c->b2_ilu.factored = false;
 }
 } // namespace ifem

@@ -18,7 +18,14 @@ void build_mf_cell_split(ifem_ctx *ctx); // several ranks: interior-first copy o
 
 // assemble.hip
 void launch_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero);
-void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, int assemble_system);
+// what one launch of the INS cell kernel integrates
+enum class AsmMode {
+  Rhs,           // the right-hand side only (the matrices stay as they are)
+  Full,          // A_uu (or its matrix-free state), B, B^T, M_p, diag(M_u) and the right-hand side
+  LevelGeometry, // B, B^T, M_p, diag(M_u) only: a multigrid level of the pressure Schur complement
+  Unconstrained, // the same without any constraint (the mesh-only blocks of ctx.hpp::GeoCache); called by the driver itself
+};
+void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode);
 // B, B^T, M_p, diag(M_u) only (multigrid levels of the pressure Schur complement): no A_uu, no right-hand side state
 void launch_ins_assemble_geometry(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero);
 

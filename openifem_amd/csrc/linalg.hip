@@ -273,13 +273,12 @@ __global__ void k_to_f32(int64_t n, const double *__restrict__ a, float *__restr
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) b[i] = float(a[i]);
 }
 
-// single-precision copy of the A_uu values for the inner (preconditioner-only) solver: same planar layout
-void auu_f32_refresh(ifem_ctx *ctx) {
-  if (ctx->auu_f32_valid) return;
-  const int64_t n = (int64_t)ctx->Auu.val.n;
-  if (ctx->Auu_f32.n != (size_t)n) ctx->Auu_f32.alloc(n);
-  if (n) hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, n, ctx->Auu.val.p, ctx->Auu_f32.p);
-  ctx->auu_f32_valid = true;
+void F32Copy::refresh(const DBuf<double> &src, hipStream_t s, unsigned grid) {
+  if (valid) return;
+  const int64_t n = (int64_t)src.n;
+  if (this->n != src.n) alloc(src.n);
+  if (n) hipLaunchKernelGGL(k_to_f32, dim3(grid), dim3(256), 0, s, n, src.p, p);
+  valid = true;
 }
 
 // algorithmic bytes of one planar-CSR product: values (vb bytes each) + 4-byte column index per block, row pointer + output
@@ -294,10 +293,10 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
   const int64_t n = rp_.n;
   const int32_t *rows = rp_.rows;
   if (n == 0) return;
-  if (ctx->Auu.val.n == 0) throw Error(IFEM_E_BADPARAM, "A_uu has no stored values (ifem_tuning::stored_uu = 0, or no assembly yet): this operation needs the block CSR");
+  const DBuf<double> &A = stored_uu(ctx);
   hipStream_t s = ctx->stream;
   const bool time_it = ctx->profile && xp == nullptr; // the A_uu-only launches of the inner solver: the dominant kernel
-  if (use_f32) auu_f32_refresh(ctx);
+  if (use_f32) ctx->Auu_f32.refresh(A, s); // single-precision copy for the inner (preconditioner-only) solver: same layout
   if (time_it) IFEM_HIP_CHECK(hipEventRecord(ctx->ev0, s));
   if (ctx->dim == 3 && !use_f32 && IFEM_UU_INTERLEAVED && ctx->tune.spmv_pipe) {
     const int rpb = 16; // rows per block = two per half-wave (measured at 128^3: 8 / 16 / 32 / 64 rows -> 14.4 / 14.4 / 15.1 / 16.0 ms)
@@ -305,7 +304,7 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
     {
       KScope ks(ctx, IFEM_KC_SPMV_UU, planar_bytes(ctx->Auu, n, 8, ctx->nUl, 24, 24));
       hipLaunchKernelGGL(k_spmv_uu_pipe, dim3(nb), dim3(256), size_t(2 * rpb) * sizeof(int64_t), s, n, ctx->Auu.rowptr.p, ctx->Auu.col.p,
-                         ctx->Auu.val.p, xu, yu, rows, rpb);
+                         A.p, xu, yu, rows, rpb);
     }
     if (xp && ctx->Bt.n_rows) { // + B^T x_p on the same rows
       KScope ks(ctx, IFEM_KC_SPMV_BBT, planar_bytes(ctx->Bt, n, 8, ctx->nPl, 8, 48));
@@ -321,7 +320,7 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
                        ctx->Auu.col.p, ctx->Auu_f32.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows); \
   else                                                                                                                 \
     hipLaunchKernelGGL((k_spmv_uu<3, G, double>), dim3(blocks_for_rows(n, G)), dim3(256), 0, s, n, ctx->Auu.rowptr.p,   \
-                       ctx->Auu.col.p, ctx->Auu.val.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows);
+                       ctx->Auu.col.p, A.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows);
     if (Gsel == 16) { IFEM_SPMV3(16) } else if (Gsel == 64) { IFEM_SPMV3(64) } else if (Gsel == 8) { IFEM_SPMV3(8) } else { IFEM_SPMV3(32) }
 #undef IFEM_SPMV3
   } else {
@@ -332,7 +331,7 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
                          ctx->Auu.col.p, ctx->Auu_f32.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows);
     else
       hipLaunchKernelGGL((k_spmv_uu<2, G, double>), dim3(blocks_for_rows(n, G)), dim3(256), 0, s, n, ctx->Auu.rowptr.p,
-                         ctx->Auu.col.p, ctx->Auu.val.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows);
+                         ctx->Auu.col.p, A.p, ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xu, xp, yu, rows);
   }
   ctx->last_spmv_f32 = use_f32;
   if (time_it) {
@@ -412,16 +411,14 @@ __global__ void k_node_scale(int64_t n_nodes, const double *__restrict__ d, cons
 
 void shat_refresh(ifem_ctx *ctx, bool f32) {
   if (!ctx->shat_valid) throw Error(IFEM_E_BADPARAM, "scalar operator not assembled: call ifem_set_ainv_kind before ifem_ins_assemble");
-  if (ctx->shat_aux_valid) return;
-  const int64_t n = ctx->nUo, nnz = (int64_t)ctx->Shat.n;
-  if (ctx->shat_dinv.n != (size_t)n) ctx->shat_dinv.alloc(n);
-  if (n) hipLaunchKernelGGL(k_csr_diag, dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n, ctx->Auu.rowptr.p,
-                            ctx->Auu.col.p, ctx->Shat.p, ctx->shat_dinv.p);
-  if (f32) {
-    if (ctx->Shat_f32.n != (size_t)nnz) ctx->Shat_f32.alloc(nnz);
-    if (nnz) hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, nnz, ctx->Shat.p, ctx->Shat_f32.p);
+  if (!ctx->shat_dinv_valid) {
+    const int64_t n = ctx->nUo;
+    if (ctx->shat_dinv.n != (size_t)n) ctx->shat_dinv.alloc(n);
+    if (n) hipLaunchKernelGGL(k_csr_diag, dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n, ctx->Auu.rowptr.p,
+                              ctx->Auu.col.p, ctx->Shat.p, ctx->shat_dinv.p);
+    ctx->shat_dinv_valid = true;
   }
-  ctx->shat_aux_valid = true;
+  if (f32) ctx->Shat_f32.refresh(ctx->Shat, ctx->stream);
 }
 
 // y_u = S^ x_u per component with the constrained dofs of set `cset` kept as scaled identity rows
@@ -491,13 +488,8 @@ void spmv_bt(ifem_ctx *ctx, const double *xp, double *yu) {
 // single-precision copies of B and B^T for the matrix-free S_m = B diag(M_u)^-1 B^T inside the approximate-preconditioner
 // kinds on several ranks (an explicit S_m would need a 2-deep pressure halo): rebuilt lazily after every assemble
 static void bbt_f32_refresh(ifem_ctx *ctx) {
-  if (ctx->bbt_f32_valid) return;
-  const int64_t nb = (int64_t)ctx->B.val.n, nt = (int64_t)ctx->Bt.val.n;
-  if (ctx->B_f32.n != (size_t)nb) ctx->B_f32.alloc(nb);
-  if (ctx->Bt_f32.n != (size_t)nt) ctx->Bt_f32.alloc(nt);
-  if (nb) hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, nb, ctx->B.val.p, ctx->B_f32.p);
-  if (nt) hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, nt, ctx->Bt.val.p, ctx->Bt_f32.p);
-  ctx->bbt_f32_valid = true;
+  ctx->B_f32.refresh(ctx->B.val, ctx->stream);
+  ctx->Bt_f32.refresh(ctx->Bt.val, ctx->stream);
 }
 void spmv_b_f32(ifem_ctx *ctx, const double *xu, double *yp) {
   const int64_t n = ctx->B.n_rows;
@@ -575,12 +567,7 @@ void spmv_mp(ifem_ctx *ctx, const double *xp, double *yp, int part, bool use_f32
   const RowPart rp_ = row_part(ctx->Mp, part);
   const int64_t n = rp_.n;
   if (n == 0) return;
-  if (use_f32 && !ctx->mp_f32_valid) {
-    const int64_t nv = (int64_t)ctx->Mp.val.n;
-    if (ctx->Mp_f32.n != (size_t)nv) ctx->Mp_f32.alloc(nv);
-    hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, nv, ctx->Mp.val.p, ctx->Mp_f32.p);
-    ctx->mp_f32_valid = true;
-  }
+  if (use_f32) ctx->Mp_f32.refresh(ctx->Mp.val, ctx->stream);
   const unsigned nb = blocks_for_rows(n, 8);
   KScope ks(ctx, IFEM_KC_SPMV_MP, planar_bytes(ctx->Mp, n, use_f32 ? 4 : 8, ctx->nPl, 8, 8));
   if (use_f32) hipLaunchKernelGGL((k_spmv_planar<1, 1, 8, float>), dim3(nb), dim3(256), 0, ctx->stream, n, ctx->Mp.rowptr.p, ctx->Mp.col.p, ctx->Mp_f32.p, xp, yp, rp_.rows);
@@ -757,14 +744,15 @@ void schur_numeric(ifem_ctx *ctx) {
   // With the unconstrained blocks at hand (assemble.hip: B / B^T are masked copies of them) only the rows whose B row touches
   // a constrained dof differ from the S_m of the unconstrained blocks: that one is formed once per mesh, a new set copies it
   // and recomputes the touched rows (a few per cent of them on a box with Dirichlet walls).
-  const bool partial = ctx->tune.geo_cache >= 1 && ctx->geo0_valid && ctx->geo_valid && ctx->B0.n == ctx->B.val.n;
+  GeoCache &g = ctx->geo;
+  const bool partial = ctx->tune.geo_cache >= 1 && g.b0_valid && g.valid && g.B0.n == ctx->B.val.n;
   if (partial) {
-    if (!ctx->sm0_valid) {
-      if (ctx->Sm0.n != ctx->Sm.val.n) ctx->Sm0.alloc(ctx->Sm.val.n);
-      launch_schur(ctx, n, nullptr, ctx->B0.p, ctx->Bt0.p, ctx->Sm0.p);
-      ctx->sm0_valid = true;
+    if (!g.sm0_valid) {
+      if (g.Sm0.n != ctx->Sm.val.n) g.Sm0.alloc(ctx->Sm.val.n);
+      launch_schur(ctx, n, nullptr, g.B0.p, g.Bt0.p, g.Sm0.p);
+      g.sm0_valid = true;
     }
-    IFEM_HIP_CHECK(hipMemcpyAsync(ctx->Sm.val.p, ctx->Sm0.p, ctx->Sm.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    IFEM_HIP_CHECK(hipMemcpyAsync(ctx->Sm.val.p, g.Sm0.p, ctx->Sm.val.n * sizeof(double), hipMemcpyDeviceToDevice, s));
     const int w = ctx->asm_constraint_set;
     if (ctx->has_c[w]) {
       DBuf<int64_t> flag;
@@ -777,9 +765,7 @@ void schur_numeric(ifem_ctx *ctx) {
     }
   } else
     launch_schur(ctx, n, nullptr, ctx->B.val.p, ctx->Bt.val.p, ctx->Sm.val.p);
-  ctx->sm_valid = true;
-  ctx->sm_f32_valid = false;
-  ctx->sm_version++;
+  sm_written(ctx);
 }
 
 // y = M x for a scalar matrix on the pattern of `M` with the values `val` (explicit T_pp on the pattern of S_m)
@@ -793,12 +779,7 @@ void spmv_planar_scalar(ifem_ctx *ctx, const PlanarCsr &M, const double *val, co
 
 void spmv_sm(ifem_ctx *ctx, const double *xp, double *yp, bool use_f32, int part) {
   if (ctx->Sm.n_rows == 0) return;
-  if (use_f32 && !ctx->sm_f32_valid) {
-    const int64_t nv = (int64_t)ctx->Sm.val.n;
-    if (ctx->Sm_f32.n != (size_t)nv) ctx->Sm_f32.alloc(nv);
-    hipLaunchKernelGGL(k_to_f32, dim3(8192), dim3(256), 0, ctx->stream, nv, ctx->Sm.val.p, ctx->Sm_f32.p);
-    ctx->sm_f32_valid = true;
-  }
+  if (use_f32) ctx->Sm_f32.refresh(ctx->Sm.val, ctx->stream);
   const RowPart rp_ = row_part(ctx->Sm, part);
   const int64_t n = rp_.n;
   if (n == 0) return;
@@ -1513,11 +1494,7 @@ __global__ void k_bjac_apply_f32(int64_t n_rows, const float *__restrict__ bj, c
 }
 // single-precision copy of the inverse node blocks (preconditioner-only consumers), refreshed after every bjac set-up
 const float *bjac_f32_ptr(ifem_ctx *ctx) {
-  if (!ctx->bjac_f32_valid && ctx->bjac.n) {
-    if (ctx->bjac_f32.n != ctx->bjac.n) ctx->bjac_f32.alloc(ctx->bjac.n);
-    hipLaunchKernelGGL(k_to_f32, dim3(vgrid((int64_t)ctx->bjac.n)), dim3(256), 0, ctx->stream, (int64_t)ctx->bjac.n, ctx->bjac.p, ctx->bjac_f32.p);
-    ctx->bjac_f32_valid = true;
-  }
+  ctx->bjac_f32.refresh(ctx->bjac, ctx->stream, vgrid((int64_t)ctx->bjac.n));
   return ctx->bjac_f32.p;
 }
 void bjac_apply_f32(ifem_ctx *ctx, const float *x, double *y) {
@@ -1532,23 +1509,24 @@ void bjac_apply_f32(ifem_ctx *ctx, const float *x, double *y) {
 }
 
 void bjac_setup(ifem_ctx *ctx) {
-  ctx->bjac_f32_valid = false;
+  bjac_written(ctx);
   const int64_t n = ctx->nUo;
   if (!n) return;
+  const double *A = stored_uu(ctx).p;
   KScope ks(ctx, IFEM_KC_SMOOTHER_SETUP, double(n) * ctx->dim * ctx->dim * 16.0);
   if (IFEM_UU_INTERLEAVED) {
     if (ctx->dim == 3)
       hipLaunchKernelGGL((k_bjac_setup_lds<3>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                         ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, ctx->Auu.val.p, ctx->bjac.p);
+                         ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, A, ctx->bjac.p);
     else
       hipLaunchKernelGGL((k_bjac_setup_lds<2>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                         ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, ctx->Auu.val.p, ctx->bjac.p);
+                         ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, A, ctx->bjac.p);
   } else if (ctx->dim == 3)
     hipLaunchKernelGGL((k_bjac_setup<3>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                       ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, ctx->Auu.val.p, ctx->bjac.p);
+                       ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, A, ctx->bjac.p);
   else
     hipLaunchKernelGGL((k_bjac_setup<2>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                       ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, ctx->Auu.val.p, ctx->bjac.p);
+                       ctx->Auu.rowptr.p, ctx->uu_diag_pos.p, A, ctx->bjac.p);
 }
 
 void bjac_apply(ifem_ctx *ctx, const double *x, double *y) {

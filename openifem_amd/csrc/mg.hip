@@ -276,7 +276,7 @@ void uu_block_diag_mf(ifem_ctx *ctx) {
   const int64_t n = ctx->nUo;
   const int dim = ctx->dim;
   if ((int64_t)ctx->bjac.n != n * dim * dim) ctx->bjac.alloc((size_t)n * dim * dim);
-  ctx->bjac_f32_valid = false;
+  bjac_written(ctx);
   if (!n) return;
   hipStream_t s = ctx->stream;
   KScope ks(ctx, IFEM_KC_SMOOTHER_SETUP, double(ctx->n_cells) * ctx->nu * dim * dim * 8.0 + double(n) * dim * dim * 24.0);

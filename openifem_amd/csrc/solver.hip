@@ -438,9 +438,7 @@ static void sm_ensure(SolveState &S) {
       sm_matrix_free(S, S.tp[1], S.tp[3], false);
       schur_probe_fill(c, col, S.tp[3]);
     }
-    c->sm_valid = true;
-    c->sm_f32_valid = false;
-    c->sm_version++;
+    sm_written(c);
   }
 }
 
@@ -475,9 +473,11 @@ static void sm_apply(SolveState &S, const double *x, double *y, bool lowp) {
 // the same buffers serve as ghost-extended pressure vectors for the transfers.
 // A fixed launch sequence on fixed buffers as a hipGraph (ctx.hpp::VcGraph): replayed while `key` -- every pointer, bound, parameter and count the
 // sequence's kernel arguments are made of -- stays what it was when the graph was captured.  A new key runs `body` eagerly once (whatever is
-// allocated or converted lazily inside exists afterwards) and is captured at its next occurrence.  Returns false when the runtime refused the
-// capture: the caller stops asking (body has run eagerly by then).
+// allocated or converted lazily inside exists afterwards) and is captured at its next occurrence.  The context's graph_epoch (a tuning or
+// profiling change) is part of every key.  Returns false when the runtime refused the capture: the caller stops asking (body has run eagerly
+// by then).
 static bool graph_run(ifem_ctx *c, ifem_ctx::VcGraph &G, std::vector<uint64_t> &key, const std::function<void()> &body) {
+  key.push_back(c->graph_epoch);
   if (G.exec && key == G.key) {
     if (hipGraphLaunch(G.exec, c->stream) == hipSuccess) { ++G.launches; return true; }
     (void)hipGetLastError(); // a replay the runtime refuses: give the graph up and run the sequence eagerly
@@ -562,9 +562,9 @@ static void mg_sm_setup(MgSm &M, int use_nonzero) {
       // (ifem_tuning::geo_cache = 2, "every assembly is a new constrained-dof set": once per assembly of the finest level,
       // not once per preconditioner application)
       ifem_ctx *f0 = M.L[0].ctx;
-      if (!(c->tune.geo_cache == 2 && c->geo_refresh_stamp == f0->asm_version)) {
+      if (!(c->tune.geo_cache == 2 && c->geo.refresh_stamp == f0->asm_version)) {
         launch_ins_assemble_geometry(c, S.P, use_nonzero);
-        c->geo_refresh_stamp = f0->asm_version;
+        c->geo.refresh_stamp = f0->asm_version;
       }
       sm_ensure(S);
     }
@@ -573,7 +573,7 @@ static void mg_sm_setup(MgSm &M, int use_nonzero) {
     // S_m in operator form (the finest level of a partition without the 2-deep pressure halo: unstructured strips): the smoother
     // needs its diagonal only, which the rows of B give; "valid" = the diagonal belongs to the present blocks
     const bool opform = !sm_is_explicit(S);
-    if (opform && !c->sm_valid) { c->sm_valid = true; c->sm_version++; }
+    if (opform && !c->sm_valid) sm_written(c);
     if (c->sm_mg_version == c->sm_version && c->sm_lmax > 0) continue;
     if ((int64_t)c->sm_dinv.n != c->nPo) c->sm_dinv.alloc((size_t)c->nPo);
     if (opform) {
@@ -688,7 +688,7 @@ static int pcg_mg_sm(MgSm &M, const double *b, double *x, double tol, int maxit,
       for (auto &v : lc->mg_vec) key_ptr(key, v.p);
       key_ptr(key, lc->sm_dinv.p); key_ptr(key, lc->Sm.val.p); key_ptr(key, lc->Sm_f32.p); key_ptr(key, lc->Sm.rowptr.p);
       key_ptr(key, lc->mg_Rp.col.p); key_ptr(key, lc->mg_Pp.col.p);
-      key.push_back(uint64_t(lc->nPo)); key.push_back(uint64_t(lc->sm_version)); key.push_back(uint64_t(lc->tune.sm_lanes)); key.push_back(uint64_t(lc->sm_f32_valid));
+      key.push_back(uint64_t(lc->nPo)); key.push_back(uint64_t(lc->sm_version)); key.push_back(uint64_t(lc->tune.sm_lanes)); key.push_back(uint64_t(lc->Sm_f32.valid));
       key_f64(key, lc->sm_lmax);
     }
     if (!graph_run(c, c->sm_graph, key, [&]() { mg_sm_vcycle(M, 0); })) { c->tune.vcycle_graph_cells = 0; graph_ok = false; }
@@ -1303,7 +1303,7 @@ void scns_refpc_setup(ifem_ctx *ctx, int verbose, bool *pvv_ok, bool *b2_ok) {
   throw Error(IFEM_E_BADPARAM, "scns_pc = 2 needs the block-interleaved A_uu layout");
 #endif
   if (!Iv.analysed) bilu_analyse(ctx, Iv, ctx->dim, ctx->nUo, ctx->Auu.rowptr.p, ctx->Auu.col.p);
-  *pvv_ok = Iv.factored ? !Iv.broken : bilu_factor(ctx, Iv, ctx->Auu.val.p);
+  *pvv_ok = Iv.factored ? !Iv.broken : bilu_factor(ctx, Iv, stored_uu(ctx).p);
   if (!*pvv_ok && verbose) fprintf(stderr, "[ifem] scns solve: ILU(0) of A_vv broke down: node-block Jacobi instead\n");
   const PlanarCsr &Pt = tpp_pattern(ctx);
   if (!ctx->b2_valid) {
@@ -1416,9 +1416,12 @@ int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_s
     if (!pa_graph_ok) { body(); return; }
     std::vector<uint64_t> key;
     for (const void *p : {(const void *)x, (const void *)y, (const void *)S.tp[1], (const void *)S.tp[4], (const void *)S.tu, (const void *)S.utmp,
-                          (const void *)ctx->pvv_ilu.LU.p, (const void *)ctx->pvv_ilu.t0.p, (const void *)ctx->b2_ilu.LU.p, (const void *)ctx->b2_ilu.t0.p,
                           (const void *)ctx->App.p, (const void *)ctx->B.val.p, (const void *)ctx->Bt.val.p})
       key_ptr(key, p);
+    for (const BIlu *I : {&ctx->pvv_ilu, &ctx->b2_ilu})
+      for (const void *p : {(const void *)I->rp.p, (const void *)I->col.p, (const void *)I->diag.p, (const void *)I->LU.p, (const void *)I->dinv.p,
+                            (const void *)I->t0.p, (const void *)I->t1.p, (const void *)I->t2.p})
+        key_ptr(key, p);
     key.push_back(uint64_t(ctx->tune.pvv_sweeps)); key.push_back(uint64_t(ctx->tune.b2pp_sweeps)); key.push_back(uint64_t(pvv_ok)); key.push_back(uint64_t(b2_ok));
     key.push_back(uint64_t(ctx->pvv_ilu.nnz)); key.push_back(uint64_t(ctx->b2_ilu.nnz));
     if (!graph_run(ctx, ctx->pa_graph, key, body)) pa_graph_ok = false;

@@ -828,6 +828,17 @@ def test_stored_uu_0_newton_loop_with_inhomogeneous_boundary_values():
         flow.run_one_step(True)
         v, p = flow.get_current_solution()
         out[stored] = (v.max(), p.max(), flow.last_newton())
+        if stored == 0:
+            # the last assembly of the loop was matrix-free: the block CSR still holds the first iteration's A_uu, and its readers refuse it
+            assert out[0][2][0] > 1, out
+            L, ctx = flow.L, flow.ctx
+            assert L.ifem_uu_vmult(ctx, capi.VEC_UPDATE, capi.VEC_RHS, 0) < 0 and b"stored" in L.ifem_last_error()
+            rp = np.zeros(L.ifem_n_local_dofs(ctx) + 1, np.int64)
+            assert L.ifem_export_csr(ctx, 0, rp.ctypes.data_as(C.c_void_p), None, None) == 0  # the pattern needs no values
+            col, val = np.zeros(int(rp.max()), np.int32), np.zeros(int(rp.max()))
+            args = (rp.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p))
+            assert L.ifem_export_csr(ctx, 0, *args) < 0 and b"stored" in L.ifem_last_error()
+            assert L.ifem_export_csr(ctx, 1, *args) == 0  # the mass matrix does not read A_uu
         flow.close()
     assert abs(out[0][0] - 0.374235) / 0.374235 < 1e-3 and abs(out[0][1] - 46.5226) / 46.5226 < 1e-3, out
     assert abs(out[0][0] - out[1][0]) <= 1e-5 * out[1][0] and abs(out[0][1] - out[1][1]) <= 1e-5 * out[1][1], out
