@@ -8,6 +8,10 @@ of SURVEY 8(d): present = analytic plane Poiseuille, evaluation point = present 
 vectors and mesh tables resident in HBM before the timed region.  Weak scaling: every GPU owns an n^3 block of the
 channel (n = 128 by default: config "3D channel flow 128^3 Q2/Q1" at N = 1, 256^3 at N = 8).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  Everything
+beyond the headline -- the true residual, the per-kernel pass and the roofline, the tuned / cold / matrix-free / time-step
+legs, the FSI and cylinder legs, the CPU baseline and bench_detail.json -- runs with --full only.
 """
 import argparse
 import ctypes as C
@@ -207,6 +211,14 @@ def emit(out):
     print(compact_line(out, detail), flush=True)
 
 
+def report(out, full):
+    """--full: emit (detail file, stderr and the line); a plain run prints the line alone"""
+    if full:
+        emit(out)
+    else:
+        print(compact_line(out), flush=True)
+
+
 def _cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -396,22 +408,24 @@ def bench_insimex(args, host):
     solver.synchronize()
     dt = (time.time() - t0) / args.steps
     st = solver.last_stats()
-    # one more step under the per-kernel-family event log: where the time step goes
-    solver.kprof_begin()
-    solver.run_one_step(False, False)
-    prof = solver.kprof_end()
-    fam = {k: v["ms"] for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]) if v["ms"] > 0.05}
-    emit({"metric": "DoF/s per InsIMEX time step (rhs assembly + solve), 3D Q2/Q1", "value": (n_u + n_p) / dt,
-          "unit": "DoF/s", "n_gpus": 1, "steps": args.steps, "warmup": 2, "ms_per_step": dt * 1e3,
-          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-          "config": {"workload": f"3D channel flow {n}^3 Q2/Q1, mpi_insimex steady-state time step", "n_dofs": n_u + n_p,
-                     "ainv_kind": args.ainv, "inner_rel": args.inner_rel, "inner_maxit": solver.opts.inner_maxit, "mg_smooth_u": solver.opts.mg_smooth_u,
-                     "outer_matrix_free": solver.opts.outer_matrix_free, "cg_mp_rel": solver.opts.mp_rel, "cg_sm_rel": solver.opts.sm_rel,
-                     "multigrid_levels": 1 + len(solver.mg_levels()),
-                     "fgmres_iters": st.fgmres_iters, "cg_mp_iters": st.cg_mp_iters, "cg_sm_iters": st.cg_sm_iters,
-                     "inner_iters": st.inner_iters, "t_cg_mp_ms": st.t_cg_mp_ms, "t_cg_sm_ms": st.t_cg_sm_ms, "t_ainv_ms": st.t_ainv_ms,
-                     "t_solve_ms": st.t_total_ms},
-          "roofline": {"kernel_ms_per_step": fam, "kernel_ms_sum": sum(v["ms"] for v in prof.values())}})
+    out = {"metric": "DoF/s per InsIMEX time step (rhs assembly + solve), 3D Q2/Q1", "value": (n_u + n_p) / dt,
+           "unit": "DoF/s", "n_gpus": 1, "steps": args.steps, "warmup": 2, "ms_per_step": dt * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"3D channel flow {n}^3 Q2/Q1, mpi_insimex steady-state time step", "n_dofs": n_u + n_p,
+                      "ainv_kind": args.ainv, "inner_rel": args.inner_rel, "inner_maxit": solver.opts.inner_maxit, "mg_smooth_u": solver.opts.mg_smooth_u,
+                      "outer_matrix_free": solver.opts.outer_matrix_free, "cg_mp_rel": solver.opts.mp_rel, "cg_sm_rel": solver.opts.sm_rel,
+                      "multigrid_levels": 1 + len(solver.mg_levels()),
+                      "fgmres_iters": st.fgmres_iters, "cg_mp_iters": st.cg_mp_iters, "cg_sm_iters": st.cg_sm_iters,
+                      "inner_iters": st.inner_iters, "t_cg_mp_ms": st.t_cg_mp_ms, "t_cg_sm_ms": st.t_cg_sm_ms, "t_ainv_ms": st.t_ainv_ms,
+                      "t_solve_ms": st.t_total_ms}}
+    if args.full:
+        # one more step under the per-kernel-family event log: where the time step goes
+        solver.kprof_begin()
+        solver.run_one_step(False, False)
+        prof = solver.kprof_end()
+        fam = {k: v["ms"] for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]) if v["ms"] > 0.05}
+        out["roofline"] = {"kernel_ms_per_step": fam, "kernel_ms_sum": sum(v["ms"] for v in prof.values())}
+    report(out, args.full)
 
 
 def extras(solver, capi, n_dofs, warm_ms):
@@ -597,22 +611,26 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cells", dest="n", type=int, default=128, help="cells per direction per GPU")
-    ap.add_argument("--cpu-cells", dest="cpu_n", default="32,64", help="cells per direction of the CPU baseline sample(s), comma separated (0 = skip; BASELINE.md section 3 plans 32 and 64: 14 s and 63 s on the 64 threads the sweep picks)")
-    ap.add_argument("--extras", type=int, default=1, help="N = 1 only: also measure cold_step (geometry blocks and S_m rebuilt, as the reference does every iteration) and time_step (a whole run_one_step Newton loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (off: the run times the steps and prints the line, nothing else): "
+                         "true residual, per-kernel pass and roofline, the side legs that --tuned / --extras / --fsi / --cylinder-legs "
+                         "select, the CPU baseline (--cpu-cells); the full record goes to bench_detail.json and stderr")
+    ap.add_argument("--cpu-cells", dest="cpu_n", default="32,64", help="with --full: cells per direction of the CPU baseline sample(s), comma separated (0 = skip; BASELINE.md section 3 plans 32 and 64: 14 s and 63 s on the 64 threads the sweep picks)")
+    ap.add_argument("--extras", type=int, default=1, help="with --full, N = 1 only: also measure cold_step (geometry blocks and S_m rebuilt, as the reference does every iteration) and time_step (a whole run_one_step Newton loop)")
     ap.add_argument("--inner-rel", type=float, default=None, help="relative residual target of the inner A_uu solve inside the preconditioner (the reference applies an exact LU there, mpi_insim.cpp:124-127)")
     ap.add_argument("--inner-rel-first", type=float, default=None, help="experiment (default: what InsIM::initialize_system sets, 5e-5 with multigrid levels): the same for the FIRST preconditioner application of a solve (0: as --inner-rel).  Measured at 128^3 (profiles/r02_inner_sweep.txt): with 1e-2 the outer FGMRES needs two iterations (relative residual 9.1e-4 after the first), with 5e-5 in the first application one (7.8e-5 <= 1e-4) for the same four inner iterations in total: 275 -> 239 ms per step; later applications (later Newton iterations need 3-5 outer iterations whatever the inner accuracy) keep the cheap setting")
     ap.add_argument("--ainv", type=int, default=None, help="IFEM_AINV_* kind of the A_uu^-1 replacement (4 = matrix-free operator + geometric multigrid V-cycle, 3 = matrix-free inner operator + block Jacobi, 1 = fp32 inner matrix, 0 = fp64 matrix)")
     ap.add_argument("--sm-rel", type=float, default=None, help="experiment: relative tolerance of CG(S_m) inside the preconditioner (reference and default: 1e-3)")
     ap.add_argument("--mp-rel", type=float, default=None, help="experiment: relative tolerance of CG(M_p) inside the preconditioner (reference and default: 1e-6)")
     ap.add_argument("--inner-restart", type=int, default=None, help="restart length of the inner GMRES of the A_uu^-1 replacement (measured at 128^3: 8/10/12/15/20/30/45 -> 557/533/537/518/522/531/543 ms per step; 16 = one multi-dot pass of the single-precision basis; the library default is 30)")
-    ap.add_argument("--tuned", type=int, default=1, help="also time the relaxed-preconditioner variant (reported as tuned_preconditioner, N = 1 only)")
+    ap.add_argument("--tuned", type=int, default=1, help="with --full: also time the relaxed-preconditioner variant (reported as tuned_preconditioner, N = 1 only)")
     ap.add_argument("--mg", type=int, default=1, help="1 (default): attach the chain of coarser (semi-coarsened) box meshes so that CG(S_m) inside the preconditioner is multigrid-preconditioned; 0: plain CG as in the reference")
     ap.add_argument("--inner-maxit", type=int, default=None, help="cap of the inner A_uu iterations (--ainv 4: 0 = exactly one V-cycle)")
     ap.add_argument("--mg-smooth-u", type=int, default=None, help="smoothing steps of the A_uu V-cycle (--ainv 4)")
     ap.add_argument("--mg-post-u", type=int, default=None, help="smoothing steps after the coarse correction of the A_uu V-cycle (default: as before it)")
     ap.add_argument("--mg-ratio-u", type=float, default=None, help="Chebyshev interval ratio of the A_uu V-cycle (--ainv 4)")
     ap.add_argument("--tune", action="append", default=[], help="experiment: ifem_tuning field=value (e.g. --tune spmv_pipe=0), applied to every multigrid level")
-    ap.add_argument("--fsi", type=int, default=32, help="N = 1 only: also time the device-side FSI inputs (FSI::update_indicator + find_fluid_bc, csrc/fsi.hip) on the bench mesh with a 24x12x12-cell solid, and the oracle's restatement on the CPU at this many cells per direction (0 = skip the leg)")
+    ap.add_argument("--fsi", type=int, default=32, help="with --full, N = 1 only: also time the device-side FSI inputs (FSI::update_indicator + find_fluid_bc, csrc/fsi.hip) on the bench mesh with a 24x12x12-cell solid, and the oracle's restatement on the CPU at this many cells per direction (0 = skip the leg)")
     ap.add_argument("--seed", type=int, default=1234, help="seed of the perturbation of the timed state")
     ap.add_argument("--rel", type=float, default=1e-3, help="relative amplitude of the perturbation of the timed state")
     ap.add_argument("--mg-min-cells", type=int, default=0, help="multigrid levels: a direction is halved only while it keeps this many cells per rank (0: the host mirror's default, 4)")
@@ -629,7 +647,7 @@ def main():
                          "reference's cylinder drivers on the host mirror with the reference .prm; cylinder3d: the extruded cylinder of "
                          "GridCreator<3>::flow_around_cylinder at --refinements (3: 0.43 M cells, 11 M DoF) -- tools/cylbench.py")
     ap.add_argument("--refinements", type=int, default=3, help="global refinements of the cylinder workloads (the reference's .prm: 3)")
-    ap.add_argument("--cylinder-legs", type=int, default=1, help="N = 1 only: append the cylinder workloads (configs 2 and 4, and the 3D "
+    ap.add_argument("--cylinder-legs", type=int, default=1, help="with --full, N = 1 only: append the cylinder workloads (configs 2 and 4, and the 3D "
                                                                  "cylinder at 3 refinements) to the channel line as side measurements")
     ap.add_argument("--solver", default="insim", choices=["insim", "insimex"],
                     help="insim (default, the BASELINE metric): one Newton iteration of MPI::InsIM; insimex: one steady-state "
@@ -681,7 +699,7 @@ def main():
             raise SystemExit("the cylinder workloads run on one GPU (the host mirror cuts unstructured meshes into strips: tools/cyl_ranks.py)")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import cylbench
-        emit(cylbench.run(args.workload, args.refinements, steps=max(args.steps, 1), device=local_rank))
+        report(cylbench.run(args.workload, args.refinements, steps=max(args.steps, 1), device=local_rank, kernels=args.full), args.full)
         return
     if args.solver == "insimex":
         return bench_insimex(args, host)
@@ -764,9 +782,10 @@ def main():
     if args.dump_outputs:  # before anything else touches the vectors of the last timed step
         dump_outputs(args.dump_outputs, solver, last, dist, rank)
     comm = solver.comm_stats(reset=True)  # exchanges / all-reduces of the K timed steps (all multigrid levels)
-    # the TRUE residual of the last timed solve, recomputed with the assembled operator (collective; outside the timed region)
-    true_res, rhs_norm = solver.true_residual()
-    solver.comm_stats(reset=True)
+    if args.full:
+        # the TRUE residual of the last timed solve, recomputed with the assembled operator (collective; outside the timed region)
+        true_res, rhs_norm = solver.true_residual()
+        solver.comm_stats(reset=True)
     if args.dump_update:
         import numpy as np
         t = solver.partition_tables()
@@ -783,66 +802,21 @@ def main():
     asm_kernel_ms /= max(args.steps, 1)
     ms_per_step = elapsed / args.steps * 1e3
     hbm_used_gb = _hbm_used_gb()  # of this rank's device, after the timed steps (the steady state of the step)
-    # ---- per-kernel pass (outside the timed region): more steps with an event pair around every launch wrapper on the context
-    # stream (ifem_kprof: nothing waits until the end of the pass, so the queue runs ahead of the host as in the timed steps)
-    prof_steps = 2
-    solver.kprof_begin()
-    tp0 = time.time()
-    for _ in range(prof_steps):
-        step()
-    solver.synchronize()
-    prof_wall_ms = (time.time() - tp0) / prof_steps * 1e3
-    prof = solver.kprof_end()
-    # device memory once the run has settled: the unconstrained copies of B / B^T / S_m (kept for a change of the constrained-dof set) are
-    # given back at the second cached assembly of a never-changed set on every level (assemble.hip)
-    hbm_steady_gb = _hbm_used_gb()
+    if args.full:
+        # ---- per-kernel pass (outside the timed region): more steps with an event pair around every launch wrapper on the context
+        # stream (ifem_kprof: nothing waits until the end of the pass, so the queue runs ahead of the host as in the timed steps)
+        prof_steps = 2
+        solver.kprof_begin()
+        tp0 = time.time()
+        for _ in range(prof_steps):
+            step()
+        solver.synchronize()
+        prof_wall_ms = (time.time() - tp0) / prof_steps * 1e3
+        prof = solver.kprof_end()
+        # device memory once the run has settled: the unconstrained copies of B / B^T / S_m (kept for a change of the constrained-dof set) are
+        # given back at the second cached assembly of a never-changed set on every level (assemble.hip)
+        hbm_steady_gb = _hbm_used_gb()
     if rank == 0:
-        kernels = kernel_table(prof, prof_steps, n, world)
-        kernel_ms_sum = sum(k["ms_per_step"] for k in kernels)
-        cached = args.warmup >= 1  # the timed steps keep B, B^T, M_p, diag(M_u), S_m of the warm-up (same constrained-dof set)
-        models = kernel_models(solver.L, solver.ctx, n_cells, n_u, n_p, cached_blocks=cached)
-        by_fam = {k["family"]: k for k in kernels}
-        # dominant kernel = the family with the largest time per step; the assembly's launch time is the live HIP-event
-        # measurement of the TIMED steps (ifem_timing::assemble_kernel_ms), the others come from the profiled steps
-        dom = kernels[0]["family"] if kernels else "assemble_cells"
-        if dom == "assemble_cells" or asm_kernel_ms >= kernels[0]["ms_per_step"]:
-            ms = asm_kernel_ms
-            nb, nf = models["asm"]
-            gbs, tfs = nb / (ms * 1e-3) / 1e9, nf / (ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": tfs, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tfs / FP64_PEAK_TFLOPS,
-                    "kernel": "k_ins_assemble3 (one wavefront per cell: sum-factorised front, FP64 MFMA contraction, row-image atomic scatter)",
-                    "traffic": pmc_traffic("k_ins_assemble3", n, "f64_cached" if cached else "f64"),
-                    "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the 128^3 launch on one GPU"
-                                      + ("" if world == 1 else " (single-rank pass; the per-rank launch of this run is the same kernel on the same block size)"),
-                    "launch_ms": ms, "launches_timed": args.steps, "algorithmic_bytes": nb, "algorithmic_flops": nf,
-                    "hbm_frac": gbs / HBM_PEAK_GBS, "compute_frac": tfs / FP64_PEAK_TFLOPS, "compute_peak": "FP64 MFMA"}
-            # what actually bounds this kernel: the memory-side rate of its f64 atomic requests.  One atomic per
-            # (cell, dof pair) of the velocity-velocity block; the unit retires ~24 G requests of up to 64 bytes per second
-            # whatever the lane count (tools/atomics_types.hip: 23.9 G/s f64, 188 G atomics/s only when 8 lanes share a
-            # segment); the kernel's staged scatter touches 871 segments per cell (tools/scatter_sim.py, CPU replay)
-            n_atom = float(n_cells) * (27 * 3) ** 2
-            n_seg = float(n_cells) * 871.0
-            roof.update({"atomic_adds": n_atom, "atomic_rate_gatom_s": n_atom / (ms * 1e-3) / 1e9, "atomic_peak_gatom_s": 188.0,
-                         "atomic_frac": n_atom / (ms * 1e-3) / 1e9 / 188.0,
-                         "atomic_segments": n_seg, "atomic_segment_rate_g_s": n_seg / (ms * 1e-3) / 1e9, "atomic_segment_peak_g_s": 24.0,
-                         "atomic_segment_frac": n_seg / (ms * 1e-3) / 1e9 / 24.0})
-        else:
-            k = kernels[0]
-            if "compute_frac" in k and k["compute_frac"] >= k["hbm_frac"]:
-                roof = {"bound": "mfma", "achieved": k["tflop_s"], "peak": COMPUTE_PEAK[dom][1], "unit": "TFLOP/s", "frac": k["compute_frac"]}
-            else:
-                roof = {"bound": "hbm", "achieved": k["gb_s"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": k["hbm_frac"]}
-            roof.update({"kernel": k["kernel"], "traffic": k.get("traffic"), "launch_ms": k["ms_per_step"] / max(k["launches_per_step"], 1),
-                         "launches_timed": k["launches_per_step"] * prof_steps, "algorithmic_bytes": k["algorithmic_bytes"],
-                         "algorithmic_flops": k["algorithmic_flops"]})
-        mfk = by_fam.get("mf_cell", {})
-        mf_calls, mf_ms = mfk.get("launches_per_step", 0), mfk.get("ms_per_step", 0.0)
-        roof.update({"kernels": kernels, "kernel_ms_sum": kernel_ms_sum, "profiled_step_ms": prof_wall_ms,
-                     "unattributed_ms": ms_per_step - kernel_ms_sum,
-                     "kernels_note": "one entry per kernel family of the step, from HIP event pairs around every launch wrapper over "
-                                     f"{prof_steps} profiled steps after the timed region (include/ifem_hip.h: ifem_kprof_begin / _end); "
-                                     "unattributed_ms = ms_per_step - kernel_ms_sum: host launch gaps and the waits for reduction results",
-                     "kernel_ms_per_step": {k["family"]: k["ms_per_step"] for k in kernels}})
         out = {
             "metric": "DoF/s per Newton step (assemble+solve), 3D INS Q2/Q1",
             "value": n_dofs_global / (elapsed / args.steps),
@@ -855,8 +829,7 @@ def main():
                                    f"(plane Poiseuille + seeded 1e-3 perturbation), {n}^3 cells per GPU",
                        "n_dofs": n_dofs_global, "cells_per_gpu": n_cells, "parallelism": f"dd{world}",
                        "assemble_ms": t_asm / args.steps * 1e3, "solve_ms": t_solve / args.steps * 1e3,
-                       "assemble_kernel_ms": asm_kernel_ms, "setup_s": t_setup, "hbm_used_gb": hbm_used_gb, "hbm_used_gb_steady": hbm_steady_gb,
-                       "true_rel_residual": true_res / rhs_norm if rhs_norm > 0 else None, "fgmres_rel_residual": last.fgmres_res / rhs_norm if rhs_norm > 0 else None,
+                       "assemble_kernel_ms": asm_kernel_ms, "setup_s": t_setup, "hbm_used_gb": hbm_used_gb,
                        "fgmres_rel_tol": solver.opts.fgmres_rel, "seed": args.seed, "perturbation": args.rel,
                        "rccl_nranks": comm["rccl_nranks"], "comm_transport": {0: "none (single rank)", 1: "rccl", 2: "local world"}[comm["transport"]],
                        "halo_neighbors": comm["n_neighbors"], "halo_stream": comm["halo_stream"],
@@ -868,93 +841,134 @@ def main():
                                        "inner_rel_first": solver.opts.inner_rel_first, "source": "InsIM::initialize_system defaults" if not overridden else "overridden: " + ",".join(overridden)},
                        "solver_opts_overridden": overridden,
                        "t_cg_mp_ms": last.t_cg_mp_ms, "t_cg_sm_ms": last.t_cg_sm_ms, "t_ainv_ms": last.t_ainv_ms,
-                       "mf_apply_ms": mf_ms / max(mf_calls, 1), "mf_applies": mf_calls,
                        "sm_multigrid_levels": int(last.sm_mg_levels),
                        "coarse_levels": [list(r) for r, _ in solver.mg_levels()],
                        "hierarchy": "csrc/host/insim.cpp::attach_multigrid_levels (C++ host mirror)"},
-            "roofline": roof,
         }
         out["config"].update({"cg_mp_rel": solver.opts.mp_rel, "cg_sm_rel": solver.opts.sm_rel})
-        # Side measurement, never `value`: the same Newton step with the accuracy knobs of the PRECONDITIONER relaxed
-        # (pressure CG solves to 1e-2 / 1e-1 instead of the reference's 1e-6 / 1e-3) and the u-u block of the outer operator
-        # applied matrix-free.  The outer FGMRES still stops at the reference's 1e-4 ||rhs|| on the same operator.
-        if world == 1 and args.tuned and args.sm_rel is None and args.mp_rel is None and not solver.opts.outer_matrix_free:
-            keep = (solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free)
-            solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free = 1e-2, 1e-1, 1
-            step()
-            fence()
-            t0 = time.time()
-            for _ in range(args.steps):
-                st = step()
-            solver.synchronize()
-            dt_t = (time.time() - t0) / args.steps
-            out["tuned_preconditioner"] = {"ms_per_step": dt_t * 1e3, "value": n_dofs_global / dt_t, "unit": "DoF/s",
-                                           "fgmres_iters": st.fgmres_iters, "cg_mp_rel": 1e-2, "cg_sm_rel": 1e-1, "outer_matrix_free": 1,
-                                           "note": "side measurement; `value` above uses the reference's tolerances"}
-            solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free = keep  # the legs below use the reference's again
-        if world == 1 and args.extras:
-            out.update(extras(solver, capi, n_dofs_global, ms_per_step))
-            # the three figures side by side: `value` keeps B, B^T, M_p, diag(M_u), S_m of the previous iteration
-            # (same constrained-dof set) and is the FIRST Newton iteration of a step; value_cold re-integrates / re-forms them
-            # inside the step as the reference does in every iteration; value_sustained = DoF x Newton iterations / time of a
-            # whole run_one_step loop from the same state (later iterations need more FGMRES iterations)
-            if "cold_step" in out:
-                out["value_cold"] = out["cold_step"]["value"]
-            if "dofs_per_s_per_iteration" in out.get("time_step", {}):
-                out["value_sustained"] = out["time_step"]["dofs_per_s_per_iteration"]
-            if "value" in out.get("matrix_free_step", {}):
-                out["value_matrix_free"] = out["matrix_free_step"]["value"]
-        if world == 1 and args.fsi:
-            # side measurement, last device leg: its Dirichlet-mode call edits the constraint sets of the context
-            try:
-                sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-                import fsibench
-                solid = fsibench.make_solid3d()
-                leg = fsibench.device_leg(solver.L, solver.ctx, capi, n_cells, solid)
-                leg["cpu_baseline"] = fsibench.cpu_leg(args.fsi, solid)
-                out["fsi_inputs"] = leg
-            except Exception as e:  # a side leg must not take the headline line with it
-                out["fsi_inputs"] = {"error": repr(e)}
-        if world == 1 and args.cylinder_legs:
-            # side measurements (configs 2 and 4 report DoF/s too; VERDICT r4 item 5: the cell kernel on an unstructured 3D
-            # mesh of scale).  The channel's contexts are released first: the 3D cylinder needs ~40 GB of its own.
-            try:
-                solver.close()
-                sys.path.insert(0, os.path.join(ROOT, "tools"))
-                import cylbench
-                legs = {}
-                for w, r in (("cylinder2d", 3), ("cylinder2d_scnsim", 3), ("cylinder3d", 3)):
-                    o = cylbench.run(w, r, steps=2, device=local_rank)
-                    legs[w] = {"value": o["value"], "unit": o["unit"], "ms_per_step": o["ms_per_step"], "config": o["config"]}
-                    if "roofline" in o and "assemble3_unstructured" in o["roofline"]:
-                        legs[w]["assemble3_unstructured"] = o["roofline"]["assemble3_unstructured"]
-                        legs[w]["kernel_ms_per_step"] = {k["family"]: k["ms_per_step"] for k in o["roofline"]["kernels"]}
-                out["cylinder_workloads"] = legs
-            except Exception as e:  # a side leg must not take the headline line with it
-                out["cylinder_workloads"] = {"error": repr(e)}
-        cpu_sizes = [int(v) for v in str(args.cpu_n).split(",") if int(v) > 0]
-        cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), "ifem_cpu_baseline_n1.json")
-        if cpu_sizes and world == 1:  # the CPU baseline is a rank-0, N = 1 measurement
-            out["cpu_baseline"] = cpu_baseline(cpu_sizes)
-            try:  # the N > 1 runs that follow on this host quote it instead of repeating it
-                with open(cache, "w") as f:
-                    json.dump(dict(out["cpu_baseline"], measured_unix_time=time.time()), f)
-            except OSError:
-                pass
-        elif world > 1:
-            # measured on rank 0 at N = 1 only: an N > 1 line names the N = 1 sample it re-uses -- the one the --gpus 1 run left on
-            # this host, else the committed one of the round's single-GPU run (profiles/cpu_baseline_n1.json)
-            for path, origin in ((cache, "the --gpus 1 run of this bench on this host"),
-                                 (os.path.join(ROOT, "profiles", "cpu_baseline_n1.json"), "committed sample of the round's 1-GPU run (profiles/cpu_baseline_n1.json)")):
+        if args.full:
+            kernels = kernel_table(prof, prof_steps, n, world)
+            kernel_ms_sum = sum(k["ms_per_step"] for k in kernels)
+            cached = args.warmup >= 1  # the timed steps keep B, B^T, M_p, diag(M_u), S_m of the warm-up (same constrained-dof set)
+            models = kernel_models(solver.L, solver.ctx, n_cells, n_u, n_p, cached_blocks=cached)
+            by_fam = {k["family"]: k for k in kernels}
+            # dominant kernel = the family with the largest time per step; the assembly's launch time is the live HIP-event
+            # measurement of the TIMED steps (ifem_timing::assemble_kernel_ms), the others come from the profiled steps
+            dom = kernels[0]["family"] if kernels else "assemble_cells"
+            if dom == "assemble_cells" or asm_kernel_ms >= kernels[0]["ms_per_step"]:
+                ms = asm_kernel_ms
+                nb, nf = models["asm"]
+                gbs, tfs = nb / (ms * 1e-3) / 1e9, nf / (ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "achieved": tfs, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tfs / FP64_PEAK_TFLOPS,
+                        "kernel": "k_ins_assemble3 (one wavefront per cell: sum-factorised front, FP64 MFMA contraction, row-image atomic scatter)",
+                        "traffic": pmc_traffic("k_ins_assemble3", n, "f64_cached" if cached else "f64"),
+                        "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the 128^3 launch on one GPU"
+                                          + ("" if world == 1 else " (single-rank pass; the per-rank launch of this run is the same kernel on the same block size)"),
+                        "launch_ms": ms, "launches_timed": args.steps, "algorithmic_bytes": nb, "algorithmic_flops": nf,
+                        "hbm_frac": gbs / HBM_PEAK_GBS, "compute_frac": tfs / FP64_PEAK_TFLOPS, "compute_peak": "FP64 MFMA"}
+                # what actually bounds this kernel: the memory-side rate of its f64 atomic requests.  One atomic per
+                # (cell, dof pair) of the velocity-velocity block; the unit retires ~24 G requests of up to 64 bytes per second
+                # whatever the lane count (tools/atomics_types.hip: 23.9 G/s f64, 188 G atomics/s only when 8 lanes share a
+                # segment); the kernel's staged scatter touches 871 segments per cell (tools/scatter_sim.py, CPU replay)
+                n_atom = float(n_cells) * (27 * 3) ** 2
+                n_seg = float(n_cells) * 871.0
+                roof.update({"atomic_adds": n_atom, "atomic_rate_gatom_s": n_atom / (ms * 1e-3) / 1e9, "atomic_peak_gatom_s": 188.0,
+                             "atomic_frac": n_atom / (ms * 1e-3) / 1e9 / 188.0,
+                             "atomic_segments": n_seg, "atomic_segment_rate_g_s": n_seg / (ms * 1e-3) / 1e9, "atomic_segment_peak_g_s": 24.0,
+                             "atomic_segment_frac": n_seg / (ms * 1e-3) / 1e9 / 24.0})
+            else:
+                k = kernels[0]
+                if "compute_frac" in k and k["compute_frac"] >= k["hbm_frac"]:
+                    roof = {"bound": "mfma", "achieved": k["tflop_s"], "peak": COMPUTE_PEAK[dom][1], "unit": "TFLOP/s", "frac": k["compute_frac"]}
+                else:
+                    roof = {"bound": "hbm", "achieved": k["gb_s"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": k["hbm_frac"]}
+                roof.update({"kernel": k["kernel"], "traffic": k.get("traffic"), "launch_ms": k["ms_per_step"] / max(k["launches_per_step"], 1),
+                             "launches_timed": k["launches_per_step"] * prof_steps, "algorithmic_bytes": k["algorithmic_bytes"],
+                             "algorithmic_flops": k["algorithmic_flops"]})
+            mfk = by_fam.get("mf_cell", {})
+            mf_calls, mf_ms = mfk.get("launches_per_step", 0), mfk.get("ms_per_step", 0.0)
+            roof.update({"kernels": kernels, "kernel_ms_sum": kernel_ms_sum, "profiled_step_ms": prof_wall_ms,
+                         "unattributed_ms": ms_per_step - kernel_ms_sum,
+                         "kernels_note": "one entry per kernel family of the step, from HIP event pairs around every launch wrapper over "
+                                         f"{prof_steps} profiled steps after the timed region (include/ifem_hip.h: ifem_kprof_begin / _end); "
+                                         "unattributed_ms = ms_per_step - kernel_ms_sum: host launch gaps and the waits for reduction results",
+                         "kernel_ms_per_step": {k["family"]: k["ms_per_step"] for k in kernels}})
+            out["config"].update({"hbm_used_gb_steady": hbm_steady_gb, "mf_apply_ms": mf_ms / max(mf_calls, 1), "mf_applies": mf_calls,
+                                  "true_rel_residual": true_res / rhs_norm if rhs_norm > 0 else None,
+                                  "fgmres_rel_residual": last.fgmres_res / rhs_norm if rhs_norm > 0 else None})
+            out["roofline"] = roof
+            # Side measurement, never `value`: the same Newton step with the accuracy knobs of the PRECONDITIONER relaxed
+            # (pressure CG solves to 1e-2 / 1e-1 instead of the reference's 1e-6 / 1e-3) and the u-u block of the outer operator
+            # applied matrix-free.  The outer FGMRES still stops at the reference's 1e-4 ||rhs|| on the same operator.
+            if world == 1 and args.tuned and args.sm_rel is None and args.mp_rel is None and not solver.opts.outer_matrix_free:
+                keep = (solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free)
+                solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free = 1e-2, 1e-1, 1
+                step()
+                fence()
+                t0 = time.time()
+                for _ in range(args.steps):
+                    st = step()
+                solver.synchronize()
+                dt_t = (time.time() - t0) / args.steps
+                out["tuned_preconditioner"] = {"ms_per_step": dt_t * 1e3, "value": n_dofs_global / dt_t, "unit": "DoF/s",
+                                               "fgmres_iters": st.fgmres_iters, "cg_mp_rel": 1e-2, "cg_sm_rel": 1e-1, "outer_matrix_free": 1,
+                                               "note": "side measurement; `value` above uses the reference's tolerances"}
+                solver.opts.mp_rel, solver.opts.sm_rel, solver.opts.outer_matrix_free = keep  # the legs below use the reference's again
+            if world == 1 and args.extras:
+                out.update(extras(solver, capi, n_dofs_global, ms_per_step))
+                # the three figures side by side: `value` keeps B, B^T, M_p, diag(M_u), S_m of the previous iteration
+                # (same constrained-dof set) and is the FIRST Newton iteration of a step; value_cold re-integrates / re-forms them
+                # inside the step as the reference does in every iteration; value_sustained = DoF x Newton iterations / time of a
+                # whole run_one_step loop from the same state (later iterations need more FGMRES iterations)
+                if "cold_step" in out:
+                    out["value_cold"] = out["cold_step"]["value"]
+                if "dofs_per_s_per_iteration" in out.get("time_step", {}):
+                    out["value_sustained"] = out["time_step"]["dofs_per_s_per_iteration"]
+                if "value" in out.get("matrix_free_step", {}):
+                    out["value_matrix_free"] = out["matrix_free_step"]["value"]
+            if world == 1 and args.fsi:
+                # side measurement, last device leg: its Dirichlet-mode call edits the constraint sets of the context
                 try:
-                    with open(path) as f:
+                    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+                    import fsibench
+                    solid = fsibench.make_solid3d()
+                    leg = fsibench.device_leg(solver.L, solver.ctx, capi, n_cells, solid)
+                    leg["cpu_baseline"] = fsibench.cpu_leg(args.fsi, solid)
+                    out["fsi_inputs"] = leg
+                except Exception as e:  # a side leg must not take the headline line with it
+                    out["fsi_inputs"] = {"error": repr(e)}
+            if world == 1 and args.cylinder_legs:
+                # side measurements (configs 2 and 4 report DoF/s too; VERDICT r4 item 5: the cell kernel on an unstructured 3D
+                # mesh of scale).  The channel's contexts are released first: the 3D cylinder needs ~40 GB of its own.
+                try:
+                    solver.close()
+                    sys.path.insert(0, os.path.join(ROOT, "tools"))
+                    import cylbench
+                    legs = {}
+                    for w, r in (("cylinder2d", 3), ("cylinder2d_scnsim", 3), ("cylinder3d", 3)):
+                        o = cylbench.run(w, r, steps=2, device=local_rank)
+                        legs[w] = {"value": o["value"], "unit": o["unit"], "ms_per_step": o["ms_per_step"], "config": o["config"]}
+                        if "roofline" in o and "assemble3_unstructured" in o["roofline"]:
+                            legs[w]["assemble3_unstructured"] = o["roofline"]["assemble3_unstructured"]
+                            legs[w]["kernel_ms_per_step"] = {k["family"]: k["ms_per_step"] for k in o["roofline"]["kernels"]}
+                    out["cylinder_workloads"] = legs
+                except Exception as e:  # a side leg must not take the headline line with it
+                    out["cylinder_workloads"] = {"error": repr(e)}
+            cpu_sizes = [int(v) for v in str(args.cpu_n).split(",") if int(v) > 0]
+            if cpu_sizes and world == 1:  # the CPU baseline is a rank-0, N = 1 measurement
+                out["cpu_baseline"] = cpu_baseline(cpu_sizes)
+            elif world > 1:
+                # measured on rank 0 at N = 1 only: an N > 1 line quotes the committed sample of the single-GPU run (no run reads
+                # what an earlier run left behind)
+                try:
+                    with open(os.path.join(ROOT, "profiles", "cpu_baseline_n1.json")) as f:
                         cb = json.load(f)
-                    cb["reused_from"] = f"N = 1 sample, not re-measured at N = {world}: {origin}"
+                    cb["reused_from"] = (f"N = 1 sample, not re-measured at N = {world}: committed sample of the round's 1-GPU run "
+                                         "(profiles/cpu_baseline_n1.json)")
                     out["cpu_baseline"] = cb
-                    break
                 except (OSError, ValueError):
-                    continue
-        emit(out)
+                    pass
+        report(out, args.full)
     if dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -48,7 +48,7 @@ def test_two_process_rccl_bench_run(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     dump = str(tmp_path / "upd")
     common = ["--cells", "16", "--steps", "1", "--warmup", "1", "--cpu-cells", "0", "--fgmres-rel", "1e-9", "--inner-rel", "1e-4",
-              "--inner-rel-first", "0", "--extras", "0", "--tuned", "0", "--fsi", "0"]
+              "--inner-rel-first", "0", "--extras", "0", "--tuned", "0", "--fsi", "0", "--full"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-update", dump] + common
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)

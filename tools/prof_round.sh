@@ -15,7 +15,7 @@ fi
 cd $R
 for d in kt fetch write; do db=$(find $O/$d -name "*.db" 2>/dev/null | head -1); [ -n "$db" ] && python tools/rocpd_summary.py $db $O/$d; done
 if [ "$2" != "quick" ]; then
-python bench.py > $O/bench_default.jsonl 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.jsonl 2> $O/bench_default.err
 tail -1 $O/bench_default.jsonl | cut -c1-600
 fi
 find $O -name "*.db" -delete
