@@ -212,10 +212,10 @@ typedef struct {
                             (mpi_insim.cpp:343-361).  0: A_uu is never stored: the assembly integrates the right-hand side (B, B^T, M_p, diag(M_u)
                             through the cached geometry path), the outer operator applies A_uu matrix-free in fp64 (equal to the stored block to
                             1e-13) and the smoothers take their node blocks from the cell integrals.  Needs the matrix-free inner solvers
-                            (IFEM_AINV_MG / _BJACOBI_MF), geo_cache >= 1 and no hanging nodes.  An assembly whose constraint set carries
-                            non-zero values (the first Newton iteration of a step with inhomogeneous boundary values: distribute_local_to_global
-                            needs the element matrix columns) takes the stored path by itself -- and allocates the values then.  Without such
-                            assemblies 78 GB less memory at 128^3; ~2 x the step rate.  The block CSR stays the default (north star). */
+                            (IFEM_AINV_MG / _BJACOBI_MF) and geo_cache >= 1.  Non-zero constraint values (either set) are moved into the
+                            right-hand side by a matrix-free lift, hanging-node lines are condensed around the operator as with the block CSR:
+                            no assembly of this mode allocates A_uu values (ifem_uu_stored_bytes stays 0).  78 GB less memory at 128^3; ~2 x
+                            the step rate.  The block CSR stays the default (north star). */
 } ifem_tuning;
 /* Initialise an ifem_tuning with ifem_default_tuning before changing fields: a zero-initialised struct gets the documented defaults
  * only for the fields where 0 is not a meaningful value (asm3_cpb, scns_pc, pvv_sweeps, b2pp_sweeps). */
@@ -283,6 +283,9 @@ int ifem_ctx_create(const ifem_mesh_desc *mesh, const ifem_partition *part, int 
 void ifem_ctx_destroy(ifem_ctx *ctx);
 int64_t ifem_n_local_dofs(const ifem_ctx *ctx);
 int64_t ifem_nnz(const ifem_ctx *ctx, int block); /* 0: A_uu blocks, 1: B blocks, 2: M_p, 3: S_m */
+/* bytes of device memory currently allocated for the VALUES of A_uu (the block CSR of ifem_tuning::stored_uu = 1); 0 when there are none: a context
+ * that has only ever assembled with stored_uu = 0 reports 0, whatever its constraint values and with or without hanging nodes */
+int64_t ifem_uu_stored_bytes(const ifem_ctx *ctx);
 
 /* FluidSolver::make_constraints result (mpi_fluid_solver.cpp:165-280): which = 0 zero_constraints,
  * 1 nonzero_constraints; Dirichlet lines (local dof, inhomogeneity; inhom == NULL: all zero).  A dof listed twice keeps

@@ -138,7 +138,8 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_mass_vmult", "ifem_mg_attach", "ifem_mg_depth", "ifem_uu_block_diag",
            "ifem_fsi_set_solid", "ifem_fsi_update_indicator", "ifem_fsi_find_fluid_bc", "ifem_fsi_get_stress",
            "ifem_get_constraints", "ifem_fsi_fluid_at_points", "ifem_comm_stats_get", "ifem_comm_stats_level", "ifem_true_residual", "ifem_tpp_ilu_probe", "ifem_tpp_override", "ifem_scns_pc_probe", "ifem_test_restart_fits",
-           "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length"]
+           "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
+           "ifem_uu_stored_bytes"]
 
 # ifem_abi_sizeof(which): the ctypes mirror of every struct of the header
 ABI_STRUCTS = None  # filled below (needs every class defined)
@@ -165,6 +166,8 @@ def load():
     L.ifem_n_local_dofs.argtypes = [C.c_void_p]
     L.ifem_nnz.restype = C.c_int64
     L.ifem_nnz.argtypes = [C.c_void_p, C.c_int]
+    L.ifem_uu_stored_bytes.restype = C.c_int64
+    L.ifem_uu_stored_bytes.argtypes = [C.c_void_p]
     L.ifem_default_solver_opts.argtypes = [C.POINTER(SolverOpts)]
     L.ifem_ctx_create.argtypes = [C.POINTER(MeshDesc), C.POINTER(Partition), C.c_int, C.POINTER(C.c_void_p)]
     L.ifem_ctx_destroy.argtypes = [C.c_void_p]
@@ -522,6 +525,10 @@ class Context:
             setattr(t, k, v)
         self._chk(self.L.ifem_set_tuning(self.h, C.byref(t)))
         self._tuning = t
+
+    def uu_stored_bytes(self):
+        """device bytes currently allocated for A_uu values (0: ifem_tuning::stored_uu = 0 has kept no block CSR)"""
+        return int(self.L.ifem_uu_stored_bytes(self.h))
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

@@ -238,6 +238,7 @@ void ifem_ctx_destroy(ifem_ctx *ctx) {
 }
 
 int64_t ifem_n_local_dofs(const ifem_ctx *ctx) { return ctx->n_local; }
+int64_t ifem_uu_stored_bytes(const ifem_ctx *ctx) { return ctx ? int64_t(ctx->Auu.val.n * sizeof(double)) : 0; }
 int64_t ifem_nnz(const ifem_ctx *ctx, int block) {
   switch (block) {
   case 0: return ctx->Auu.nnzb;

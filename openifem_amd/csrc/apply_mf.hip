@@ -103,7 +103,10 @@ struct alignas(16) MfCell { // per-cell LDS scratch
 
 // CONV = false: the evaluation point is zero (InsIMEX matrix: no convective / Newton terms) -- the second field is neither gathered
 // nor interpolated
-template <int DIM, int KV, int WPB, bool CONV, typename R, typename XT>
+// LIFT = true (uu_lift_mf): the input mask is inverted -- A.x holds the constraint values and enters ONLY where A.is_c is set, so the
+// cell results are the columns of the constrained dofs times their values (the K g that distribute_local_to_global moves into the
+// right-hand side).  A wave whose two cells touch no constrained dof with a non-zero value stores zeros and moves on (wave-uniform).
+template <int DIM, int KV, int WPB, bool CONV, typename R, typename XT, bool LIFT = false>
 __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
   constexpr int N1 = KV + 1, NN = MfGeo<DIM, N1>::NN, NV = 1 << DIM, NF = CONV ? 2 : 1;
   constexpr int NP = NN / N1;        // pencils per field and direction
@@ -180,11 +183,27 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
     const Pre cur = pre;
     const int32_t nd_next = nd_ahead;
     nd_ahead = load_id(pair + 2 * WPB);
+    if constexpr (LIFT) {
+      bool touched = false;
+      if (q_lane) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) touched = touched || (cur.f[c] != 0 && cur.x[c] != XT(0));
+      }
+      if (!__any(touched)) { // no LDS traffic on this path: nothing to order
+        load_vals(pair + WPB, nd_next, pre);
+        if (active && q_lane) {
+#pragma unroll
+          for (int c = 0; c < DIM; ++c) A.ycell[cell * (DIM * NN) + hl * DIM + c] = R(0);
+        }
+        continue;
+      }
+    }
     if (q_lane) {
 #pragma unroll
       for (int c = 0; c < DIM; ++c) {
         Val v;
-        v.f[0] = cur.f[c] != 0 ? R(0) : R(cur.x[c]);
+        if constexpr (LIFT) v.f[0] = cur.f[c] != 0 ? R(cur.x[c]) : R(0);
+        else v.f[0] = cur.f[c] != 0 ? R(0) : R(cur.x[c]);
         if constexpr (CONV) v.f[1] = R(cur.u[c]);
         S.V[qoff[c]] = v;
       }
@@ -397,7 +416,9 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
 // spot -- fuse.mode 1: xs += x, r -= t (residual update after the coarse correction); mode 2: the Chebyshev step
 // xs += x, r -= t, x <- a x + b B r with the inverse node block B (x is the smoother's direction vector and is updated in
 // place: the cell kernel that read it has completed, and a thread only touches the entries of its own node).
-template <int DIM, typename R, bool FUSE, typename V>
+// LIFT (uu_lift_mf; x = the constraint values, y = the right-hand side): free rows y_i -= sum, constrained rows y_r = d_r x_r with
+// the same d_r as above.
+template <int DIM, typename R, bool FUSE, typename V, bool LIFT = false>
 __global__ void k_mf_gather(int64_t n, int nn, const int64_t *__restrict__ inc_ptr, const int32_t *__restrict__ inc,
                             const R *__restrict__ ycell, const uint8_t *__restrict__ is_c,
                             const double *__restrict__ bjac, const float *__restrict__ bjf, const V *x, double *y, MfFuseT<V> fuse) {
@@ -435,7 +456,8 @@ __global__ void k_mf_gather(int64_t n, int nn, const int64_t *__restrict__ inc_p
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int64_t i = nd * DIM + c;
-      y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : s[c];
+      if constexpr (LIFT) y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : y[i] - s[c];
+      else y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : s[c];
     }
   } else {
     double xv[DIM], rv[DIM], bj[DIM * DIM];
@@ -498,7 +520,7 @@ static void mf_tables(MfTables &t, int kv) {
     }
 }
 
-template <typename R, typename XT>
+template <typename R, typename XT, bool LIFT = false>
 static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT<XT> *fuse, int part) {
   if (!ctx->mf_valid) throw Error(IFEM_E_BADPARAM, "matrix-free A_uu: no assembled state (call ifem_ins_assemble first)");
   const int64_t n = int64_t(ctx->dim) * ctx->nUo;
@@ -517,7 +539,7 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   a.inv_dt = R(1.0 / ctx->mf_params.dt);
   { MfTables t; mf_tables(t, ctx->kv); mf_tables_to(a.t, t); }
   a.xcd = ctx->tune.xcd_swizzle;
-  const bool time_it = ctx->profile;
+  const bool time_it = ctx->profile && !LIFT; // (the lift runs inside an assembly, whose own timing owns the two events)
   if (ctx->n_cells >= (int64_t(1) << 26) || ctx->nu > 32) throw Error(IFEM_E_BADPARAM, "matrix-free A_uu: incidence entries hold 26 cell bits and 5 node bits");
   if (ctx->uinc.n_rows == 0 && ctx->nUo) build_incidence(ctx);
   const size_t need = size_t(ctx->n_cells) * ctx->dim * ctx->nu; // in doubles: the float variant uses half of it
@@ -538,10 +560,10 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   };
   const unsigned g_all = unsigned(std::min<int64_t>((n_pairs + WPB - 1) / WPB, int64_t(1) << 30));
 #define IFEM_MF2(D, K)                                                                                                 \
-  { if (conv) { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, true, R, XT>));  \
-                hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, true, R, XT>), dim3(std::min(cap, g_all)), block, 0, s, a); }       \
-    else { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, false, R, XT>));     \
-           hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, false, R, XT>), dim3(std::min(cap, g_all)), block, 0, s, a); } }
+  { if (conv) { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, true, R, XT, LIFT>));  \
+                hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, true, R, XT, LIFT>), dim3(std::min(cap, g_all)), block, 0, s, a); }       \
+    else { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, false, R, XT, LIFT>));     \
+           hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, false, R, XT, LIFT>), dim3(std::min(cap, g_all)), block, 0, s, a); } }
   if (n_pairs > 0) {
     // algorithmic traffic of the cell kernel: x, evaluation point (fp64 in HBM), constraint flags once per entry,
     // the per-cell results once, vertex coordinates and node ids per cell; flops of the sum-factorised passes + the point stage
@@ -565,7 +587,7 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   const double per_node = ctx->dim * double(sizeof(XT)) * (fuse ? (fuse->mode >= 2 ? 6.0 : 5.0) : 2.0) + (fuse ? 4.0 * ctx->dim * ctx->dim : 0.0) + 8.0 + ctx->dim;
   KScope ksg(ctx, IFEM_KC_MF_GATHER, double(ctx->n_cells) * ctx->nu * (ctx->dim * sizeof(R) + 4.0) + double(ctx->nUo) * per_node);
 #define IFEM_MFG(D, F)                                                                                                 \
-  hipLaunchKernelGGL((k_mf_gather<D, R, F, XT>), dim3(unsigned((n / D + 255) / 256)), dim3(256), 0, s, n, ctx->nu, ctx->uinc.rowptr.p, \
+  hipLaunchKernelGGL((k_mf_gather<D, R, F, XT, LIFT>), dim3(unsigned((n / D + 255) / 256)), dim3(256), 0, s, n, ctx->nu, ctx->uinc.rowptr.p, \
                      ctx->uinc.col.p, a.ycell, a.is_c, ctx->bjac.p, fuse ? bjac_f32_ptr(ctx) : nullptr, xu, yu, f0)
   if (ctx->dim == 3) { if (fuse) IFEM_MFG(3, true); else IFEM_MFG(3, false); }
   else { if (fuse) IFEM_MFG(2, true); else IFEM_MFG(2, false); }
@@ -584,6 +606,34 @@ void apply_uu_mf(ifem_ctx *ctx, const double *xu, double *yu, bool single, const
   if (single && ctx->tune.mf_f32) apply_uu_mf_t<float, double>(ctx, xu, yu, fuse, part);
   else apply_uu_mf_t<double, double>(ctx, xu, yu, fuse, part);
 }
+
+// the lift vector g (ghost-extended): the constraint values on the constrained dofs of the set, zero elsewhere
+__global__ void k_lift_vector(int64_t n, const uint8_t *__restrict__ is_c, const double *__restrict__ cval, double *__restrict__ g) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) g[i] = is_c[i] ? cval[i] : 0.0;
+}
+
+// Inhomogeneity lift of a stored_uu = 0 assembly (assemble.hip), on the state that assembly just recorded (mf_eval, mf_params,
+// mf_noconv, asm_constraint_set) and after its uu_block_diag_mf: with g = the values of the active constraint set on its dofs,
+//   velocity rows:  b_free -= (A_uu[free, constrained] g),   b_r = d_r g_r   (cell kernel + node gather with the mask inverted)
+//   pressure rows:  b_p   -= B0[:, constrained u] g           (the unconstrained B of the geometry cache on the masked vector)
+// which is what distribute_local_to_global leaves in the right-hand side of the stored assembly.  Pressure dofs cannot be
+// constrained (ifem_set_constraints refuses them), so there is no B^T half.  The constraint arrays cover the local dofs, ghosts
+// included: the lift vector needs no exchange.
+void uu_lift_mf(ifem_ctx *ctx) {
+  const int w = ctx->asm_constraint_set;
+  if (!ctx->has_c[w]) return;
+  if (!ctx->geo.b0_valid || ctx->geo.B0.n != ctx->B.val.n) throw Error(IFEM_E_BADPARAM, "inhomogeneity lift: the unconstrained B is not cached");
+  double *rhs = ctx->vec[IFEM_VEC_RHS].p;
+  apply_uu_mf_t<double, double, true>(ctx, ctx->cval[w].p, rhs, nullptr, 0);
+  const int64_t nul = int64_t(ctx->dim) * ctx->nUl, npo = ctx->nPo;
+  if (!npo) return;
+  if ((int64_t)ctx->mf_lift.n != nul + npo) ctx->mf_lift.alloc(size_t(nul + npo));
+  double *g = ctx->mf_lift.p, *bp = g + nul;
+  if (nul) hipLaunchKernelGGL(k_lift_vector, dim3(unsigned(std::min<int64_t>((nul + 255) / 256, 4096))), dim3(256), 0, ctx->stream, nul, ctx->is_c[w].p, ctx->cval[w].p, g);
+  spmv_b(ctx, g, bp, 0, ctx->geo.B0.p);
+  v_axpy(ctx, npo, -1.0, bp, rhs + int64_t(ctx->dim) * ctx->nUo);
+}
+
 void apply_uu_mf_f32v(ifem_ctx *ctx, const float *xu, const MfFuseT<float> *fuse, int part) {
   if (!fuse) throw Error(IFEM_E_BADPARAM, "apply_uu_mf_f32v: the fused form only");
   apply_uu_mf_t<float, float>(ctx, xu, nullptr, fuse, part);

@@ -98,11 +98,13 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   // ifem_tuning::stored_uu = 0: the velocity-velocity block is never stored.  The cell kernel integrates the right-hand side (and,
   // through the geometry path, B / B^T / M_p / diag(M_u)); A_uu is applied matrix-free in fp64 by the outer operator (the same
   // operator to 1e-13, test_matrix_free_uu_apply_equals_assembled_block) and its node-block diagonal comes from the cell integrals.
-  // An assembly with inhomogeneous constraint values needs the element matrix columns (distribute_local_to_global moves K g into the
-  // right-hand side): that one -- the first Newton iteration of a step with non-zero boundary values -- takes the stored path.
-  const bool mf_only = full && ctx->tune.stored_uu == 0 && !(use_nonzero && ctx->inhom_any[1]);
-  if (full && ctx->tune.stored_uu == 0 && ctx->hang.active)
-    throw Error(IFEM_E_BADPARAM, "stored_uu = 0 with hanging-node constraints is not supported");
+  // An assembly whose active constraint set carries non-zero values (the first Newton iteration of a step with inflow values, every
+  // FSI step) owes the right-hand side the K g that distribute_local_to_global moves there: K g is the operator applied to a vector
+  // that lives on the constrained dofs, so the matrix-free cell kernel computes it with its input mask inverted and the unconstrained
+  // B of the geometry cache supplies the pressure rows (apply_mf.hip::uu_lift_mf, after the epilogue below).  Hanging-node lines are
+  // condensed around the operator afterwards (hanging_condense_rhs), on the lifted right-hand side.
+  const bool mf_only = full && ctx->tune.stored_uu == 0;
+  const bool mf_lift = mf_only && ctx->has_c[use_nonzero ? 1 : 0] && ctx->inhom_any[use_nonzero ? 1 : 0];
   if (full && !mf_only) ensure_auu_values(ctx);
   if (full) ctx->uu_is_stored = !mf_only;
   if (mode == AsmMode::Rhs && !ctx->assembled) throw Error(IFEM_E_BADPARAM, "rhs-only assembly before any matrix assembly");
@@ -116,6 +118,8 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
     ctx->mf_noconv = imex != 0;
     ctx->asm_version++;
     skip_geo = ctx->geo.reuse(geo_key, ctx->tune.geo_cache == 1, true);
+    // the lift applies the unconstrained B: a cache that gave its copies back (GeoCache::kKeep) integrates them once more and keeps them
+    if (mf_lift && skip_geo && !ctx->geo.b0_valid) skip_geo = false;
   }
   bool mass = false; // M_p and diag(M_u) re-integrated by this assembly
   // A NEW constrained-dof set (every FSI step): the blocks are masked copies of the unconstrained ones, which are integrated
@@ -198,8 +202,10 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   if (unconstrained) return; // the caller copies the blocks away
   if (matrices) { ctx->geo.valid = true; ctx->geo.key = geo_key; }
   if (level) { level_geometry_epilogue(ctx, use_nonzero, mass); return; }
-  if (full) assemble_epilogue(ctx, use_nonzero, mass);
-  else {
+  if (full) {
+    assemble_epilogue(ctx, use_nonzero, mass);
+    if (mf_lift) uu_lift_mf(ctx);
+  } else {
     IFEM_HIP_CHECK(hipEventSynchronize(ctx->ev1));
     float ms = 0;
     IFEM_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

@@ -388,7 +388,7 @@ struct ifem_ctx {
   ifem::MgCsr mg_Pp, mg_Rp, mg_Pu, mg_Ru;
   ifem::DBuf<int32_t> mg_inj_u; // [nUo of the coarse level] coincident owned velocity node of this level
   ifem::DBuf<uint8_t> mg_Pu_mask, mg_Ru_mask; // per weight 8 bytes: {column | components dropped by the Dirichlet flags of the two levels << 29, weight as float} (mg.hip::mg_csr_mask)
-  bool uu_is_stored = true;                   // the last full assembly scattered A_uu (false: ifem_tuning::stored_uu = 0 took the matrix-free path)
+  bool uu_is_stored = true;                   // the last full assembly scattered A_uu (false: ifem_tuning::stored_uu = 0, the matrix-free path)
   bool inhom_any[2] = {false, false};         // constraint object `which` carries a non-zero inhomogeneity somewhere (any rank)
   uint64_t graph_epoch = 0;                   // bumped by ifem_set_tuning / ifem_set_profiling / ifem_mg_attach: solver.hip::graph_run adds it to every replay key
   int64_t mg_mask_key[2] = {-1, -1};          // constrained-dof sets (flag ids of this level and the coarser one) of the masks
@@ -415,6 +415,7 @@ struct ifem_ctx {
   // matrix-free A_uu (IFEM_AINV_GMRES_BJACOBI_MF): state of the last ifem_ins_assemble
   ifem::DBuf<double> mf_ycell; // per-cell results of the matrix-free apply [n_cells][nu][dim] (two-stage scatter)
   ifem::DBuf<double> mf_eval;  // velocity part of the evaluation point, ghost-extended
+  ifem::DBuf<double> mf_lift;  // inhomogeneity lift (apply_mf.hip::uu_lift_mf): lift vector [dim*nUl] and B0 times it [nPo]
   ifem_ins_params mf_params{};
   bool mf_valid = false;
   bool mf_noconv = false; // the assembled matrix has no convective terms (InsIMEX): the operator skips the second field group
@@ -508,7 +509,8 @@ inline KScope::~KScope() {
 
 namespace ifem {
 // The stored A_uu values, for every reader outside the assembly: refused when no assembly stored them or the last full assembly
-// took the matrix-free path (ifem_tuning::stored_uu = 0) -- the array then still holds an older matrix.
+// took the matrix-free path (ifem_tuning::stored_uu = 0) -- the array is then empty, or still holds the matrix of an assembly made
+// before the tuning changed.
 inline const DBuf<double> &stored_uu(const ifem_ctx *c) {
   if (c->Auu.val.n == 0 || !c->uu_is_stored)
     throw Error(IFEM_E_BADPARAM, "A_uu has no stored values (ifem_tuning::stored_uu = 0, or no assembly yet): this operation needs the block CSR");

@@ -71,6 +71,7 @@ void apply_uu_mf(ifem_ctx *ctx, const double *xu, double *yu, bool single = fals
 // the same on SINGLE-PRECISION vectors, fused form only (the level vectors of the A_uu V-cycle, solver.hip): single-precision
 // cell arithmetic, x and the vectors of `fuse` are float
 void apply_uu_mf_f32v(ifem_ctx *ctx, const float *xu, const MfFuseT<float> *fuse, int part = 0);
+void uu_lift_mf(ifem_ctx *ctx); // apply_mf.hip: inhomogeneity lift of the right-hand side after a stored_uu = 0 assembly
 // scalar velocity operator S^ (IFEM_AINV_SCALAR_GMRES): auxiliary data, SpMV on all components, Jacobi
 void shat_refresh(ifem_ctx *ctx, bool f32);
 void spmv_shat(ifem_ctx *ctx, const double *xu, double *yu, bool f32);
@@ -79,7 +80,7 @@ void shat_jacobi(ifem_ctx *ctx, const double *x, double *y);
 // `part` of the row-parallel products below: 0 all rows, 1 the rows that read owned columns only, 2 the others (several
 // ranks: 1 runs while the halo of x is in flight, 2 after halo_wait; see PlanarCsr::split_rows)
 void build_row_split(ifem_ctx *ctx, PlanarCsr &M, int64_t n_owned_cols, const PlanarCsr *M2 = nullptr, int64_t n_owned_cols2 = 0);
-void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part = 0);
+void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part = 0, const double *val = nullptr); // val: other values on the pattern of B (the unconstrained block)
 // y_u = B^T x_p
 void spmv_bt(ifem_ctx *ctx, const double *xp, double *yu);
 void spmv_b_f32(ifem_ctx *ctx, const double *xu, double *yp);  // same with single-precision copies of the values

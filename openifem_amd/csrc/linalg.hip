@@ -460,17 +460,18 @@ void shat_jacobi(ifem_ctx *ctx, const double *x, double *y) {
   else hipLaunchKernelGGL((k_node_scale<2>), dim3(vgrid(n * 2)), dim3(256), 0, ctx->stream, n, ctx->shat_dinv.p, x, y);
 }
 
-void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part) {
+void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part, const double *val) {
   const RowPart rp_ = row_part(ctx->B, part);
   const int64_t n = rp_.n;
   if (n == 0) return;
+  if (!val) val = ctx->B.val.p;
   KScope ks(ctx, IFEM_KC_SPMV_BBT, planar_bytes(ctx->B, n, 8, ctx->nUl, 8 * ctx->dim, 8));
   if (ctx->dim == 3)
     hipLaunchKernelGGL((k_spmv_planar<1, 3, 32>), dim3(blocks_for_rows(n, 32)), dim3(256), 0, ctx->stream, n,
-                       ctx->B.rowptr.p, ctx->B.col.p, ctx->B.val.p, xu, yp, rp_.rows);
+                       ctx->B.rowptr.p, ctx->B.col.p, val, xu, yp, rp_.rows);
   else
     hipLaunchKernelGGL((k_spmv_planar<1, 2, 16>), dim3(blocks_for_rows(n, 16)), dim3(256), 0, ctx->stream, n,
-                       ctx->B.rowptr.p, ctx->B.col.p, ctx->B.val.p, xu, yp, rp_.rows);
+                       ctx->B.rowptr.p, ctx->B.col.p, val, xu, yp, rp_.rows);
 }
 
 void spmv_bt(ifem_ctx *ctx, const double *xp, double *yu) {
