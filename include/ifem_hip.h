@@ -216,6 +216,10 @@ typedef struct {
                             right-hand side by a matrix-free lift, hanging-node lines are condensed around the operator as with the block CSR:
                             no assembly of this mode allocates A_uu values (ifem_uu_stored_bytes stays 0).  78 GB less memory at 128^3; ~2 x
                             the step rate.  The block CSR stays the default (north star). */
+  int32_t mf_uniform;    /* 1 (default): a context whose local cells are all the same axis-aligned box (decided once, at ifem_ctx_create,
+                            from the vertex coordinates: every subdivided_hyper_rectangle level) runs the constant-geometry variants of the
+                            matrix-free A_uu kernels (cell kernel and coarse-level node blocks): J^-1 = diag(1 / h), JxW = prod(h) w_q, no
+                            vertex coordinates are read.  Other meshes are unaffected.  0: the general kernels everywhere */
 } ifem_tuning;
 /* Initialise an ifem_tuning with ifem_default_tuning before changing fields: a zero-initialised struct gets the documented defaults
  * only for the fields where 0 is not a meaningful value (asm3_cpb, scns_pc, pvv_sweeps, b2pp_sweeps). */

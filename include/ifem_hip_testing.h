@@ -34,6 +34,11 @@ int ifem_scns_pc_probe(ifem_ctx *ctx, int which, const double *x, double *y);
  * collective (the smallest wish of all ranks wins): a test gives the ranks different bounds and checks that they agree. */
 int ifem_test_restart_fits(ifem_ctx *ctx, int columns);
 
+/* Which matrix-free A_uu kernels this context launches: returns 1 for the constant-geometry variants (every local cell is the same
+ * axis-aligned box and ifem_tuning::mf_uniform is on), 0 for the general ones, < 0 on error.  h (may be NULL) receives the three edge
+ * lengths the context detected (zeros: not a uniform box level; entries past dim are zero), whatever the tuning says. */
+int ifem_test_mf_uniform(ifem_ctx *ctx, double *h);
+
 #ifdef __cplusplus
 }
 #endif

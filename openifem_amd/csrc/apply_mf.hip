@@ -43,6 +43,7 @@ struct MfArgsT {
   int xcd;
   R *ycell; // per-cell results of the two-stage scatter
   MfTablesT<R> t;
+  R ih[3], vol; // UNI kernels only: 1 / h_d and prod h_d of the level's one axis-aligned box cell (ifem_ctx::mf_h)
 };
 
 template <int DIM, int N1>
@@ -92,7 +93,7 @@ struct MfLay {
 template <typename R, int NF>
 struct alignas(sizeof(R) * NF) MfVal { R f[NF]; };
 
-template <int DIM, int N1, typename R, int NF>
+template <int DIM, int N1, typename R, int NF, bool UNI = false>
 struct alignas(16) MfCell { // per-cell LDS scratch
   static constexpr int SZ = MfLay<DIM, N1>::SZ;
   MfVal<R, NF> V[SZ]; // nodal values -> values at the Gauss points; then, as R[SZ] over its head, integrand -> nodal result
@@ -100,22 +101,36 @@ struct alignas(16) MfCell { // per-cell LDS scratch
   R C[8 * DIM];       // [e][k]: monomial coefficients of the d-linear map
   R X[(1 << DIM) * DIM];
 };
+// UNI: the geometry is three constants of the launch, nothing of it passes through LDS
+template <int DIM, int N1, typename R, int NF>
+struct alignas(16) MfCell<DIM, N1, R, NF, true> {
+  static constexpr int SZ = MfLay<DIM, N1>::SZ;
+  MfVal<R, NF> V[SZ];
+  MfVal<R, NF> G[SZ];
+};
+// what the prefetch carries of the cell's geometry: one vertex coordinate per lane, or nothing
+template <bool UNI> struct MfPreGeo { double vc; };
+template <> struct MfPreGeo<true> {};
 
 // CONV = false: the evaluation point is zero (InsIMEX matrix: no convective / Newton terms) -- the second field is neither gathered
 // nor interpolated
 // LIFT = true (uu_lift_mf): the input mask is inverted -- A.x holds the constraint values and enters ONLY where A.is_c is set, so the
 // cell results are the columns of the constrained dofs times their values (the K g that distribute_local_to_global moves into the
 // right-hand side).  A wave whose two cells touch no constrained dof with a non-zero value stores zeros and moves on (wave-uniform).
-template <int DIM, int KV, int WPB, bool CONV, typename R, typename XT, bool LIFT = false>
+// UNI = true (ifem_ctx::mf_uniform: every cell of the context is the same axis-aligned box of edges h): J = diag(h), so J^-1 =
+// diag(A.ih) and JxW = A.vol wq are constants of the lane -- no vertex coordinates are loaded, the monomial coefficients, the
+// Jacobian, its cofactors and the reciprocal are gone, and the two contractions with J^-1 keep their diagonal term only.  Chosen at
+// launch for the whole grid.
+template <int DIM, int KV, int WPB, bool CONV, typename R, typename XT, bool LIFT = false, bool UNI = false>
 __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
   constexpr int N1 = KV + 1, NN = MfGeo<DIM, N1>::NN, NV = 1 << DIM, NF = CONV ? 2 : 1;
   constexpr int NP = NN / N1;        // pencils per field and direction
   constexpr int NPL = DIM * NP;      // pencil lanes (one per pencil and component)
   using Lay = MfLay<DIM, N1>;
   using Val = MfVal<R, NF>;
-  __shared__ MfCell<DIM, N1, R, NF> SS[2 * WPB];
+  __shared__ MfCell<DIM, N1, R, NF, UNI> SS[2 * WPB];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
-  MfCell<DIM, N1, R, NF> &S = SS[2 * wave + half];
+  MfCell<DIM, N1, R, NF, UNI> &S = SS[2 * wave + half];
   R *const Vs = reinterpret_cast<R *>(S.V), *const Gs = reinterpret_cast<R *>(S.G); // single-field views (transposed passes)
   // ---- per-lane roles (fixed for the life of the wave)
   const bool pen_lane = hl < NPL;
@@ -147,6 +162,7 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
     for (int k = 1; k < N1; ++k) { x_ = qi[d] == k ? A.t.xi[k] : x_; w_ = qi[d] == k ? A.t.w[k] : w_; }
     xi[d] = x_; wq *= w_;
   }
+  [[maybe_unused]] const R JxW_uni = A.vol * wq; // UNI: the same at this lane's point of every cell
 
   // every block owns one contiguous range of cell pairs (XCD-aware: neighbouring ranges run on the same XCD)
   const int64_t n_pairs = (A.n_cells - A.first_cell + 1) / 2;
@@ -160,7 +176,7 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
   const int64_t p_first = vb * per_block + wave;
   // 32-bit index arithmetic in the prefetch (cells * nodes-per-cell and dim * nodes are below 2^31 by the int32 node ids)
   auto cell_of = [&](int64_t pr) { const int64_t c = A.first_cell + 2 * pr + half; return (pr < p_end && c < A.n_cells) ? uint32_t(c) : 0u; };
-  struct Pre { XT x[DIM]; double u[DIM], vc; uint8_t f[DIM]; } pre;
+  struct Pre { XT x[DIM]; double u[DIM]; MfPreGeo<UNI> g; uint8_t f[DIM]; } pre;
   auto load_id = [&](int64_t pr) -> int32_t { return q_lane ? A.cell_unodes[cell_of(pr) * uint32_t(NN) + uint32_t(hl)] : 0; };
   auto load_vals = [&](int64_t pr, int32_t nd, Pre &o) {
     if (q_lane) {
@@ -172,7 +188,7 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
         o.f[c] = A.is_c ? A.is_c[dof] : uint8_t(0); // one byte per dof: stays in L2
       }
     }
-    if (hl < NV * DIM) o.vc = A.vcoords[int64_t(cell_of(pr)) * (NV * DIM) + hl];
+    if constexpr (!UNI) { if (hl < NV * DIM) o.g.vc = A.vcoords[int64_t(cell_of(pr)) * (NV * DIM) + hl]; }
   };
   int32_t nd_ahead = load_id(p_first + WPB);
   load_vals(p_first, load_id(p_first), pre);
@@ -208,10 +224,10 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
         S.V[qoff[c]] = v;
       }
     }
-    if (hl < NV * DIM) S.X[hl] = R(cur.vc);
+    if constexpr (!UNI) { if (hl < NV * DIM) S.X[hl] = R(cur.g.vc); }
     wsync();
     // monomial coefficients of x(xi) = sum_k C_k prod_{d in k} xi_d:  C_k = sum_{v subset of k} (-1)^{|k|-|v|} X_v
-    if (hl < NV * DIM) {
+    if constexpr (!UNI) if (hl < NV * DIM) {
       const int k = hl / DIM, e = hl % DIM;
       R acc = 0;
 #pragma unroll
@@ -249,8 +265,10 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
       for (int d = 0; d < DIM; ++d) wsync();
     }
     // ---- geometry at the quadrature point
-    R Ji[DIM * DIM], JxW = 0;
-    {
+    [[maybe_unused]] R Ji[DIM * DIM];
+    R JxW = 0;
+    if constexpr (UNI) JxW = JxW_uni;
+    else {
       R J[DIM * DIM];
       if constexpr (DIM == 3) {
         const R e_ = xi[1], z_ = xi[2], x_ = xi[0];
@@ -315,11 +333,16 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
 #pragma unroll
         for (int c = 0; c < DIM; ++c) {
           const Val g = S.G[qoff[c]];
+          if constexpr (UNI) { // d/dx_d = (1 / h_d) d/dxi_d
+            gx[c][d] = A.ih[d] * g.f[0];
+            if constexpr (CONV) gu[c][d] = A.ih[d] * g.f[1];
+          } else {
 #pragma unroll
-          for (int e = 0; e < DIM; ++e) gx[c][e] += Ji[d * DIM + e] * g.f[0];
-          if constexpr (CONV) {
+            for (int e = 0; e < DIM; ++e) gx[c][e] += Ji[d * DIM + e] * g.f[0];
+            if constexpr (CONV) {
 #pragma unroll
-            for (int e = 0; e < DIM; ++e) gu[c][e] += Ji[d * DIM + e] * g.f[1];
+              for (int e = 0; e < DIM; ++e) gu[c][e] += Ji[d * DIM + e] * g.f[1];
+            }
           }
         }
       }
@@ -346,10 +369,13 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
         for (int e = 0; e < DIM; ++e) tp[e] = JxW * (A.mu * gx[c][e] + (e == c ? A.gamma * A.rho * divx : R(0)));
 #pragma unroll
         for (int d = 0; d < DIM; ++d) {
-          R t = 0;
+          if constexpr (UNI) That[c][d] = A.ih[d] * tp[d];
+          else {
+            R t = 0;
 #pragma unroll
-          for (int e = 0; e < DIM; ++e) t += Ji[d * DIM + e] * tp[e];
-          That[c][d] = t;
+            for (int e = 0; e < DIM; ++e) t += Ji[d * DIM + e] * tp[e];
+            That[c][d] = t;
+          }
         }
       }
       // the integrand goes to the single-field view over the head of V: every paired value of the wave has been read above
@@ -550,6 +576,13 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   const dim3 block(64 * WPB);
   const int64_t n_pairs = (a.n_cells - a.first_cell + 1) / 2;
   const bool conv = !ctx->mf_noconv;
+  // one axis-aligned box cell on the whole context (setup.hip::detect_uniform_cells): the constant-geometry kernels
+  const bool uni = mf_takes_uniform(ctx);
+  if (uni) {
+    double vol = 1;
+    for (int d = 0; d < ctx->dim; ++d) { a.ih[d] = R(1.0 / ctx->mf_h[d]); vol *= ctx->mf_h[d]; }
+    a.vol = R(vol);
+  }
   // every block walks one contiguous range of cell pairs: the grid is a whole number of resident rounds (4 per CU slot)
   // so that no round runs partly empty
   auto grid_for_kernel = [&](const void *fn) {
@@ -559,19 +592,20 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
     return unsigned(cus) * unsigned(per_cu) * 4u;
   };
   const unsigned g_all = unsigned(std::min<int64_t>((n_pairs + WPB - 1) / WPB, int64_t(1) << 30));
+#define IFEM_MF2_(D, K, C, U)                                                                                          \
+  { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, C, R, XT, LIFT, U>)); \
+    hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, C, R, XT, LIFT, U>), dim3(std::min(cap, g_all)), block, 0, s, a); }
 #define IFEM_MF2(D, K)                                                                                                 \
-  { if (conv) { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, true, R, XT, LIFT>));  \
-                hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, true, R, XT, LIFT>), dim3(std::min(cap, g_all)), block, 0, s, a); }       \
-    else { static const unsigned cap = grid_for_kernel(reinterpret_cast<const void *>(&k_apply_uu_mf2<D, K, WPB, false, R, XT, LIFT>));     \
-           hipLaunchKernelGGL((k_apply_uu_mf2<D, K, WPB, false, R, XT, LIFT>), dim3(std::min(cap, g_all)), block, 0, s, a); } }
+  { if (conv) { if (uni) IFEM_MF2_(D, K, true, true) else IFEM_MF2_(D, K, true, false) }                                \
+    else { if (uni) IFEM_MF2_(D, K, false, true) else IFEM_MF2_(D, K, false, false) } }
   if (n_pairs > 0) {
     // algorithmic traffic of the cell kernel: x, evaluation point (fp64 in HBM), constraint flags once per entry,
-    // the per-cell results once, vertex coordinates and node ids per cell; flops of the sum-factorised passes + the point stage
+    // the per-cell results once, vertex coordinates (general kernels only) and node ids per cell; flops of the sum-factorised passes + the point stage
     const int64_t nc = a.n_cells - a.first_cell;
     const int d = ctx->dim, n1 = ctx->kv + 1, npc = 1 << d;
     const double share = ctx->n_cells > 0 ? double(nc) / double(ctx->n_cells) : 0.0;
     const double passes = double((2 * d) * d * ctx->nu * n1 * 2 * 2 + d * d * ctx->nu * n1 * 2 * 2);
-    KScope ks(ctx, IFEM_KC_MF_CELL, share * double(n) * (sizeof(XT) + 8 + 1) + double(nc) * (npc * d * 8 + ctx->nu * 4 + ctx->nu * d * sizeof(R)),
+    KScope ks(ctx, IFEM_KC_MF_CELL, share * double(n) * (sizeof(XT) + 8 + 1) + double(nc) * ((uni ? 0 : npc * d * 8) + ctx->nu * 4 + ctx->nu * d * sizeof(R)),
               double(nc) * (passes + ctx->nu * 190.0));
     if (ctx->dim == 3 && ctx->kv == 2) IFEM_MF2(3, 2)
     else if (ctx->dim == 3) IFEM_MF2(3, 1)
@@ -579,6 +613,7 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
     else IFEM_MF2(2, 1)
   }
 #undef IFEM_MF2
+#undef IFEM_MF2_
   if (part == 1) return; // the node gather follows the boundary cells
   if (time_it) IFEM_HIP_CHECK(hipEventRecord(ctx->ev1, s));
   const MfFuseT<XT> f0 = fuse ? *fuse : MfFuseT<XT>{};

@@ -356,6 +356,11 @@ struct ifem_ctx {
   ifem::DBuf<int32_t> mf_cell_unodes;
   ifem::DBuf<double> mf_vcoords;
   int64_t mf_n_interior = -1;
+  // every local cell (ghost layer included) is the same axis-aligned box with edges mf_h: decided once at creation from vcoords
+  // (setup.hip::detect_uniform_cells), which never change afterwards.  The matrix-free A_uu kernels then run their constant-geometry
+  // variants (apply_mf.hip, mg.hip::k_uu_diag) unless ifem_tuning::mf_uniform = 0
+  bool mf_uniform = false;
+  double mf_h[3] = {0, 0, 0};
   ifem_tuning tune{};    // ifem_set_tuning
   ifem::PlanarCsr Sm;  // mass_schur(1,1) = B diag(M_u)^-1 B^T, explicit (single rank only; empty otherwise)
   bool sm_valid = false;
@@ -477,6 +482,11 @@ struct ifem_ctx {
   std::vector<hipEvent_t> pc_ev;
   size_t pc_used = 0;
 };
+
+namespace ifem {
+// the matrix-free A_uu kernels of this context take their constant-geometry variants
+inline bool mf_takes_uniform(const ifem_ctx *c) { return c->mf_uniform && c->tune.mf_uniform != 0; }
+} // namespace ifem
 
 namespace ifem {
 inline KProf &kprof_root(ifem_ctx *c) {

@@ -13,6 +13,7 @@ bool ensure_scat3(ifem_ctx *ctx, bool with_rows); // records of the 3D Q2/Q1 cel
 void build_schur_pattern(ifem_ctx *ctx);
 void build_schur_pattern_owned(ifem_ctx *ctx); // several ranks: owned x owned block, into ctx->TppPat
 void build_incidence(ifem_ctx *ctx);
+void detect_uniform_cells(ifem_ctx *ctx); // sets ifem_ctx::mf_uniform / mf_h from vcoords (once, at context creation)
 int64_t compact_flagged_rows(ifem_ctx *ctx, const int64_t *flag, int64_t n, DBuf<int32_t> &rows); // ascending list of the flagged rows
 void build_mf_cell_split(ifem_ctx *ctx); // several ranks: interior-first copy of the cell tables for the matrix-free apply
 

@@ -99,13 +99,16 @@ struct DiagArgs {
   double mu, rho, gamma, inv_dt;
   int conv;
   Tab1D t;
+  double ih[3], vol; // UNI kernels only: 1 / h_d and prod h_d of the level's one axis-aligned box cell (ifem_ctx::mf_h)
 };
 
 // Half a wavefront per cell (8 cells per block), 1D tables in LDS, every loop over nodes / points / components unrolled (the
 // node or point index of the inner loops is a compile-time constant, the lane's own index selects the LDS table row).
 // R: arithmetic type of the integrals (float on the levels of the V-cycle: the smoother applies the inverse blocks in single precision
 // anyway, and the kernel is bound by its ~65 kFLOP per cell); the per-node sums are accumulated in double
-template <int DIM, int KV, typename R>
+// UNI = true (ifem_ctx::mf_uniform): J^-1 = diag(A.ih) and JxW = A.vol wq on every cell, as in apply_mf.hip -- no vertex coordinates,
+// no per-point inverse Jacobians in LDS, diagonal contractions
+template <int DIM, int KV, typename R, bool UNI = false>
 __global__ __launch_bounds__(256) void k_uu_diag(DiagArgs A) {
   constexpr int N1 = KV + 1, NN = (DIM == 2) ? N1 * N1 : N1 * N1 * N1, NV = 1 << DIM, CPB = 8;
   __shared__ R sX[CPB][NV * DIM], sJi[CPB][NN * DIM * DIM], sW[CPB][NN], sU[CPB][NN * DIM], sGu[CPB][NN * DIM * DIM], sE[CPB][NN * DIM];
@@ -122,14 +125,15 @@ __global__ __launch_bounds__(256) void k_uu_diag(DiagArgs A) {
 #pragma unroll
     for (int c = 0; c < DIM; ++c) sE[slot][hl * DIM + c] = A.conv ? R(A.eval[int64_t(DIM) * nd + c]) : R(0);
   }
-  if (hl < NV * DIM) sX[slot][hl] = R(A.vcoords[cc * NV * DIM + hl]);
+  if constexpr (!UNI) { if (hl < NV * DIM) sX[slot][hl] = R(A.vcoords[cc * NV * DIM + hl]); }
   __syncthreads();
   const int li = hl < NN ? hl : 0; // my point (first stage) / my node (second stage)
   const int l0 = li % N1, l1 = (li / N1) % N1, l2 = DIM == 3 ? li / (N1 * N1) : 0;
   if (hl < NN) { // lane = quadrature point: Jacobian of the d-linear map, fields of the evaluation point
     const int q = hl;
     const int qi[3] = {l0, l1, l2};
-    R L[3][2], J[DIM * DIM], Ji[DIM * DIM], wq = 1;
+    [[maybe_unused]] R L[3][2], J[DIM * DIM], Ji[DIM * DIM];
+    R wq = 1;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
       R x_ = R(A.t.xi[0]), w_ = R(A.t.w[0]);
@@ -137,24 +141,27 @@ __global__ __launch_bounds__(256) void k_uu_diag(DiagArgs A) {
       for (int k = 1; k < N1; ++k) { x_ = qi[d] == k ? R(A.t.xi[k]) : x_; w_ = qi[d] == k ? R(A.t.w[k]) : w_; }
       L[d][1] = x_; L[d][0] = R(1) - x_; wq *= w_;
     }
+    if constexpr (UNI) sW[slot][q] = R(A.vol) * wq;
+    else {
 #pragma unroll
-    for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
+      for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int b[3] = {v & 1, (v >> 1) & 1, (v >> 2) & 1};
+      for (int v = 0; v < NV; ++v) {
+        const int b[3] = {v & 1, (v >> 1) & 1, (v >> 2) & 1};
 #pragma unroll
-      for (int d = 0; d < DIM; ++d) {
-        R g = b[d] ? R(1) : R(-1);
+        for (int d = 0; d < DIM; ++d) {
+          R g = b[d] ? R(1) : R(-1);
 #pragma unroll
-        for (int o = 0; o < DIM; ++o) if (o != d) g *= L[o][b[o]];
+          for (int o = 0; o < DIM; ++o) if (o != d) g *= L[o][b[o]];
 #pragma unroll
-        for (int e = 0; e < DIM; ++e) J[e * DIM + d] += sX[slot][v * DIM + e] * g;
+          for (int e = 0; e < DIM; ++e) J[e * DIM + d] += sX[slot][v * DIM + e] * g;
+        }
       }
-    }
-    const R det = inv_small<DIM, R>(J, Ji);
-    sW[slot][q] = R(fabs(det)) * wq;
+      const R det = inv_small<DIM, R>(J, Ji);
+      sW[slot][q] = R(fabs(det)) * wq;
 #pragma unroll
-    for (int i = 0; i < DIM * DIM; ++i) sJi[slot][q * DIM * DIM + i] = Ji[i];
+      for (int i = 0; i < DIM * DIM; ++i) sJi[slot][q * DIM * DIM + i] = Ji[i];
+    }
     R u[DIM], gr[DIM * DIM];
 #pragma unroll
     for (int c = 0; c < DIM; ++c) u[c] = 0;
@@ -187,8 +194,11 @@ __global__ __launch_bounds__(256) void k_uu_diag(DiagArgs A) {
 #pragma unroll
       for (int d = 0; d < DIM; ++d) { // physical gradient d_d u_c = sum_e (d^_e u_c) Ji[e][d]
         R t = 0;
+        if constexpr (UNI) t = gr[c * DIM + d] * R(A.ih[d]);
+        else {
 #pragma unroll
-        for (int e = 0; e < DIM; ++e) t += gr[c * DIM + e] * Ji[e * DIM + d];
+          for (int e = 0; e < DIM; ++e) t += gr[c * DIM + e] * Ji[e * DIM + d];
+        }
         sGu[slot][q * DIM * DIM + c * DIM + d] = t;
       }
     }
@@ -212,13 +222,18 @@ __global__ __launch_bounds__(256) void k_uu_diag(DiagArgs A) {
         const R N = n0v * n1v * n2v;
         const R dr[3] = {d0v * n1v * n2v, n0v * d1v * n2v, n0v * n1v * d2v};
         R ga[DIM];
-        const R *Ji = &sJi[slot][q * DIM * DIM];
+        if constexpr (UNI) {
 #pragma unroll
-        for (int d = 0; d < DIM; ++d) {
-          R t = 0;
+          for (int d = 0; d < DIM; ++d) ga[d] = dr[d] * R(A.ih[d]);
+        } else {
+          const R *Ji = &sJi[slot][q * DIM * DIM];
 #pragma unroll
-          for (int e = 0; e < DIM; ++e) t += dr[e] * Ji[e * DIM + d];
-          ga[d] = t;
+          for (int d = 0; d < DIM; ++d) {
+            R t = 0;
+#pragma unroll
+            for (int e = 0; e < DIM; ++e) t += dr[e] * Ji[e * DIM + d];
+            ga[d] = t;
+          }
         }
         const R w = sW[slot][q];
         R gg = 0, ug = 0;
@@ -290,18 +305,21 @@ void uu_block_diag_mf(ifem_ctx *ctx) {
   a.conv = ctx->mf_noconv ? 0 : 1;
   tab1d(a.t, ctx->kv);
   const dim3 grid(unsigned((ctx->n_cells + 7) / 8)), block(256); // 8 cells per block
-  // single-precision integrals where the blocks serve the single-precision V-cycle (ifem_tuning::mf_f32, the default)
-  if (ctx->tune.mf_f32) {
-    if (dim == 3 && ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<3, 2, float>), grid, block, 0, s, a);
-    else if (dim == 3) hipLaunchKernelGGL((k_uu_diag<3, 1, float>), grid, block, 0, s, a);
-    else if (ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<2, 2, float>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_uu_diag<2, 1, float>), grid, block, 0, s, a);
-  } else {
-    if (dim == 3 && ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<3, 2, double>), grid, block, 0, s, a);
-    else if (dim == 3) hipLaunchKernelGGL((k_uu_diag<3, 1, double>), grid, block, 0, s, a);
-    else if (ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<2, 2, double>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_uu_diag<2, 1, double>), grid, block, 0, s, a);
+  // one axis-aligned box cell on the whole context (setup.hip::detect_uniform_cells): the constant-geometry kernels
+  const bool uni = mf_takes_uniform(ctx);
+  if (uni) {
+    a.vol = 1;
+    for (int d = 0; d < dim; ++d) { a.ih[d] = 1.0 / ctx->mf_h[d]; a.vol *= ctx->mf_h[d]; }
   }
+#define IFEM_DIAG(R, U)                                                                                  \
+  { if (dim == 3 && ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<3, 2, R, U>), grid, block, 0, s, a);      \
+    else if (dim == 3) hipLaunchKernelGGL((k_uu_diag<3, 1, R, U>), grid, block, 0, s, a);                 \
+    else if (ctx->kv == 2) hipLaunchKernelGGL((k_uu_diag<2, 2, R, U>), grid, block, 0, s, a);             \
+    else hipLaunchKernelGGL((k_uu_diag<2, 1, R, U>), grid, block, 0, s, a); }
+  // single-precision integrals where the blocks serve the single-precision V-cycle (ifem_tuning::mf_f32, the default)
+  if (ctx->tune.mf_f32) { if (uni) IFEM_DIAG(float, true) else IFEM_DIAG(float, false) }
+  else { if (uni) IFEM_DIAG(double, true) else IFEM_DIAG(double, false) }
+#undef IFEM_DIAG
   if (dim == 3) hipLaunchKernelGGL((k_block_invert<3>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, ctx->bjac.p);
   else hipLaunchKernelGGL((k_block_invert<2>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, ctx->bjac.p);
   IFEM_HIP_CHECK(hipGetLastError());

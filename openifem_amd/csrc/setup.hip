@@ -461,6 +461,97 @@ void build_incidence(ifem_ctx *ctx) {
   one(ctx->uinc, ctx->nUo, ctx->nu, ctx->mf_n_interior >= 0 ? ctx->mf_cell_unodes.p : ctx->cell_unodes.p);
 }
 
+// ---- uniform box levels (ifem_ctx::mf_uniform): is every local cell the same axis-aligned box?
+// A cell qualifies when vertex v sits at X_0 + ((v & 1) h_0, ((v >> 1) & 1) h_1, ((v >> 2) & 1) h_2) with one h > 0 for the whole context.
+// h is the MEAN edge over the cells (not one cell's rounded difference): per direction the edges of a row telescope, so the mean is
+// the extent over the count up to the rounding of the sum.  Everything is reduced in a fixed order (fixed grid, tree sums): the same
+// mesh gives the same h, bit for bit, on every run.
+// Permitted deviation: a box mesh forms its coordinates as lo + i * step with step = (hi - lo) / n rounded, i.e. with three roundings
+// (step, product, sum), each at most u M with u = eps / 2 and M = max |coordinate|: 1.5 eps M per coordinate.  The test compares
+// x_v with x_0 + b h_mean: two coordinates (3 eps M), the mean of edges that are each off by at most 3 eps M (3 eps M), the rounding
+// of the comparison's own sum (0.5 eps M) -- 6.5 eps M, taken as 8 eps M.
+constexpr int kUniBlocks = 1024;
+__global__ __launch_bounds__(256) void k_uni_partial(int64_t n_cells, int dim, const double *__restrict__ vc, double *__restrict__ partial) {
+  __shared__ double sh[4][256];
+  const int nvd = (1 << dim) * dim;
+  double e[3] = {0, 0, 0}, m = 0;
+  for (int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x; c < n_cells; c += int64_t(gridDim.x) * 256) {
+    const double *x = vc + c * nvd;
+    for (int d = 0; d < dim; ++d) e[d] += x[(1 << d) * dim + d] - x[d];
+    for (int k = 0; k < nvd; ++k) m = fmax(m, fabs(x[k]));
+  }
+  for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] = e[d];
+  sh[3][threadIdx.x] = m;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) {
+      for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] += sh[d][threadIdx.x + w];
+      sh[3][threadIdx.x] = fmax(sh[3][threadIdx.x], sh[3][threadIdx.x + w]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) partial[blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
+}
+// out[0..2] = mean edge, out[3] = max |coordinate|, out[4] = 0 (k_uni_check raises it to 1 at the first cell that does not fit)
+__global__ __launch_bounds__(256) void k_uni_final(int n_blocks, int64_t n_cells, const double *__restrict__ partial, double *__restrict__ out) {
+  __shared__ double sh[4][256];
+  double e[3] = {0, 0, 0}, m = 0;
+  for (int b = threadIdx.x; b < n_blocks; b += 256) {
+    for (int d = 0; d < 3; ++d) e[d] += partial[b * 4 + d];
+    m = fmax(m, partial[b * 4 + 3]);
+  }
+  for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] = e[d];
+  sh[3][threadIdx.x] = m;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) {
+      for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] += sh[d][threadIdx.x + w];
+      sh[3][threadIdx.x] = fmax(sh[3][threadIdx.x], sh[3][threadIdx.x + w]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) out[threadIdx.x] = sh[threadIdx.x][0] / double(n_cells);
+  if (threadIdx.x == 3) out[3] = sh[3][0];
+  if (threadIdx.x == 4) out[4] = 0.0;
+}
+__global__ __launch_bounds__(256) void k_uni_check(int64_t n_cells, int dim, const double *__restrict__ vc, double *__restrict__ out) {
+  const int nv = 1 << dim;
+  const double tol = 8.0 * 2.220446049250313e-16 * out[3];
+  bool bad = false;
+  for (int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x; c < n_cells; c += int64_t(gridDim.x) * 256) {
+    const double *x = vc + c * nv * dim;
+    for (int v = 1; v < nv; ++v)
+      for (int d = 0; d < dim; ++d) {
+        const double want = x[d] + (((v >> d) & 1) ? out[d] : 0.0);
+        bad = bad || !(fabs(x[v * dim + d] - want) <= tol); // (a NaN coordinate does not fit either)
+      }
+  }
+  if (bad) out[4] = 1.0; // every writer stores the same value
+}
+void detect_uniform_cells(ifem_ctx *ctx) {
+  ctx->mf_uniform = false;
+  for (double &h : ctx->mf_h) h = 0;
+  const int64_t n = ctx->n_cells;
+  if (n == 0) return;
+  hipStream_t s = ctx->stream;
+  const int blocks = int(std::min<int64_t>((n + 255) / 256, kUniBlocks));
+  DBuf<double> partial, out;
+  partial.alloc(size_t(blocks) * 4); out.alloc(5);
+  hipLaunchKernelGGL(k_uni_partial, dim3(blocks), dim3(256), 0, s, n, ctx->dim, ctx->vcoords.p, partial.p);
+  hipLaunchKernelGGL(k_uni_final, dim3(1), dim3(256), 0, s, blocks, n, partial.p, out.p);
+  hipLaunchKernelGGL(k_uni_check, dim3(blocks), dim3(256), 0, s, n, ctx->dim, ctx->vcoords.p, out.p);
+  double h[5] = {0, 0, 0, 0, 1};
+  IFEM_HIP_CHECK(hipMemcpyAsync(h, out.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  IFEM_HIP_CHECK(hipStreamSynchronize(s)); // (`partial` and `out` leave scope)
+  IFEM_HIP_CHECK(hipGetLastError());
+  const double tol = 8.0 * 2.220446049250313e-16 * h[3];
+  bool ok = h[4] == 0.0;
+  for (int d = 0; d < ctx->dim; ++d) ok = ok && h[d] > tol; // h > 0, and an edge the tolerance cannot swallow
+  if (!ok) return;
+  ctx->mf_uniform = true;
+  for (int d = 0; d < ctx->dim; ++d) ctx->mf_h[d] = h[d];
+}
+
 // ---- cell tables of the matrix-free apply on several ranks: interior cells (all nodes owned) first, then the cells that
 // touch a ghost node; order kept inside both groups (the Morton locality survives)
 __global__ void k_cell_flag(int64_t n_cells, int nu, const int32_t *__restrict__ cell_unodes, int32_t n_owned, int64_t *__restrict__ flag) {

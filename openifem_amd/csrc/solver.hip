@@ -1101,6 +1101,7 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
         key.push_back(uint64_t(lc->nUo)); key.push_back(uint64_t(lc->n_cells)); key.push_back(uint64_t(lc->mf_noconv)); key.push_back(uint64_t(lc->tune.xcd_swizzle));
         // everything else the captured launches are made of: the epoch moves with ifem_set_tuning / ifem_set_profiling / ifem_mg_attach
         key.push_back(lc->graph_epoch); key.push_back(uint64_t(lc->tune.mf_f32));
+        key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) putd(hd); // which cell kernels, and their constants
         put(lc->bjac.p); put(lc->vcoords.p); put(lc->cell_unodes.p); put(lc->uinc.col.p);
         putd(lc->uu_lmax); putd(lc->mf_params.viscosity); putd(lc->mf_params.rho); putd(lc->mf_params.grad_div); putd(lc->mf_params.dt);
       }
