@@ -564,23 +564,24 @@ int ifem_halo_exchange(ifem_ctx *ctx, int vec) {
   IFEM_API_END
 }
 
-int ifem_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) {
-  IFEM_API_BEGIN
+// one assembly through the driver, waited for; timing.assemble_ms is its wall time
+static void timed_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode) {
   if (!p || p->dt <= 0) throw Error(IFEM_E_BADPARAM, "bad ifem_ins_params");
   auto t0 = std::chrono::steady_clock::now();
-  launch_ins_assemble(ctx, p, use_nonzero);
+  launch_ins_assemble_ex(ctx, p, use_nonzero, imex, mode);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->timing.assemble_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int ifem_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero) {
+  IFEM_API_BEGIN
+  timed_assemble(ctx, p, use_nonzero, 0, AsmMode::Full);
   IFEM_API_END
 }
 
 int ifem_imex_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int assemble_system) {
   IFEM_API_BEGIN
-  if (!p || p->dt <= 0) throw Error(IFEM_E_BADPARAM, "bad ifem_ins_params");
-  auto t0 = std::chrono::steady_clock::now();
-  launch_ins_assemble_ex(ctx, p, use_nonzero, 1, assemble_system ? AsmMode::Full : AsmMode::Rhs);
-  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  ctx->timing.assemble_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  timed_assemble(ctx, p, use_nonzero, 1, assemble_system ? AsmMode::Full : AsmMode::Rhs);
   IFEM_API_END
 }
 
@@ -638,7 +639,7 @@ int ifem_ins_newton_step(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_sol
       if (outer >= max_iterations) throw Error(IFEM_E_NEWTON_MAXIT, "Too many Newton iterations!");
       const int nz = apply_nonzero && outer == 0;
       v_zero(ctx, ctx->n_local, ctx->vec[IFEM_VEC_UPDATE].p); // newton_update = 0 (:427)
-      launch_ins_assemble(ctx, p, nz);
+      launch_ins_assemble_ex(ctx, p, nz, 0, AsmMode::Full);
       ifem_solve_stats st{};
       const int rc = ins_solve(ctx, p, o, nz, &st);
       if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");

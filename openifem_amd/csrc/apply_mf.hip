@@ -657,7 +657,7 @@ __global__ void k_lift_vector(int64_t n, const uint8_t *__restrict__ is_c, const
 void uu_lift_mf(ifem_ctx *ctx) {
   const int w = ctx->asm_constraint_set;
   if (!ctx->has_c[w]) return;
-  if (!ctx->geo.b0_valid || ctx->geo.B0.n != ctx->B.val.n) throw Error(IFEM_E_BADPARAM, "inhomogeneity lift: the unconstrained B is not cached");
+  const double *B0 = unconstrained_blocks(ctx).B0.p;
   double *rhs = ctx->vec[IFEM_VEC_RHS].p;
   apply_uu_mf_t<double, double, true>(ctx, ctx->cval[w].p, rhs, nullptr, 0);
   const int64_t nul = int64_t(ctx->dim) * ctx->nUl, npo = ctx->nPo;
@@ -665,7 +665,7 @@ void uu_lift_mf(ifem_ctx *ctx) {
   if ((int64_t)ctx->mf_lift.n != nul + npo) ctx->mf_lift.alloc(size_t(nul + npo));
   double *g = ctx->mf_lift.p, *bp = g + nul;
   if (nul) hipLaunchKernelGGL(k_lift_vector, dim3(unsigned(std::min<int64_t>((nul + 255) / 256, 4096))), dim3(256), 0, ctx->stream, nul, ctx->is_c[w].p, ctx->cval[w].p, g);
-  spmv_b(ctx, g, bp, 0, ctx->geo.B0.p);
+  spmv_b(ctx, g, bp, 0, B0);
   v_axpy(ctx, npo, -1.0, bp, rhs + int64_t(ctx->dim) * ctx->nUo);
 }
 

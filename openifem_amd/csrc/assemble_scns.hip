@@ -426,7 +426,18 @@ static void launch_scns_t(ifem_ctx *ctx, const ScnsArgs &A) {
   IFEM_HIP_CHECK(hipGetLastError());
 }
 
+static auto scns_launcher(int dim, int kv) -> void (*)(ifem_ctx *, const ScnsArgs &) {
+  if (dim == 2 && kv == 1) return launch_scns_t<2, 1>;
+  if (dim == 2 && kv == 2) return launch_scns_t<2, 2>;
+  if (dim == 3 && kv == 1) return launch_scns_t<3, 1>;
+  if (dim == 3 && kv == 2) return launch_scns_t<3, 2>;
+  throw Error(IFEM_E_BADPARAM, "unsupported (dim, kv)");
+}
+
 void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonzero) {
+  // every refusal before anything is allocated or zero-filled
+  if (p->formulation != IFEM_FORM_SCNSIM && p->formulation != IFEM_FORM_SUPG_INSIM) throw Error(IFEM_E_BADPARAM, "ifem_scns_params.formulation");
+  const auto launch = scns_launcher(ctx->dim, ctx->kv);
   hipStream_t s = ctx->stream;
   KScope ks(ctx, IFEM_KC_ASSEMBLE, 16.0 * double(ctx->Auu.val.n + ctx->Bt.val.n + ctx->B.val.n + ctx->Mp.val.n)); // (zero fill + cell kernel + block-Jacobi set-up)
   if (ctx->App.n != ctx->Mp.val.n) ctx->App.alloc(ctx->Mp.val.n);
@@ -437,37 +448,17 @@ void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonz
   IFEM_HIP_CHECK(hipMemsetAsync(ctx->App.p, 0, ctx->App.n * sizeof(double), s));
   IFEM_HIP_CHECK(hipMemsetAsync(ctx->vec[IFEM_VEC_RHS].p, 0, ctx->vec[IFEM_VEC_RHS].n * sizeof(double), s));
   ScnsArgs A{};
-  A.n_cells = ctx->n_cells; A.nUo = ctx->nUo; A.nUl = ctx->nUl; A.nPo = ctx->nPo;
-  A.fe = ctx->d_fe.p;
-  A.vcoords = ctx->vcoords.p; A.cell_unodes = ctx->cell_unodes.p; A.cell_pnodes = ctx->cell_pnodes.p;
-  A.cell_face_bid = ctx->cell_face_bid.p; A.indicator = ctx->indicator.p;
-  A.posUU = ctx->posUU.p; A.posUP = ctx->posUP.p; A.posPU = ctx->posPU.p; A.posPP = ctx->posPP.p;
-  A.rp_uu = ctx->Auu.rowptr.p; A.rp_bt = ctx->Bt.rowptr.p; A.rp_b = ctx->B.rowptr.p; A.rp_mp = ctx->Mp.rowptr.p;
-  A.v_uu = ctx->Auu.val.p; A.v_bt = ctx->Bt.val.p; A.v_b = ctx->B.val.p; A.v_pp = ctx->App.p;
-  A.rhs = ctx->vec[IFEM_VEC_RHS].p;
-  const int w = use_nonzero ? 1 : 0;
-  A.is_c = ctx->has_c[w] ? ctx->is_c[w].p : nullptr;
-  A.cval = ctx->has_c[w] ? ctx->cval[w].p : nullptr;
-  A.use_inhom = (use_nonzero && ctx->has_c[1]) ? 1 : 0;
-  A.eval = ctx->vec[IFEM_VEC_EVAL].p; A.present = ctx->vec[IFEM_VEC_PRESENT].p;
-  A.fsi_acc = ctx->indicator.p ? ctx->vec[IFEM_VEC_FSI_ACC].p : nullptr;
+  fill_cell_args(ctx, p, use_nonzero ? 1 : 0, A);
+  A.v_pp = ctx->App.p;
+  A.eval = ctx->vec[IFEM_VEC_EVAL].p;
   A.stress = ctx->stress_valid ? ctx->stress.p : nullptr;
   A.fsi_stress = ctx->fsi_stress.n ? ctx->fsi_stress.p : nullptr;
   A.sigma_pml = ctx->sigma_pml.n ? ctx->sigma_pml.p : nullptr;
   A.body_force = ctx->body_force.n ? ctx->body_force.p : nullptr;
   A.eddy = ctx->eddy_viscosity.n ? ctx->eddy_viscosity.p : nullptr;
   A.mu = p->viscosity; A.rho_f = p->rho; A.rho_s = p->solid_rho; A.dt = p->dt;
-  if (p->formulation != IFEM_FORM_SCNSIM && p->formulation != IFEM_FORM_SUPG_INSIM) throw Error(IFEM_E_BADPARAM, "ifem_scns_params.formulation");
   A.inc = p->formulation == IFEM_FORM_SUPG_INSIM;
-  for (int i = 0; i < 3; ++i) A.g[i] = p->gravity[i];
-  A.n_neumann = p->n_neumann;
-  for (int i = 0; i < 8; ++i) { A.neumann_id[i] = p->neumann_id[i]; A.neumann_p[i] = p->neumann_p[i]; }
-  const int dim = ctx->dim;
-  if (dim == 2 && ctx->kv == 1) launch_scns_t<2, 1>(ctx, A);
-  else if (dim == 2 && ctx->kv == 2) launch_scns_t<2, 2>(ctx, A);
-  else if (dim == 3 && ctx->kv == 1) launch_scns_t<3, 1>(ctx, A);
-  else if (dim == 3 && ctx->kv == 2) launch_scns_t<3, 2>(ctx, A);
-  else throw Error(IFEM_E_BADPARAM, "unsupported (dim, kv)");
+  launch(ctx, A);
   scns_assembled(ctx);
   bjac_setup(ctx);
   ctx->assembled = true;

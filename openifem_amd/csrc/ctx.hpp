@@ -309,20 +309,24 @@ struct GeoCache {
   int set_changes = 0;     // times the constrained-dof set changed while blocks were cached
   uint64_t seen_asm = 0;   // a multigrid level: the finest level's asm_version its `unchanged` last counted
   int64_t refresh_stamp = -1; // a coarse multigrid level: the finest level's assembly its blocks were last refreshed for (geo_cache = 2)
-  // An assembly asks for the blocks of set `k`: true when the cached ones are still those (`may_reuse`: the caching mode allows it).
-  // `count`: the request belongs to a new assembly (a multigrid level is asked once per preconditioner application) -- the kKeep-th such
-  // hit of a run whose set never changed gives the unconstrained copies back.
-  bool reuse(int64_t k, bool may_reuse, bool count) {
-    if (!(may_reuse && valid && key == k)) {
-      if (valid && key != k) ++set_changes;
-      unchanged = 0;
-      return false;
-    }
-    if (count && ++unchanged == kKeep && b0_valid && set_changes == 0) {
+  // An assembly asks for the blocks of set `k`: are the cached ones still those?  (Whether they may stay is the caller's caching mode.)
+  bool holds(int64_t k) const { return valid && key == k; }
+  // ... and tells what it does with them (assemble.hip::commit_assembly).  kept: they stay.  `count`: the request belongs to a new
+  // assembly (a multigrid level is asked once per preconditioner application) -- the kKeep-th such hit of a run whose set never
+  // changed gives the unconstrained copies back.
+  bool hit_releases(bool count) const { return count && unchanged + 1 == kKeep && b0_valid && set_changes == 0; }
+  void kept(bool count) {
+    if (hit_releases(count)) {
       B0.release(); Bt0.release(); Sm0.release();
       b0_valid = sm0_valid = false;
     }
-    return true;
+    if (count) ++unchanged;
+  }
+  // replaced: the assembly overwrites them with the blocks of set `k`; the driver sets `valid` again once they are written
+  void replaced(int64_t k) {
+    if (valid && key != k) ++set_changes;
+    unchanged = 0;
+    valid = false; key = k;
   }
 };
 
@@ -525,6 +529,17 @@ inline const DBuf<double> &stored_uu(const ifem_ctx *c) {
   if (c->Auu.val.n == 0 || !c->uu_is_stored)
     throw Error(IFEM_E_BADPARAM, "A_uu has no stored values (ifem_tuning::stored_uu = 0, or no assembly yet): this operation needs the block CSR");
   return c->Auu.val;
+}
+
+// The unconstrained B / B^T and the S_m of them (geometry cache), for their readers outside the assembly: the S_m of a new set
+// (linalg.hip::schur_numeric) and the inhomogeneity lift (apply_mf.hip::uu_lift_mf).  Refused when the cache has given them back
+// (GeoCache::kKeep) or never integrated them (ifem_tuning::geo_cache = 0).
+inline bool has_unconstrained_blocks(const ifem_ctx *c) { return c->geo.b0_valid && c->geo.B0.n == c->B.val.n; }
+// ... and B / B^T in place are masked copies of them, so S_m of the set differs from theirs only in the rows of constrained dofs
+inline bool masked_from_unconstrained(const ifem_ctx *c) { return c->tune.geo_cache >= 1 && c->geo.valid && has_unconstrained_blocks(c); }
+inline GeoCache &unconstrained_blocks(ifem_ctx *c) { // B0, Bt0; Sm0 / sm0_valid are schur_numeric's to form on first use
+  if (!has_unconstrained_blocks(c)) throw Error(IFEM_E_BADPARAM, "the unconstrained B / B^T of the geometry cache are not there (released, or ifem_tuning::geo_cache = 0)");
+  return c->geo;
 }
 
 // ---- Invalidation events: what goes stale when a writer rewrites device data.  Every writer names its write through one of these;

@@ -18,17 +18,34 @@ int64_t compact_flagged_rows(ifem_ctx *ctx, const int64_t *flag, int64_t n, DBuf
 void build_mf_cell_split(ifem_ctx *ctx); // several ranks: interior-first copy of the cell tables for the matrix-free apply
 
 // assemble.hip
-void launch_ins_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero);
-// what one launch of the INS cell kernel integrates
+// what one call of the INS assembly driver assembles
 enum class AsmMode {
   Rhs,           // the right-hand side only (the matrices stay as they are)
   Full,          // A_uu (or its matrix-free state), B, B^T, M_p, diag(M_u) and the right-hand side
-  LevelGeometry, // B, B^T, M_p, diag(M_u) only: a multigrid level of the pressure Schur complement
-  Unconstrained, // the same without any constraint (the mesh-only blocks of ctx.hpp::GeoCache); called by the driver itself
+  LevelGeometry, // B, B^T, M_p, diag(M_u) only: a multigrid level of the pressure Schur complement (no A_uu, no right-hand side state)
 };
 void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode);
-// B, B^T, M_p, diag(M_u) only (multigrid levels of the pressure Schur complement): no A_uu, no right-hand side state
-void launch_ins_assemble_geometry(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero);
+// the part of the argument block that the INS and the SCnsIM cell kernels share (AsmArgs, ScnsArgs: the same field names);
+// `cset`: the constraint object the scatter applies (0 / 1), -1: none
+template <class Args, class Params>
+void fill_cell_args(const ifem_ctx *ctx, const Params *p, int cset, Args &A) {
+  A.n_cells = ctx->n_cells; A.nUo = ctx->nUo; A.nUl = ctx->nUl; A.nPo = ctx->nPo;
+  A.fe = ctx->d_fe.p;
+  A.vcoords = ctx->vcoords.p; A.cell_unodes = ctx->cell_unodes.p; A.cell_pnodes = ctx->cell_pnodes.p;
+  A.cell_face_bid = ctx->cell_face_bid.p; A.indicator = ctx->indicator.p;
+  A.posUU = ctx->posUU.p; A.posUP = ctx->posUP.p; A.posPU = ctx->posPU.p; A.posPP = ctx->posPP.p;
+  A.rp_uu = ctx->Auu.rowptr.p; A.rp_bt = ctx->Bt.rowptr.p; A.rp_b = ctx->B.rowptr.p; A.rp_mp = ctx->Mp.rowptr.p;
+  A.v_uu = ctx->Auu.val.p; A.v_bt = ctx->Bt.val.p; A.v_b = ctx->B.val.p; A.rhs = ctx->vec[IFEM_VEC_RHS].p;
+  const bool constrained = cset >= 0 && ctx->has_c[cset];
+  A.is_c = constrained ? ctx->is_c[cset].p : nullptr;
+  A.cval = constrained ? ctx->cval[cset].p : nullptr;
+  A.use_inhom = (cset == 1 && constrained) ? 1 : 0;
+  A.present = ctx->vec[IFEM_VEC_PRESENT].p;
+  A.fsi_acc = ctx->indicator.p ? ctx->vec[IFEM_VEC_FSI_ACC].p : nullptr;
+  for (int i = 0; i < 3; ++i) A.g[i] = p->gravity[i];
+  A.n_neumann = p->n_neumann;
+  for (int i = 0; i < 8; ++i) { A.neumann_id[i] = p->neumann_id[i]; A.neumann_p[i] = p->neumann_p[i]; }
+}
 
 // fsi.hip -- fluid-side inputs of MPI::FSI (source/mpi_fsi.cpp:96-127,142-223,291-663)
 void fsi_set_solid(ifem_ctx *ctx, const ifem_fsi_solid *s);

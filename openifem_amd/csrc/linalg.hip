@@ -745,9 +745,8 @@ void schur_numeric(ifem_ctx *ctx) {
   // With the unconstrained blocks at hand (assemble.hip: B / B^T are masked copies of them) only the rows whose B row touches
   // a constrained dof differ from the S_m of the unconstrained blocks: that one is formed once per mesh, a new set copies it
   // and recomputes the touched rows (a few per cent of them on a box with Dirichlet walls).
-  GeoCache &g = ctx->geo;
-  const bool partial = ctx->tune.geo_cache >= 1 && g.b0_valid && g.valid && g.B0.n == ctx->B.val.n;
-  if (partial) {
+  if (masked_from_unconstrained(ctx)) {
+    GeoCache &g = unconstrained_blocks(ctx);
     if (!g.sm0_valid) {
       if (g.Sm0.n != ctx->Sm.val.n) g.Sm0.alloc(ctx->Sm.val.n);
       launch_schur(ctx, n, nullptr, g.B0.p, g.Bt0.p, g.Sm0.p);

@@ -563,7 +563,7 @@ static void mg_sm_setup(MgSm &M, int use_nonzero) {
       // not once per preconditioner application)
       ifem_ctx *f0 = M.L[0].ctx;
       if (!(c->tune.geo_cache == 2 && c->geo.refresh_stamp == f0->asm_version)) {
-        launch_ins_assemble_geometry(c, S.P, use_nonzero);
+        launch_ins_assemble_ex(c, S.P, use_nonzero, 0, AsmMode::LevelGeometry);
         c->geo.refresh_stamp = f0->asm_version;
       }
       sm_ensure(S);

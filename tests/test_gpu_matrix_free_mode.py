@@ -159,6 +159,38 @@ def test_repeated_inhomogeneous_assemblies_survive_the_release_of_the_unconstrai
     ctx.close()
 
 
+def test_refused_assembly_leaves_the_context_and_the_device_as_they_were():
+    # stored_uu = 0 takes B / B^T from the geometry cache: with geo_cache = 0 the assembly is refused, and the refusal comes before
+    # anything is zero-filled or recorded -- the next accepted assembly of the same set KEEPS the cached blocks, so it shows what
+    # the refused one left behind.  (The sums are atomic-ordered: 1e-12 of the largest entry, not bitwise.)
+    capi = _capi()
+    m, dofs, vals, ev, pr, rng = _box(3, 2, 47)
+    ctx = capi.Context(m.dim, m.kv, m.vcoords, m.cell_unodes, m.cell_pnodes, m.cell_face_bid, m.n_unodes, m.n_pnodes)
+    _matrix_free(ctx, capi)
+    ctx.set_constraints(0, dofs, None)
+    ctx.set_constraints(1, dofs, vals)
+    ctx.vec_set(capi.VEC_PRESENT, pr)
+    ctx.vec_set(capi.VEC_EVAL, ev)
+    P = capi.make_params(**_kw(3))
+    ctx.assemble(P, True)
+    x = rng.standard_normal(m.n_dofs)
+    y0, b0 = ctx.system_vmult(x), ctx.vec_get(capi.VEC_RHS)
+    assert ctx.uu_stored_bytes() == 0
+    ctx.set_tuning(geo_cache=0)
+    with pytest.raises(capi.IfemError) as e:
+        ctx.assemble(P, True)
+    assert e.value.code == capi.E_BADPARAM and "geo_cache" in str(e.value)
+    assert ctx.uu_stored_bytes() == 0
+    ctx.set_tuning(geo_cache=1)
+    ctx.assemble(P, True)
+    y1, b1 = ctx.system_vmult(x), ctx.vec_get(capi.VEC_RHS)
+    ey, eb = np.abs(y1 - y0).max() / np.abs(y0).max(), np.abs(b1 - b0).max() / np.abs(b0).max()
+    print("after the refusal: system_vmult", ey, "rhs", eb)
+    assert ey <= 1e-12 and eb <= 1e-12
+    assert ctx.uu_stored_bytes() == 0
+    ctx.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. Newton update
 

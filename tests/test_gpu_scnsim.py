@@ -250,8 +250,7 @@ def test_reference_driver_acoustic_pml_mpi(tmp_path):
     assert abs(v.max()) < 5e-2 and abs(v).max() > 0
 
 
-@pytest.mark.parametrize("dim,kv,reps", [(2, 1, (5, 4)), (3, 1, (3, 3, 2)), (2, 2, (3, 2))])
-def test_supg_insim_assembly_matches_oracle(dim, kv, reps):
+def _supg_insim_parity(dim, kv, reps, refuse_first=False):
     # IFEM_FORM_SUPG_INSIM (mpi_insim_supg.cpp:100-262): the incompressible SUPG/PSPG/LSIC integrand; indicator, PML and
     # stress inputs are present on purpose and must be ignored by this formulation
     capi = _capi()
@@ -277,10 +276,25 @@ def test_supg_insim_assembly_matches_oracle(dim, kv, reps):
     ctx.set_indicator((rng.uniform(size=m.n_cells) < 0.5).astype(np.int32))
     ctx.set_scns_fields(rng.uniform(0, 3, (m.n_cells, nq)), bf, None)
     ctx.update_stress(kw["mu"])
+    if refuse_first:
+        with pytest.raises(capi.IfemError) as e:
+            ctx.scns_assemble(capi.make_scns_params(formulation=7, **kw), True)
+        assert e.value.code == capi.E_BADPARAM and "formulation" in str(e.value)
     ctx.scns_assemble(capi.make_scns_params(formulation=capi.FORM_SUPG_INSIM, **kw), True)
     A, b = ctx.export_csr(0), ctx.vec_get(capi.VEC_RHS)
     assert abs(A - Ao).max() / abs(Ao).max() < 1e-11
     assert np.abs(b - bo).max() / np.abs(bo).max() < 1e-11
+
+
+@pytest.mark.parametrize("dim,kv,reps", [(2, 1, (5, 4)), (3, 1, (3, 3, 2)), (2, 2, (3, 2))])
+def test_supg_insim_assembly_matches_oracle(dim, kv, reps):
+    _supg_insim_parity(dim, kv, reps)
+
+
+def test_refused_formulation_is_followed_by_a_valid_assembly_that_matches_the_oracle():
+    # ifem_scns_params.formulation is checked before anything is allocated or zero-filled: the valid assembly that follows the
+    # refusal meets the same parity bounds
+    _supg_insim_parity(2, 1, (5, 4), refuse_first=True)
 
 
 def test_reference_driver_fluid_pressure_driven_mpi_insim_supg():
