@@ -220,6 +220,12 @@ typedef struct {
                             from the vertex coordinates: every subdivided_hyper_rectangle level) runs the constant-geometry variants of the
                             matrix-free A_uu kernels (cell kernel and coarse-level node blocks): J^-1 = diag(1 / h), JxW = prod(h) w_q, no
                             vertex coordinates are read.  Other meshes are unaffected.  0: the general kernels everywhere */
+  int32_t inner_f32;     /* 1 (default): the flexible inner GMRES of IFEM_AINV_MG (inner_maxit > 0) keeps its V and Z bases in single precision,
+                            as the V-cycle between them and the cell arithmetic of its operator are: the cycle reads the basis column and
+                            writes the Z column directly (no conversion passes), the operator product reads the Z column as float, and the
+                            cycle skips the passes nothing reads (the zero fill of its solution vectors, the dead direction of the last
+                            pre-smoothing step).  w, the Hessenberg arithmetic, the stopping test and the restart residual stay fp64.
+                            0: fp64 bases around the conversions, the V-cycle with every pass (for comparing one build with itself) */
 } ifem_tuning;
 /* Initialise an ifem_tuning with ifem_default_tuning before changing fields: a zero-initialised struct gets the documented defaults
  * only for the fields where 0 is not a meaningful value (asm3_cpb, scns_pc, pvv_sweeps, b2pp_sweeps). */

@@ -39,6 +39,12 @@ int ifem_test_restart_fits(ifem_ctx *ctx, int columns);
  * lengths the context detected (zeros: not a uniform box level; entries past dim are zero), whatever the tuning says. */
 int ifem_test_mf_uniform(ifem_ctx *ctx, double *h);
 
+/* y_u = A_uu x_u on the velocity part of two context vectors as the single-precision inner solver of IFEM_AINV_MG forms the product
+ * (ifem_tuning::inner_f32; solver.hip::uu_apply_f32col): x rounded to float, its ghost entries exchanged as float, single-precision
+ * cell arithmetic, fp64 result.  After ifem_ins_assemble / ifem_imex_assemble.  Stages the column in a level vector of the A_uu V-cycle and
+ * may (re)allocate it: a captured cycle of the context is then captured anew at its next use. */
+int ifem_test_uu_vmult_f32col(ifem_ctx *ctx, int dst, int src);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,7 +119,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
 void ifem_default_tuning(ifem_tuning *t) {
   t->geo_cache = 1; t->xcd_swizzle = 1; t->asm_skip = 0; t->spmv_lanes = 32; t->sm_lanes = 32; t->mf_f32 = 1;
   t->tpp_operator = 0; t->spmv_pipe = 1; t->halo_overlap = 1; t->asm3_variant = 0; t->cg_single_reduction = 1; t->asm3_cpb = 2; t->tpp_milu_permille = 950; t->tpp_ilu_order = 2; t->basis_pad = 32 * 33; t->tpp_tri_sweeps = 0; t->uu_row_order = 1; t->eig_steps = 0; t->vcycle_graph_cells = 262144;
-  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1;
+  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1;
 }
 
 int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
@@ -812,6 +812,19 @@ int ifem_uu_vmult(ifem_ctx *ctx, int dst, int src, int variant) {
   else if (variant == IFEM_AINV_GMRES_BJACOBI || variant == IFEM_AINV_GMRES_BJACOBI_F32)
     spmv_uu(ctx, xe, nullptr, ctx->vec[dst].p, variant == IFEM_AINV_GMRES_BJACOBI_F32);
   else throw Error(IFEM_E_BADPARAM, "variant: IFEM_AINV_GMRES_BJACOBI, _F32, _MF or IFEM_AINV_MG (single-precision matrix-free)");
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_test_uu_vmult_f32col(ifem_ctx *ctx, int dst, int src) {
+  IFEM_API_BEGIN
+  if (!vec_ok(dst) || !vec_ok(src) || is_ext(dst) || is_ext(src) || dst == src) throw Error(IFEM_E_BADPARAM, "use two non-ghosted vectors");
+  if (!ctx->assembled) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_vmult_f32col called before ifem_ins_assemble");
+  const int64_t nuo = int64_t(ctx->dim) * ctx->nUo, nv = int64_t(ctx->dim) * ctx->nUl + 8;
+  auto &col = ctx->mguf_vec[4]; // (a level vector of the V-cycle, idle outside of it)
+  if ((int64_t)col.n < nv) { col.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(col.p, 0, col.n * sizeof(float), ctx->stream)); }
+  v_cvt_d2f(ctx, nuo, ctx->vec[src].p, col.p);
+  uu_apply_f32col(ctx, col.p, ctx->vec[dst].p);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
 }

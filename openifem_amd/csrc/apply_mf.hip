@@ -441,7 +441,8 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
 // FUSE (the multigrid smoother, solver.hip::mg_uu_smooth): the product t = (A x)_node is not stored but consumed on the
 // spot -- fuse.mode 1: xs += x, r -= t (residual update after the coarse correction); mode 2: the Chebyshev step
 // xs += x, r -= t, x <- a x + b B r with the inverse node block B (x is the smoother's direction vector and is updated in
-// place: the cell kernel that read it has completed, and a thread only touches the entries of its own node).
+// place: the cell kernel that read it has completed, and a thread only touches the entries of its own node).  fuse.first: xs = x
+// is stored without reading xs (the first step of a sweep from zero: no memset of xs before it).
 // LIFT (uu_lift_mf; x = the constraint values, y = the right-hand side): free rows y_i -= sum, constrained rows y_r = d_r x_r with
 // the same d_r as above.
 template <int DIM, typename R, bool FUSE, typename V, bool LIFT = false>
@@ -487,15 +488,21 @@ __global__ void k_mf_gather(int64_t n, int nn, const int64_t *__restrict__ inc_p
     }
   } else {
     double xv[DIM], rv[DIM], bj[DIM * DIM];
+    if (fuse.mode >= 2) {
 #pragma unroll
-    for (int e = 0; e < DIM * DIM; ++e) bj[e] = double(bjf[nd * DIM * DIM + e]);
+      for (int e = 0; e < DIM * DIM; ++e) bj[e] = double(bjf[nd * DIM * DIM + e]);
+    } else { // mode 1 applies no node block: only the diagonal entry of a constrained row is needed
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) bj[c * DIM + c] = fl[c] ? double(bjf[nd * DIM * DIM + c * DIM + c]) : 1.0;
+    }
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
       const int64_t i = nd * DIM + c;
       xv[c] = double(x[i]);
       const double t = fl[c] ? xv[c] / bj[c * DIM + c] : s[c];
       rv[c] = double(fuse.r[i]) - t;
-      fuse.xs[i] = V(double(fuse.xs[i]) + xv[c]);
+      const double x0 = fuse.first ? 0.0 : double(fuse.xs[i]); // first: xs is not read (it holds nothing yet)
+      fuse.xs[i] = V(x0 + xv[c]);
       fuse.r[i] = V(rv[c]);
     }
     if (fuse.mode >= 2) {
@@ -619,7 +626,9 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   const MfFuseT<XT> f0 = fuse ? *fuse : MfFuseT<XT>{};
   // node gather: the per-cell results and the incidence entries once, the node's row pointer; fused form: the inverse node block
   // (single precision) and the smoother's vectors (mode 1: xs, r read + written, x read; modes 2 / 3: d written too)
-  const double per_node = ctx->dim * double(sizeof(XT)) * (fuse ? (fuse->mode >= 2 ? 6.0 : 5.0) : 2.0) + (fuse ? 4.0 * ctx->dim * ctx->dim : 0.0) + 8.0 + ctx->dim;
+  // (fuse->first: xs is not read; mode 1 reads no node block)
+  const double per_node = ctx->dim * double(sizeof(XT)) * (fuse ? (fuse->mode >= 2 ? 6.0 : 5.0) - (fuse->first ? 1.0 : 0.0) : 2.0) +
+                          (fuse && fuse->mode >= 2 ? 4.0 * ctx->dim * ctx->dim : 0.0) + 8.0 + ctx->dim;
   KScope ksg(ctx, IFEM_KC_MF_GATHER, double(ctx->n_cells) * ctx->nu * (ctx->dim * sizeof(R) + 4.0) + double(ctx->nUo) * per_node);
 #define IFEM_MFG(D, F)                                                                                                 \
   hipLaunchKernelGGL((k_mf_gather<D, R, F, XT, LIFT>), dim3(unsigned((n / D + 255) / 256)), dim3(256), 0, s, n, ctx->nu, ctx->uinc.rowptr.p, \
@@ -667,6 +676,10 @@ void uu_lift_mf(ifem_ctx *ctx) {
   if (nul) hipLaunchKernelGGL(k_lift_vector, dim3(unsigned(std::min<int64_t>((nul + 255) / 256, 4096))), dim3(256), 0, ctx->stream, nul, ctx->is_c[w].p, ctx->cval[w].p, g);
   spmv_b(ctx, g, bp, 0, B0);
   v_axpy(ctx, npo, -1.0, bp, rhs + int64_t(ctx->dim) * ctx->nUo);
+}
+
+void apply_uu_mf_f32in(ifem_ctx *ctx, const float *xu, double *yu, int part) {
+  apply_uu_mf_t<float, float>(ctx, xu, yu, nullptr, part);
 }
 
 void apply_uu_mf_f32v(ifem_ctx *ctx, const float *xu, const MfFuseT<float> *fuse, int part) {

@@ -451,6 +451,7 @@ struct ifem_ctx {
   ifem::DBuf<double> vec[IFEM_N_VECS];
   // Krylov workspace
   ifem::DBuf<double> krylovV, krylovZ, innerV, innerZ, work;
+  ifem::DBuf<float> innerVf, innerZf; // bases of the single-precision flexible inner solver of IFEM_AINV_MG (ifem_tuning::inner_f32)
   ifem::DBuf<double> scal; // device scalars for reductions
   ifem::DBuf<double> partials; // per-block partial sums of the fused dot products [64][4096]
   double *h_scal = nullptr; // pinned host mirror

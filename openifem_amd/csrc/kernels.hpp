@@ -75,12 +75,14 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
 // optional epilogue of the matrix-free product t = A_uu x (owned rows), see apply_mf.hip::k_mf_gather: t is consumed instead of
 // stored.  mode 1: xs += x, r -= t; mode 2 additionally d = a x + b B r (B = inverse node block, single-precision copy) -- the
 // Chebyshev step of the multigrid smoother, d being the owned part of x itself; mode 3: mode 1, then d = b B r into another
-// vector d -- the first direction of the smoothing sweep that follows the coarse correction
+// vector d -- the first direction of the smoothing sweep that follows the coarse correction.  In mode 1 the node block is only
+// read where a constraint flag needs its diagonal
 template <typename V>
 struct MfFuseT {
   int mode = 0;
   double a = 0, b = 0;
   V *xs = nullptr, *r = nullptr, *d = nullptr;
+  int first = 0; // 1: xs holds nothing yet (the first step of a sweep that starts from zero): xs = x is stored, xs is not read
 };
 using MfFuse = MfFuseT<double>;
 // part (several ranks, build_mf_cell_split): 0 every cell, then the node gather; 1 only the cells whose nodes are all owned
@@ -89,6 +91,8 @@ void apply_uu_mf(ifem_ctx *ctx, const double *xu, double *yu, bool single = fals
 // the same on SINGLE-PRECISION vectors, fused form only (the level vectors of the A_uu V-cycle, solver.hip): single-precision
 // cell arithmetic, x and the vectors of `fuse` are float
 void apply_uu_mf_f32v(ifem_ctx *ctx, const float *xu, const MfFuseT<float> *fuse, int part = 0);
+// the plain product on a single-precision input (a Z column of the single-precision inner solver): same cell kernel, fp64 result
+void apply_uu_mf_f32in(ifem_ctx *ctx, const float *xu, double *yu, int part = 0);
 void uu_lift_mf(ifem_ctx *ctx); // apply_mf.hip: inhomogeneity lift of the right-hand side after a stored_uu = 0 assembly
 // scalar velocity operator S^ (IFEM_AINV_SCALAR_GMRES): auxiliary data, SpMV on all components, Jacobi
 void shat_refresh(ifem_ctx *ctx, bool f32);
@@ -194,6 +198,11 @@ void mg_csr_apply_nodes_f32(ifem_ctx *ctx, const MgCsr &M, const float *x, const
 void v_cvt_d2f(ifem_ctx *ctx, int64_t n, const double *x, float *y);
 void v_cvt_f2d(ifem_ctx *ctx, int64_t n, const float *x, double *y);
 void v_axpy_f32v(ifem_ctx *ctx, int64_t n, float a, const float *x, float *y);
+// entry and exit of the A_uu V-cycle (ifem_tuning::inner_f32): r = float(src), d = c0 B r in one pass; out = x + d
+void vc_entry(ifem_ctx *ctx, double c0, const double *src, float *r, float *d);
+void vc_entry_f32(ifem_ctx *ctx, double c0, const float *src, float *r, float *d);
+void vc_exit(ifem_ctx *ctx, int64_t n, const float *x, const float *d, double *out);
+void vc_exit_f32(ifem_ctx *ctx, int64_t n, const float *x, const float *d, float *out);
 
 // all-reduce helpers (identity for a single rank)
 void allreduce_sum(ifem_ctx *ctx, double *host_vals, int n);
@@ -233,6 +242,8 @@ int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o
 void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, const double *src, double *dst);
 void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst);
 int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
+// y = A_uu z on a compact owned SINGLE-PRECISION column (ghosts refreshed on a float copy), single-precision cell arithmetic, fp64 result
+void uu_apply_f32col(ifem_ctx *ctx, const float *z, double *y);
 
 // owned-range dot over a block vector (u range + p range), all-reduced
 double bv_dot(ifem_ctx *ctx, const double *x, const double *y);

@@ -480,6 +480,55 @@ __global__ void k_cvt_f2d(int64_t n, const float *__restrict__ x, double *__rest
 __global__ void k_axpy_f32v(int64_t n, float a, const float *__restrict__ x, float *__restrict__ y) {
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) y[i] += a * x[i];
 }
+// Entry of the A_uu V-cycle (ifem_tuning::inner_f32): r = src rounded to the level precision and the first direction d = c0 B r per
+// node, in one pass over src -- what k_cvt_d2f followed by k_cheb_init_block compute, without the second read of r
+template <int DIM, typename T>
+__global__ void k_vc_entry(int64_t n_nodes, double c0, const float *__restrict__ bj, const T *__restrict__ src, float *__restrict__ r,
+                           float *__restrict__ d) {
+  const int64_t nd = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (nd >= n_nodes) return;
+  double rv[DIM];
+#pragma unroll
+  for (int j = 0; j < DIM; ++j) {
+    const float rf = float(src[nd * DIM + j]);
+    r[nd * DIM + j] = rf;
+    rv[j] = double(rf);
+  }
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    double t = 0;
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) t += double(bj[nd * DIM * DIM + i * DIM + j]) * rv[j];
+    d[nd * DIM + i] = float(c0 * t);
+  }
+}
+template <typename T>
+static void vc_entry_t(ifem_ctx *ctx, double c0, const T *src, float *r, float *d) {
+  const int64_t n = ctx->nUo;
+  if (!n) return;
+  const dim3 g(unsigned((n + 255) / 256)), b(256);
+  const float *bjf = bjac_f32_ptr(ctx);
+  KScope ks(ctx, IFEM_KC_VECTOR, double(n) * ctx->dim * (4.0 * ctx->dim + 8.0 + sizeof(T)));
+  if (ctx->dim == 3) hipLaunchKernelGGL((k_vc_entry<3, T>), g, b, 0, ctx->stream, n, c0, bjf, src, r, d);
+  else hipLaunchKernelGGL((k_vc_entry<2, T>), g, b, 0, ctx->stream, n, c0, bjf, src, r, d);
+}
+void vc_entry(ifem_ctx *ctx, double c0, const double *src, float *r, float *d) { vc_entry_t<double>(ctx, c0, src, r, d); }
+void vc_entry_f32(ifem_ctx *ctx, double c0, const float *src, float *r, float *d) { vc_entry_t<float>(ctx, c0, src, r, d); }
+
+// Exit: out = x + d, the last Chebyshev update of the finest level delivered where the caller wants it (k_axpy_f32v followed by k_cvt_f2d)
+template <typename T>
+__global__ void k_vc_exit(int64_t n, const float *__restrict__ x, const float *__restrict__ d, T *__restrict__ out) {
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) out[i] = T(x[i] + d[i]);
+}
+void vc_exit(ifem_ctx *ctx, int64_t n, const float *x, const float *d, double *out) {
+  KScope ks(ctx, IFEM_KC_VECTOR, 16.0 * double(n));
+  if (n) hipLaunchKernelGGL(k_vc_exit<double>, dim3(mgrid(n)), dim3(256), 0, ctx->stream, n, x, d, out);
+}
+void vc_exit_f32(ifem_ctx *ctx, int64_t n, const float *x, const float *d, float *out) {
+  KScope ks(ctx, IFEM_KC_VECTOR, 12.0 * double(n));
+  if (n) hipLaunchKernelGGL(k_vc_exit<float>, dim3(mgrid(n)), dim3(256), 0, ctx->stream, n, x, d, out);
+}
+
 void v_cvt_d2f(ifem_ctx *ctx, int64_t n, const double *x, float *y) {
   KScope ks(ctx, IFEM_KC_VECTOR, 12.0 * double(n));
   if (n) hipLaunchKernelGGL(k_cvt_d2f, dim3(mgrid(n)), dim3(256), 0, ctx->stream, n, x, y);

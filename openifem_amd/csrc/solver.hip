@@ -128,21 +128,23 @@ static int gmres(ifem_ctx *ctx, int64_t n, int64_t ld, bool reorth, const OpFn &
 // 128^3 would hold 61 vectors of 425 MB where the bench's solves use 2 to 14.  Contents are kept; new columns are zero.
 // max_cols: the most columns the solver can ever ask for (restart length + 1): growth never goes beyond it (rounded up to the
 // multiple of 4 the fused kernels read), so FGMRES(30) ends at 32 columns, not at 36
-static void grow_basis(ifem_ctx *c, DBuf<double> &B, int64_t ld, int64_t cols, int64_t max_cols) {
+template <typename T>
+static void grow_basis(ifem_ctx *c, DBuf<T> &B, int64_t ld, int64_t cols, int64_t max_cols) {
   const int64_t have = ld > 0 ? int64_t(B.n) / ld : 0;
   if (have >= cols || ld <= 0) return;
   const int64_t cap = std::max<int64_t>((std::max(max_cols, cols) + 3) / 4 * 4, cols);
   const int64_t want = std::min(cap, std::max<int64_t>((cols + 7) / 8 * 8, have + have / 2));
-  DBuf<double> nb;
+  DBuf<T> nb;
   nb.alloc(size_t(want) * size_t(ld));
-  if (have > 0) IFEM_HIP_CHECK(hipMemcpyAsync(nb.p, B.p, size_t(have) * size_t(ld) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  IFEM_HIP_CHECK(hipMemsetAsync(nb.p + size_t(have) * size_t(ld), 0, size_t(want - have) * size_t(ld) * sizeof(double), c->stream));
+  if (have > 0) IFEM_HIP_CHECK(hipMemcpyAsync(nb.p, B.p, size_t(have) * size_t(ld) * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+  IFEM_HIP_CHECK(hipMemsetAsync(nb.p + size_t(have) * size_t(ld), 0, size_t(want - have) * size_t(ld) * sizeof(T), c->stream));
   IFEM_HIP_CHECK(hipStreamSynchronize(c->stream));
   B.swap(nb);
 }
 // the callback gmres() gets for the pair (V: up to max_v columns, Z: up to max_v - 1)
-static std::function<void(int, double *&, double *&)> basis_grower(ifem_ctx *c, DBuf<double> &Vb, DBuf<double> &Zb, int64_t ld, int max_v) {
-  return [c, &Vb, &Zb, ld, max_v](int cols, double *&V, double *&Z) {
+template <typename T>
+static std::function<void(int, T *&, T *&)> basis_grower(ifem_ctx *c, DBuf<T> &Vb, DBuf<T> &Zb, int64_t ld, int max_v) {
+  return [c, &Vb, &Zb, ld, max_v](int cols, T *&V, T *&Z) {
     grow_basis(c, Vb, ld, std::min(cols, max_v), max_v);
     grow_basis(c, Zb, ld, std::min(cols - 1, max_v - 1), max_v - 1);
     V = Vb.p; Z = Zb.p;
@@ -213,6 +215,85 @@ static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, c
     v_scale_store_f32(ctx, n, 1.0, w, vy);
     Pinv(vy, z);
     v_axpy(ctx, n, 1.0, z, x);
+    if (done || it >= maxit) break;
+  }
+  if (res_out) *res_out = res;
+  return it;
+}
+
+// Flexible inner solver of IFEM_AINV_MG (ifem_tuning::inner_f32): right-preconditioned restarted FGMRES, x0 = 0, with BOTH bases in single
+// precision -- the preconditioner (a single-precision V-cycle) reads column j of V and writes column j of Z, the operator (single-precision
+// cell arithmetic) reads that Z column and writes the fp64 w.  w, b, x, the Hessenberg arithmetic, the stopping test and the restart residual
+// b - A x are fp64; Gram-Schmidt is the single fused pass of gmres(reorth = false).  Same iteration as gmres(flexible = true) up to the rounding
+// of the stored columns.  The fused kernels take at most 64 columns per call: longer bases (the self-lengthening restart) go in chunks.
+using OpF32In = std::function<void(const float *, double *)>;
+using OpF32F32 = std::function<void(const float *, float *)>;
+static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32In &Af, const OpF32F32 &Pinv, const double *b, double *x,
+                      int m, int maxit, double tol, float *V, float *Z, double *w, double *res_out,
+                      const std::function<void(double *, int)> &allreduce, const std::function<void(int, float *&, float *&)> &ensure) {
+  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), h(m + 4);
+  constexpr int kChunk = 64;
+  auto mdot = [&](int k, const float *B, double *out) {
+    for (int k0 = 0; k0 < k; k0 += kChunk) v_mdot_f32(ctx, n, std::min(kChunk, k - k0), B + int64_t(k0) * ld, ld, w, out + k0);
+    allreduce(out, k);
+  };
+  auto maxpy = [&](int k, const float *B, const double *coef, double *dst, double *norm2) { // dst -= sum coef_i B_i
+    for (int k0 = 0; k0 < k; k0 += kChunk) {
+      const bool last = k0 + kChunk >= k;
+      v_maxpy_f32(ctx, n, std::min(kChunk, k - k0), B + int64_t(k0) * ld, ld, coef + k0, dst, last ? norm2 : nullptr);
+    }
+    if (norm2) allreduce(norm2, 1);
+  };
+  v_zero(ctx, n, x);
+  int it = 0;
+  double res = 0;
+  bool first = true;
+  while (true) {
+    const double *r0 = w;
+    if (first) { r0 = b; first = false; }
+    else { A(x, w); v_axpby(ctx, n, 1.0, b, -1.0, w); }
+    double bb = v_dot(ctx, n, r0, r0);
+    allreduce(&bb, 1);
+    const double beta = std::sqrt(bb);
+    res = beta;
+    if (res <= tol || it >= maxit || !std::isfinite(res)) break;
+    v_scale_store_f32(ctx, n, 1.0 / beta, r0, V);
+    std::fill(g.begin(), g.end(), 0.0);
+    g[0] = beta;
+    int j = 0;
+    bool done = false;
+    for (; j < m && it < maxit; ++j) {
+      ensure(j + 2, V, Z); // columns 0 .. j + 1 of V, 0 .. j of Z
+      float *zj = Z + (int64_t)j * ld;
+      Pinv(V + (int64_t)j * ld, zj);
+      Af(zj, w);
+      mdot(j + 1, V, h.data());
+      double ww = 0;
+      maxpy(j + 1, V, h.data(), w, &ww);
+      for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i];
+      const double hn = std::sqrt(ww);
+      H[(size_t)(j + 1) * m + j] = hn;
+      if (hn > 0) v_scale_store_f32(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
+      for (int i = 0; i < j; ++i) {
+        const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
+        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
+        H[(size_t)i * m + j] = t;
+      }
+      const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
+      cs[j] = a / r; sn[j] = c / r;
+      H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
+      g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
+      res = std::fabs(g[j + 1]);
+      ++it;
+      if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
+    }
+    for (int i = j - 1; i >= 0; --i) {
+      double t = g[i];
+      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
+      y[i] = t / H[(size_t)i * m + i];
+    }
+    for (int i = 0; i < j; ++i) h[i] = -y[i];
+    maxpy(j, Z, h.data(), x, nullptr); // x += sum y_i z_i
     if (done || it >= maxit) break;
   }
   if (res_out) *res_out = res;
@@ -790,6 +871,27 @@ static void uu_apply_level_f32(SolveState &S, float *x_ext, const MfFuseT<float>
   apply_uu_mf_f32v(c, x_ext, fuse);
 }
 
+// the plain product on a compact owned single-precision column (a Z column of fgmres_f32), fp64 result: one rank reads the column in
+// place; several ranks extend a copy by the ghost entries (level vector 3: the cycle does not use it), the interior cells running
+// while the halo travels
+void uu_apply_f32col(ifem_ctx *c, const float *z, double *y) {
+  if (c->halo.nranks == 1) { apply_uu_mf_f32in(c, z, y); return; }
+  const int64_t nuo = int64_t(c->dim) * c->nUo, nv = int64_t(c->dim) * c->nUl + 8;
+  auto &ext = c->mguf_vec[3];
+  if ((int64_t)ext.n < nv) { ext.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(ext.p, 0, ext.n * sizeof(float), c->stream)); }
+  if (nuo) IFEM_HIP_CHECK(hipMemcpyAsync(ext.p, z, size_t(nuo) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  if (halo_overlap_ok(c)) {
+    build_mf_cell_split(c);
+    halo_start_f32(c, ext.p);
+    apply_uu_mf_f32in(c, ext.p, y, 1);
+    halo_wait(c);
+    apply_uu_mf_f32in(c, ext.p, y, 2);
+    return;
+  }
+  halo_exchange_f32(c, ext.p);
+  apply_uu_mf_f32in(c, ext.p, y);
+}
+
 static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
   ifem_ctx *f0 = M.L[0].ctx;
   // size of the evaluation point the bounds below were estimated at: A_uu carries rho C(u), so a bound taken at a small
@@ -882,8 +984,13 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
   }
 }
 
-// d_ready: the first direction d = (1/theta) B r is already in place (written by the fused residual update, MfFuse mode 3)
-static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, float *x, float *r, bool keep_r, bool d_ready = false) {
+// d_ready: the first direction d = (1/theta) B r is already in place (written by the fused residual update, MfFuse mode 3, or by the
+// entry kernel of the cycle)
+// trim (ifem_tuning::inner_f32): the passes nothing reads are left out -- x_fresh: x holds nothing yet, the first fused step stores xs = x
+// instead of adding to a zeroed vector; the last step of a keep_r sweep updates x and r only (mode 1: its new direction would be
+// overwritten by the residual update after the coarse correction); no_exit: the closing x += d is the caller's (it delivers x + d elsewhere)
+static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, float *x, float *r, bool keep_r, bool d_ready = false,
+                         bool trim = false, bool x_fresh = false, bool no_exit = false) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *d = c->mguf_vec[2].p;
@@ -892,29 +999,38 @@ static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, fl
   if (!d_ready) cheb_init_block_f32(c, 1.0 / theta, r, d);
   for (int k = 0; k < nsteps; ++k) {
     const bool last = k == nsteps - 1;
-    if (last && !keep_r) { v_axpy_f32v(c, S.nuo, 1.0f, d, x); break; }
+    if (last && !keep_r) {
+      if (no_exit) break;
+      if (k == 0 && x_fresh) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream)); // (a one-step sweep from zero)
+      v_axpy_f32v(c, S.nuo, 1.0f, d, x);
+      break;
+    }
     const double rho_new = 1.0 / (2.0 * sigma - rho_old);
     // x += d; r -= A d; d = rho_new rho_old d + (2 rho_new / delta) B r, fused into the node gather of the product
     MfFuseT<float> f;
-    f.mode = 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
+    f.mode = (trim && last) ? 1 : 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
+    f.first = (k == 0 && x_fresh) ? 1 : 0;
     uu_apply_level_f32(S, d, &f);
     rho_old = rho_new;
   }
 }
 
 // level l: mguf_vec[1] = V(mguf_vec[0]); mguf_vec[0] is overwritten by the residual
-static void mg_uu_vcycle(MgUu &M, size_t l) {
+// trim = false: every pass of the cycle as it was written first (ifem_tuning::inner_f32 = 0).  trim = true: level 0 starts from r AND the first
+// direction d (vc_entry) and ends BEFORE its last update x += d (vc_exit delivers x + d); no level zeroes its x (see mg_uu_smooth)
+static void mg_uu_vcycle(MgUu &M, size_t l, bool trim = false) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *r = c->mguf_vec[0].p, *x = c->mguf_vec[1].p;
   const double hi = 1.1 * c->uu_lmax;
-  IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream));
+  const bool top = trim && l == 0;
+  if (!trim) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream));
   if (l + 1 == M.L.size()) {
-    mg_uu_smooth(M, l, 24, hi / 400.0, hi, x, r, false);
+    mg_uu_smooth(M, l, 24, hi / 400.0, hi, x, r, false, top, trim, trim, top);
     return;
   }
   const double lo = hi / M.ratio;
-  mg_uu_smooth(M, l, M.nu, lo, hi, x, r, true);
+  mg_uu_smooth(M, l, M.nu, lo, hi, x, r, true, top, trim, trim);
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
   mg_csr_apply_nodes_f32(c, c->mg_Ru, r, c->mg_Ru_mask, cc->mguf_vec[0].p);
@@ -922,14 +1038,20 @@ static void mg_uu_vcycle(MgUu &M, size_t l) {
   // sum over the ranks; from there down nothing is exchanged and the prolongation reads the replica directly
   if (c->mg_replica) allreduce_sum_vec_f32(c, cc->mguf_vec[0].p, int64_t(cc->dim) * cc->nUo, cc->mguf_vec[4].p);
   else halo_reverse_add_f32(cc, cc->mguf_vec[0].p);
-  mg_uu_vcycle(M, l + 1);
+  mg_uu_vcycle(M, l + 1, trim);
   halo_exchange_f32(cc, cc->mguf_vec[1].p);
   float *e = c->mguf_vec[4].p;
   mg_csr_apply_nodes_f32(c, c->mg_Pu, cc->mguf_vec[1].p, c->mg_Pu_mask, e);
   MfFuseT<float> f; // x += e; r -= A e; d = (1/theta) B r: the first direction of the post-smoothing sweep
   f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = 1.0 / (0.5 * (hi + lo));
   uu_apply_level_f32(S, e, &f);
-  mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, false, true);
+  mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, false, true, trim, false, top);
+}
+// the first direction of level 0 is (1 / theta) B r with the theta of the sweep the cycle starts with
+static double mg_uu_entry_c0(const MgUu &M) {
+  const double hi = 1.1 * M.L[0].ctx->uu_lmax;
+  const double lo = M.L.size() == 1 ? hi / 400.0 : hi / M.ratio;
+  return 1.0 / (0.5 * (hi + lo));
 }
 
 static void precond_vmult(SolveState &S, const double *src, double *dst) {
@@ -1083,15 +1205,19 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
     if (!c->mf_valid) throw Error(IFEM_E_BADPARAM, "IFEM_AINV_MG needs the operator state of ifem_ins_assemble / ifem_imex_assemble");
     mg_uu_setup(Mu);
     OpFn Amf = [&](const double *x, double *y) { uu_apply_level(S, x, y); };
+    // ifem_tuning::inner_f32: single-precision bases around the cycle, and the cycle without the passes nothing reads (mg_uu_vcycle)
+    const bool trim = c->tune.inner_f32 != 0;
+    OpF32In Amf32 = [&](const float *z, double *y) { uu_apply_f32col(c, z, y); }; // the product on a Z column of fgmres_f32
     // the cycle itself: eagerly, or as a captured hipGraph (ctx.hpp::VcGraph) on small single-rank chains
     bool graph_ok = c->tune.vcycle_graph_cells > 0 && c->n_cells <= c->tune.vcycle_graph_cells && !c->profile && !kprof_root(c).on && !profiler_attached();
     for (const SolveState &L : Mu.L) graph_ok = graph_ok && L.ctx->halo.nranks == 1 && !L.ctx->mg_replica && !L.ctx->profile;
     auto run_vcycle = [&]() {
-      if (!graph_ok) { mg_uu_vcycle(Mu, 0); return; }
+      if (!graph_ok) { mg_uu_vcycle(Mu, 0, trim); return; }
       std::vector<uint64_t> key;
       auto put = [&](const void *ptr) { key_ptr(key, ptr); };
       auto putd = [&](double v) { key_f64(key, v); };
       key.push_back(Mu.L.size()); key.push_back(uint64_t(Mu.nu)); key.push_back(uint64_t(Mu.nu_post)); putd(Mu.ratio);
+      key.push_back(uint64_t(trim)); // which passes the captured cycle consists of
       for (const SolveState &L : Mu.L) {
         ifem_ctx *lc = L.ctx;
         (void)bjac_f32_ptr(lc); // lazy state (the single-precision copy of the inverse node blocks) stays outside the graph
@@ -1105,16 +1231,29 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
         put(lc->bjac.p); put(lc->vcoords.p); put(lc->cell_unodes.p); put(lc->uinc.col.p);
         putd(lc->uu_lmax); putd(lc->mf_params.viscosity); putd(lc->mf_params.rho); putd(lc->mf_params.grad_div); putd(lc->mf_params.dt);
       }
-      if (!graph_run(c, c->vc_graph, key, [&]() { mg_uu_vcycle(Mu, 0); })) {
+      if (!graph_run(c, c->vc_graph, key, [&]() { mg_uu_vcycle(Mu, 0, trim); })) {
         c->tune.vcycle_graph_cells = 0;
         graph_ok = false;
         if (o->verbose) fprintf(stderr, "[ifem] hipGraph capture of the A_uu V-cycle failed: eager launches from now on\n");
       }
     };
+    // the cycle between its entry and exit runs on the fixed level vectors (and is what a hipGraph captures): whatever vector it is
+    // applied to only appears as an argument of the entry and exit kernels outside of it
     OpFn Vc = [&](const double *x, double *y) {
-      v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
+      if (!trim) {
+        v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
+        run_vcycle();
+        v_cvt_f2d(c, S.nuo, c->mguf_vec[1].p, y);
+        return;
+      }
+      vc_entry(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
       run_vcycle();
-      v_cvt_f2d(c, S.nuo, c->mguf_vec[1].p, y);
+      vc_exit(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
+    };
+    OpF32F32 Vcf = [&](const float *x, float *y) { // column j of V -> column j of Z (trim only)
+      vc_entry_f32(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
+      run_vcycle();
+      vc_exit_f32(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
     };
     // one attempt of A~^-1 with the V-cycle; returns false when the result is not finite (a Chebyshev bound below the
     // spectral radius turns the smoothers into amplifiers)
@@ -1139,17 +1278,29 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
         // GMRES(40), 59 with GMRES(100)) stagnates across restarts; the bases grow on demand, so the longer cycle costs memory
         // only where it is used.  Capped at 128 columns and at a quarter of the free device memory.
         const int mi = std::max(std::max(1, o->inner_restart), c->inner_restart_eff);
-        grow_basis(c, c->innerV, ld, std::min(mi + 1, kBasisStart), mi + 1);
-        grow_basis(c, c->innerZ, ld, std::min(mi, kBasisStart), mi);
-        const auto grow = basis_grower(c, c->innerV, c->innerZ, ld, mi + 1);
-        const int its = gmres(c, S.nuo, ld, /*reorth=*/false, Amf, Vc, true, S.utmp, dst0, mi, o->inner_maxit, inner_rel_now * un,
-                              c->innerV.p, c->innerZ.p, S.inner_w, &res, mdot, nullptr, &grow);
+        int its;
+        // one pair of bases per context: a change of ifem_tuning::inner_f32 gives the other pair back (a no-op when it is empty).  The fp64
+        // basis the node-block-Jacobi fallback below grows under inner_f32 = 1 is deliberately temporary: the next application frees it here
+        if (trim) { c->innerV.release(); c->innerZ.release(); } else { c->innerVf.release(); c->innerZf.release(); }
+        if (trim) {
+          grow_basis(c, c->innerVf, ld, std::min(mi + 1, kBasisStart), mi + 1);
+          grow_basis(c, c->innerZf, ld, std::min(mi, kBasisStart), mi);
+          const auto grow = basis_grower(c, c->innerVf, c->innerZf, ld, mi + 1);
+          its = fgmres_f32(c, S.nuo, ld, Amf, Amf32, Vcf, S.utmp, dst0, mi, o->inner_maxit, inner_rel_now * un, c->innerVf.p, c->innerZf.p,
+                           S.inner_w, &res, [&](double *v, int k) { allreduce_sum(c, v, k); }, grow);
+        } else {
+          grow_basis(c, c->innerV, ld, std::min(mi + 1, kBasisStart), mi + 1);
+          grow_basis(c, c->innerZ, ld, std::min(mi, kBasisStart), mi);
+          const auto grow = basis_grower(c, c->innerV, c->innerZ, ld, mi + 1);
+          its = gmres(c, S.nuo, ld, /*reorth=*/false, Amf, Vc, true, S.utmp, dst0, mi, o->inner_maxit, inner_rel_now * un,
+                      c->innerV.p, c->innerZ.p, S.inner_w, &res, mdot, nullptr, &grow);
+        }
         S.st.inner_iters += its;
         if (its > 2 * mi && mi < 128) {
           size_t fr = 0, tot = 0;
           (void)hipMemGetInfo(&fr, &tot);
           int want = std::min(128, 2 * mi);
-          const double per_col = 2.0 * double(ld) * sizeof(double);
+          const double per_col = 2.0 * double(ld) * (trim ? sizeof(float) : sizeof(double));
           int fits = int(std::min<double>(128.0, 0.25 * double(fr) / std::max(per_col, 1.0)));
           if (c->test_restart_fits > 0) fits = c->test_restart_fits; // test aid (ifem_test_restart_fits): a rank that is short of memory
           want = std::min(want, std::max(fits, mi));
@@ -1173,6 +1324,9 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
       if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle returned non-finite values: re-estimating the Chebyshev bounds\n");
       mg_uu_setup(Mu, /*force_bounds=*/true);
       res = 0;
+      // the fused single-precision kernels read, with zero coefficients, up to 3 columns past the ones in use: none may keep a NaN
+      if (c->innerVf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerVf.p, 0, c->innerVf.n * sizeof(float), c->stream));
+      if (c->innerZf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerZf.p, 0, c->innerZf.n * sizeof(float), c->stream));
       if (!attempt()) {
         if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle still non-finite: node-block Jacobi for this application\n");
         OpFn Pbj = [&](const double *x, double *y) { bjac_apply(c, x, y); };
@@ -1183,6 +1337,10 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
           grow_basis(c, c->innerV, ldj, std::min(cols, mj + 1), mj + 1); // (not flexible: one z vector)
           V = c->innerV.p;
         };
+        // gmres() stores its first basis vector before it asks `growv` for columns: the fp64 basis must exist here (with
+        // ifem_tuning::inner_f32 the context has not allocated it before this fallback)
+        grow_basis(c, c->innerV, ldj, std::min(mj + 1, kBasisStart), mj + 1);
+        if (S.nuo > 0 && !c->innerV.p) throw Error(IFEM_E_BADPARAM, "inner GMRES: no basis storage");
         S.st.inner_iters += gmres(c, S.nuo, ldj, /*reorth=*/false, Amf, Pbj, false, S.utmp, dst0, mj,
                                   std::max(o->inner_maxit, 50), inner_rel_now * un, c->innerV.p, S.inner_z, S.inner_w, &res, mdot, nullptr, &growv);
       }
@@ -1247,7 +1405,9 @@ static void carve_workspace(SolveState &S, bool krylov) {
   grow_basis(c, c->krylovV, basis_ld(S.ctx, S.n), std::min(m + 1, kBasisStart), m + 1); // the rest on demand (basis_grower)
   grow_basis(c, c->krylovZ, basis_ld(S.ctx, S.n), std::min(m, kBasisStart), m);
   // the inner solve of IFEM_AINV_MG is flexible too and grows its bases the same way; the other kinds' kernels want theirs whole
-  grow_inner_basis(c, (int64_t)(S.o->ainv_kind == IFEM_AINV_MG ? std::min(mi + 1, kBasisStart) : mi + 1) * basis_ld(S.ctx, S.nuo));
+  // (its single-precision bases, ifem_tuning::inner_f32, are the solver's own: precond_vmult allocates them where it runs that solver)
+  if (!(S.o->ainv_kind == IFEM_AINV_MG && c->tune.inner_f32 && S.o->inner_maxit > 0))
+    grow_inner_basis(c, (int64_t)(S.o->ainv_kind == IFEM_AINV_MG ? std::min(mi + 1, kBasisStart) : mi + 1) * basis_ld(S.ctx, S.nuo));
 }
 
 void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, const double *src, double *dst) {
