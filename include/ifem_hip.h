@@ -226,6 +226,14 @@ typedef struct {
                             cycle skips the passes nothing reads (the zero fill of its solution vectors, the dead direction of the last
                             pre-smoothing step).  w, the Hessenberg arithmetic, the stopping test and the restart residual stay fp64.
                             0: fp64 bases around the conversions, the V-cycle with every pass (for comparing one build with itself) */
+  int32_t uu_smoother;   /* smoother of the A_uu V-cycle of IFEM_AINV_MG.  0 (default): Chebyshev on the inverse node blocks (node-block
+                            Jacobi).  1: on every level that is a uniform box (mf_uniform in effect) of Q2 velocity on one rank without
+                            hanging-node lines, the inverse node blocks are replaced by the additive vertex-patch sum B = sum_v R_v^T A_v^-1
+                            R_v (patch = the +-1 node lattice box around a mesh vertex; A_v from mu K + rho/dt M + gamma rho GradDiv with the
+                            constraint rule of the assembly, convection left to the residual): it sees the near-null space of the grad-div
+                            term that the node blocks miss at large gamma rho / mu.  Other levels keep the node blocks.  Same Chebyshev
+                            recurrence, interval [lambda_max / ratio, 1.1 lambda_max] with lambda_max(B A_uu) estimated per smoother kind.
+                            Any other value: IFEM_E_BADPARAM */
 } ifem_tuning;
 /* Initialise an ifem_tuning with ifem_default_tuning before changing fields: a zero-initialised struct gets the documented defaults
  * only for the fields where 0 is not a meaningful value (asm3_cpb, scns_pc, pvv_sweeps, b2pp_sweeps). */

@@ -99,7 +99,7 @@ class Tuning(C.Structure):
     _fields_ = [("geo_cache", C.c_int32), ("xcd_swizzle", C.c_int32), ("asm_skip", C.c_int32), ("spmv_lanes", C.c_int32),
                 ("sm_lanes", C.c_int32), ("mf_f32", C.c_int32), ("tpp_operator", C.c_int32), ("spmv_pipe", C.c_int32), ("halo_overlap", C.c_int32),
                 ("asm3_variant", C.c_int32), ("cg_single_reduction", C.c_int32), ("asm3_cpb", C.c_int32), ("tpp_milu_permille", C.c_int32), ("tpp_ilu_order", C.c_int64), ("basis_pad", C.c_int64), ("tpp_tri_sweeps", C.c_int32), ("uu_row_order", C.c_int32), ("eig_steps", C.c_int32), ("vcycle_graph_cells", C.c_int32),
-                ("scns_pc", C.c_int32), ("pvv_sweeps", C.c_int32), ("b2pp_sweeps", C.c_int32), ("scns_inner_reorth", C.c_int32), ("scns_inner_left", C.c_int32), ("scns_graph", C.c_int32), ("stored_uu", C.c_int32), ("mf_uniform", C.c_int32), ("inner_f32", C.c_int32)]
+                ("scns_pc", C.c_int32), ("pvv_sweeps", C.c_int32), ("b2pp_sweeps", C.c_int32), ("scns_inner_reorth", C.c_int32), ("scns_inner_left", C.c_int32), ("scns_graph", C.c_int32), ("stored_uu", C.c_int32), ("mf_uniform", C.c_int32), ("inner_f32", C.c_int32), ("uu_smoother", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -139,7 +139,8 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_fsi_set_solid", "ifem_fsi_update_indicator", "ifem_fsi_find_fluid_bc", "ifem_fsi_get_stress",
            "ifem_get_constraints", "ifem_fsi_fluid_at_points", "ifem_comm_stats_get", "ifem_comm_stats_level", "ifem_true_residual", "ifem_tpp_ilu_probe", "ifem_tpp_override", "ifem_scns_pc_probe", "ifem_test_restart_fits",
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
-           "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col"]
+           "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
+           "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info"]
 
 # ifem_abi_sizeof(which): the ctypes mirror of every struct of the header
 ABI_STRUCTS = None  # filled below (needs every class defined)
@@ -226,6 +227,8 @@ def load():
     L.ifem_test_restart_fits.argtypes = [C.c_void_p, C.c_int]
     L.ifem_test_mf_uniform.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_test_uu_vmult_f32col.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.ifem_test_uu_patch_vmult.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.ifem_test_uu_patch_info.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -536,6 +539,19 @@ class Context:
         """(takes the constant-geometry matrix-free A_uu kernels, detected cell edges [3]) -- ifem_test_mf_uniform"""
         h = np.zeros(3)
         return bool(self._chk(self.L.ifem_test_mf_uniform(self.h, _ptr(h)))), h
+
+    def uu_patch_info(self):
+        """(eligible, patches, patch types, bytes of the inverse tables) of the vertex-patch smoother -- ifem_test_uu_patch_info"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.ifem_test_uu_patch_info(self.h, _ptr(out)))
+        return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def uu_patch_vmult(self, x):
+        """B x_u with the vertex-patch B of the last assembly's operator state; x and the result are whole context vectors of
+        which the velocity part counts -- ifem_test_uu_patch_vmult"""
+        self.vec_set(VEC_TMP, x)
+        self._chk(self.L.ifem_test_uu_patch_vmult(self.h, VEC_UPDATE, VEC_TMP))
+        return self.vec_get(VEC_UPDATE)
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

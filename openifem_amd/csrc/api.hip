@@ -119,7 +119,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
 void ifem_default_tuning(ifem_tuning *t) {
   t->geo_cache = 1; t->xcd_swizzle = 1; t->asm_skip = 0; t->spmv_lanes = 32; t->sm_lanes = 32; t->mf_f32 = 1;
   t->tpp_operator = 0; t->spmv_pipe = 1; t->halo_overlap = 1; t->asm3_variant = 0; t->cg_single_reduction = 1; t->asm3_cpb = 2; t->tpp_milu_permille = 950; t->tpp_ilu_order = 2; t->basis_pad = 32 * 33; t->tpp_tri_sweeps = 0; t->uu_row_order = 1; t->eig_steps = 0; t->vcycle_graph_cells = 262144;
-  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1;
+  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->uu_smoother = 0;
 }
 
 int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
@@ -132,6 +132,7 @@ int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
   if (t->asm3_cpb > 0 && t->asm3_cpb != 2 && t->asm3_cpb != 4 && t->asm3_cpb != 8) throw Error(IFEM_E_BADPARAM, "asm3_cpb must be 2, 4 or 8 (cells per workgroup of the 3D Q2/Q1 cell kernel)");
   if (t->tpp_ilu_order < -1 || t->tpp_ilu_order > 2) throw Error(IFEM_E_BADPARAM, "tpp_ilu_order must be -1, 0, 1 or 2");
   if (t->scns_pc != 0 && t->scns_pc != 1 && t->scns_pc != 2) throw Error(IFEM_E_BADPARAM, "scns_pc must be 1 (explicit T_pp) or 2 (the reference's structure); 0 = default");
+  if (t->uu_smoother != 0 && t->uu_smoother != 1) throw Error(IFEM_E_BADPARAM, "uu_smoother must be 0 (node-block Jacobi) or 1 (vertex patches on uniform box levels)");
   ctx->tune = *t;
   ++ctx->graph_epoch;
   if (ctx->tune.asm3_cpb <= 0) ctx->tune.asm3_cpb = 2; // a zero-initialised struct: the defaults of the fields added after round 4
@@ -826,6 +827,35 @@ int ifem_test_uu_vmult_f32col(ifem_ctx *ctx, int dst, int src) {
   v_cvt_d2f(ctx, nuo, ctx->vec[src].p, col.p);
   uu_apply_f32col(ctx, col.p, ctx->vec[dst].p);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_test_uu_patch_vmult(ifem_ctx *ctx, int dst, int src) {
+  IFEM_API_BEGIN
+  if (!vec_ok(dst) || !vec_ok(src) || is_ext(dst) || is_ext(src) || dst == src) throw Error(IFEM_E_BADPARAM, "use two non-ghosted vectors");
+  if (!ctx->assembled || !ctx->mf_valid) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_patch_vmult called before ifem_ins_assemble");
+  if (!patch_setup(ctx)) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_patch_vmult: this level cannot take the vertex-patch smoother (ifem_test_uu_patch_info)");
+  const int64_t nuo = int64_t(ctx->dim) * ctx->nUo, nv = int64_t(ctx->dim) * ctx->nUl + 8;
+  for (int k = 3; k <= 4; ++k) { // (level vectors of the V-cycle, idle outside of it)
+    auto &v = ctx->mguf_vec[k];
+    if ((int64_t)v.n < nv) { v.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(v.p, 0, v.n * sizeof(float), ctx->stream)); }
+  }
+  v_cvt_d2f(ctx, nuo, ctx->vec[src].p, ctx->mguf_vec[3].p);
+  patch_apply(ctx, 0.0, 1.0, ctx->mguf_vec[3].p, ctx->mguf_vec[4].p);
+  v_cvt_f2d(ctx, nuo, ctx->mguf_vec[4].p, ctx->vec[dst].p);
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_test_uu_patch_info(ifem_ctx *ctx, int64_t out[4]) {
+  IFEM_API_BEGIN
+  if (!out) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_patch_info: null output");
+  const bool ok = ctx->mf_valid ? patch_setup(ctx) : patch_eligible(ctx);
+  const bool tables = ok && ctx->patch.valid;
+  out[0] = ok ? 1 : 0;
+  out[1] = tables ? ctx->patch.n_patches : 0;
+  out[2] = tables ? ctx->patch.n_types : 0;
+  out[3] = tables ? ctx->patch.inv_bytes : 0;
   IFEM_API_END
 }
 

@@ -280,6 +280,22 @@ struct MgCsr {
 } // namespace ifem
 
 namespace ifem {
+// Vertex-patch smoother of the A_uu V-cycle on a uniform box level (patch.hip; ifem_tuning::uu_smoother = 1): the patch of a mesh
+// vertex is the lattice box of +-1 velocity node around it, clipped at the domain.  All patches with the same present nodes and the
+// same constrained dofs (a "type") share one inverse.  Built on the host once per (mu, rho, gamma, dt, h, constrained-dof set).
+struct PatchSmoother {
+  bool eligible = false, valid = false; // the level can take the patch smoother / the tables below belong to `key`
+  double key[8] = {0, 0, 0, 0, 0, 0, 0, -1};
+  int64_t n_patches = 0, inv_bytes = 0;
+  int n_types = 0;
+  DBuf<int32_t> tab;   // [n_patches][3^dim] velocity nodes of every patch (-1: clipped), patches sorted by (colour, type)
+  DBuf<float> inv;     // [n_types][N][N] inverse patch matrices, N = dim 3^dim (symmetric; clipped nodes: identity rows)
+  DBuf<int32_t> work;  // [n_work][3] work items of the kernel: type, first patch, patches (one colour, one type each)
+  int work_ptr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // work items of colour c: [work_ptr[c], work_ptr[c + 1])
+};
+} // namespace ifem
+
+namespace ifem {
 // reference tables of the 3D Q2/Q1 cell kernel (assemble3.hip), built on the host, copied into LDS by every workgroup
 struct Tabs3 {
   double Nz[16], dNz[16];           // [q2 (4)][a2 (4)] 1D shape values / derivatives, zero for q2 = 3 or a2 = 3 (MFMA padding)
@@ -411,6 +427,11 @@ struct ifem_ctx {
   int64_t uu_lmax_asm = -1; // ifem_tuning::geo_cache = 2: the finest level's assembly the A_uu bound was last refreshed for
   int64_t asm_version = 0, uu_mg_version = -1; // full assemblies done / the assembly the A_uu V-cycle data belong to
   double uu_lmax_key[6] = {0, 0, 0, 0, 0, -1};  // (mu, rho, gamma, dt, noconv, constrained-dof set) of the cached eigenvalue bound
+  // the bound is one of B A_uu, so it belongs to a smoother kind (0 node-block Jacobi, 1 vertex patches): the fields above describe kind
+  // `uu_bound_kind`, the other kind's bound waits here and the two are swapped when the level changes its smoother (solver.hip::mg_uu_setup)
+  int uu_bound_kind = 0;
+  struct UuBound { double lmax = 0, evn = -1, key[6] = {0, 0, 0, 0, 0, -1}; ifem::DBuf<double> eig; } uu_bound_other;
+  ifem::PatchSmoother patch; // vertex-patch smoother of this level (patch.hip)
   int64_t sm_version = 0, sm_mg_version = -1; // S_m values rebuilt / the version the V-cycle data belong to
   // explicit T_pp = A_pp - A_pv Binv A_vp on the pattern of Sm and its dense LU (tpp.hip)
   ifem::DBuf<double> Tpp, tpp_diag;

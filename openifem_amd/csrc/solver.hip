@@ -938,6 +938,15 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
         c->mg_mask_key[0] = key[0]; c->mg_mask_key[1] = key[1];
       }
     }
+    // the smoother's B of this level: the inverse node blocks, or (ifem_tuning::uu_smoother = 1 on an eligible level) the vertex-patch
+    // sum of patch.hip, whose tables are made here, outside of any captured cycle.  The bound below is one of B A_uu: each kind keeps its own
+    const int kind = (c->tune.uu_smoother == 1 && patch_setup(c)) ? 1 : 0;
+    if (kind != c->uu_bound_kind) {
+      auto &o = c->uu_bound_other;
+      std::swap(c->uu_lmax, o.lmax); std::swap(c->uu_lmax_evn, o.evn); c->uu_eig.swap(o.eig);
+      for (int i = 0; i < 6; ++i) std::swap(c->uu_lmax_key[i], o.key[i]);
+      c->uu_bound_kind = kind;
+    }
     // eigenvalue bound of (block D)^-1 A_uu: depends on the parameters and the constrained-dof set, hardly on the evaluation
     // point (the viscous and mass terms carry the top of the spectrum): estimated once per such state
     const double key[6] = {f0->mf_params.viscosity, f0->mf_params.rho, f0->mf_params.grad_div, f0->mf_params.dt,
@@ -964,6 +973,11 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
       if (!(nx > 0)) break;
       v_scale(c, S.nuo, 1.0 / std::sqrt(nx), x);
       uu_apply_level(S, x, y);
+      if (kind == 1) { // the patch B acts on the single-precision level vectors (3 and 4 are idle outside of a cycle)
+        v_cvt_d2f(c, S.nuo, y, c->mguf_vec[3].p);
+        patch_apply(c, 0.0, 1.0, c->mguf_vec[3].p, c->mguf_vec[4].p);
+        v_cvt_f2d(c, S.nuo, c->mguf_vec[4].p, z);
+      } else
       bjac_apply(c, y, z);
       double nz = v_dot(c, S.nuo, z, z);
       allreduce_sum(c, &nz, 1);
@@ -996,7 +1010,8 @@ static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, fl
   float *d = c->mguf_vec[2].p;
   const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
   double rho_old = 1.0 / sigma;
-  if (!d_ready) cheb_init_block_f32(c, 1.0 / theta, r, d);
+  const bool patch = patch_active(c); // B = the vertex-patch sum: the fused product updates x and r (mode 1), the patch kernel the direction
+  if (!d_ready) { if (patch) patch_apply(c, 0.0, 1.0 / theta, r, d); else cheb_init_block_f32(c, 1.0 / theta, r, d); }
   for (int k = 0; k < nsteps; ++k) {
     const bool last = k == nsteps - 1;
     if (last && !keep_r) {
@@ -1006,6 +1021,15 @@ static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, fl
       break;
     }
     const double rho_new = 1.0 / (2.0 * sigma - rho_old);
+    if (patch) {
+      MfFuseT<float> f;
+      f.mode = 1; f.xs = x; f.r = r; f.d = d; f.first = (k == 0 && x_fresh) ? 1 : 0;
+      uu_apply_level_f32(S, d, &f);
+      // (the direction of the last step of a keep_r sweep is never read: the residual update after the coarse correction writes a new one)
+      if (!last) patch_apply(c, rho_new * rho_old, 2.0 * rho_new / delta, r, d);
+      rho_old = rho_new;
+      continue;
+    }
     // x += d; r -= A d; d = rho_new rho_old d + (2 rho_new / delta) B r, fused into the node gather of the product
     MfFuseT<float> f;
     f.mode = (trim && last) ? 1 : 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
@@ -1044,7 +1068,9 @@ static void mg_uu_vcycle(MgUu &M, size_t l, bool trim = false) {
   mg_csr_apply_nodes_f32(c, c->mg_Pu, cc->mguf_vec[1].p, c->mg_Pu_mask, e);
   MfFuseT<float> f; // x += e; r -= A e; d = (1/theta) B r: the first direction of the post-smoothing sweep
   f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = 1.0 / (0.5 * (hi + lo));
+  if (patch_active(c)) f.mode = 1; // x += e; r -= A e here, the first direction from the patch kernel
   uu_apply_level_f32(S, e, &f);
+  if (patch_active(c)) patch_apply(c, 0.0, f.b, r, f.d);
   mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, false, true, trim, false, top);
 }
 // the first direction of level 0 is (1 / theta) B r with the theta of the sweep the cycle starts with
@@ -1229,6 +1255,7 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
         key.push_back(lc->graph_epoch); key.push_back(uint64_t(lc->tune.mf_f32));
         key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) putd(hd); // which cell kernels, and their constants
         put(lc->bjac.p); put(lc->vcoords.p); put(lc->cell_unodes.p); put(lc->uinc.col.p);
+        key.push_back(uint64_t(patch_active(lc))); put(lc->patch.tab.p); put(lc->patch.inv.p); put(lc->patch.work.p); // the level's smoother and its tables
         putd(lc->uu_lmax); putd(lc->mf_params.viscosity); putd(lc->mf_params.rho); putd(lc->mf_params.grad_div); putd(lc->mf_params.dt);
       }
       if (!graph_run(c, c->vc_graph, key, [&]() { mg_uu_vcycle(Mu, 0, trim); })) {
@@ -1246,11 +1273,19 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
         v_cvt_f2d(c, S.nuo, c->mguf_vec[1].p, y);
         return;
       }
+      if (patch_active(c)) { // the first direction is the patch kernel's: the entry only rounds the residual
+        v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
+        patch_apply(c, 0.0, mg_uu_entry_c0(Mu), c->mguf_vec[0].p, c->mguf_vec[2].p);
+      } else
       vc_entry(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
       run_vcycle();
       vc_exit(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
     };
     OpF32F32 Vcf = [&](const float *x, float *y) { // column j of V -> column j of Z (trim only)
+      if (patch_active(c)) {
+        if (S.nuo) IFEM_HIP_CHECK(hipMemcpyAsync(c->mguf_vec[0].p, x, size_t(S.nuo) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        patch_apply(c, 0.0, mg_uu_entry_c0(Mu), c->mguf_vec[0].p, c->mguf_vec[2].p);
+      } else
       vc_entry_f32(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
       run_vcycle();
       vc_exit_f32(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
