@@ -419,18 +419,20 @@ struct ifem_ctx {
   int64_t mg_mask_key[2] = {-1, -1};          // constrained-dof sets (flag ids of this level and the coarser one) of the masks
   ifem::DBuf<double> sm_dinv, mg_vec[6], mgu_vec[5];
   ifem::DBuf<float> mguf_vec[5]; // single-precision level vectors of the A_uu V-cycle (solver.hip)
-  double sm_lmax = 0, uu_lmax = 0;
-  double uu_evn = 0, uu_lmax_evn = -1; // ||evaluation point|| of the current assembly (finest level) / of the cached A_uu bound
+  double sm_lmax = 0;
+  double uu_evn = 0; // ||evaluation point|| of the current assembly (finest level)
   int64_t uu_evn_asm = -1;
-  // last iterate of the two power iterations: the next estimate (new constrained-dof set, same mesh) starts from it
-  ifem::DBuf<double> sm_eig, uu_eig;
-  int64_t uu_lmax_asm = -1; // ifem_tuning::geo_cache = 2: the finest level's assembly the A_uu bound was last refreshed for
+  ifem::DBuf<double> sm_eig; // last iterate of the S_m power iteration: the next estimate (new constrained-dof set, same mesh) starts from it
   int64_t asm_version = 0, uu_mg_version = -1; // full assemblies done / the assembly the A_uu V-cycle data belong to
-  double uu_lmax_key[6] = {0, 0, 0, 0, 0, -1};  // (mu, rho, gamma, dt, noconv, constrained-dof set) of the cached eigenvalue bound
-  // the bound is one of B A_uu, so it belongs to a smoother kind (0 node-block Jacobi, 1 vertex patches): the fields above describe kind
-  // `uu_bound_kind`, the other kind's bound waits here and the two are swapped when the level changes its smoother (solver.hip::mg_uu_setup)
+  // cached Chebyshev bound of the A_uu V-cycle's smoother.  It is a bound of B A_uu, so each smoother kind (0 node-block Jacobi, 1 vertex
+  // patches) keeps its own; solver.hip::mg_uu_setup selects the level's kind, the cycle reads that entry
+  struct UuBound {
+    double lmax = 0, evn = -1, key[6] = {0, 0, 0, 0, 0, -1}; // estimate; ||evaluation point|| and (mu, rho, gamma, dt, noconv, constrained-dof set) it was taken at
+    ifem::DBuf<double> eig; // last iterate of its power iteration: the next estimate (new constrained-dof set, same mesh) starts from it
+    int64_t asm_stamp = -1; // ifem_tuning::geo_cache = 2: the finest level's assembly it was last checked for
+  } uu_bound[2];
   int uu_bound_kind = 0;
-  struct UuBound { double lmax = 0, evn = -1, key[6] = {0, 0, 0, 0, 0, -1}; ifem::DBuf<double> eig; } uu_bound_other;
+  double uu_lmax() const { return uu_bound[uu_bound_kind].lmax; }
   ifem::PatchSmoother patch; // vertex-patch smoother of this level (patch.hip)
   int64_t sm_version = 0, sm_mg_version = -1; // S_m values rebuilt / the version the V-cycle data belong to
   // explicit T_pp = A_pp - A_pv Binv A_vp on the pattern of Sm and its dense LU (tpp.hip)

@@ -1,11 +1,11 @@
 // solver.hip -- host drivers of the Krylov path; every vector/matrix operation is a HIP kernel on ctx->stream.
-//   fgmres()            deal.II SolverFGMRES as used by InsIM::solve            (mpi_insim.cpp:379-388)
+//   gmres(flexible)     deal.II SolverFGMRES as used by InsIM::solve            (mpi_insim.cpp:379-388)
 //   cg()                PETSc KSPCG + PreconditionNone                          (mpi_insim.cpp:73-82,88-108)
-//   precond_vmult()     InsIM::BlockSchurPreconditioner::vmult                  (mpi_insim.cpp:57-128)
+//   precond_vmult()     InsIM::BlockSchurPreconditioner::vmult                  (mpi_insim.cpp:57-128): solve_mp(), solve_sm(), ainv_apply()
 //   ins_solve()         InsIM::solve                                            (mpi_insim.cpp:365-395)
-//   ins_newton_step()   Newton loop of InsIM::run_one_step                      (mpi_insim.cpp:416-473)
-// A~^-1 (MUMPS in the reference) is an inner right-preconditioned GMRES(m) on the BSR A_uu with node-block
-// Jacobi; the outer solver is *flexible* GMRES precisely so that such an inexact inner solve is admissible.
+// A~^-1 (MUMPS in the reference, ainv_apply() here) is an inner right-preconditioned GMRES(m): on the BSR A_uu with node-block Jacobi, or
+// (IFEM_AINV_MG, the type MgUu) on the matrix-free A_uu with a multigrid V-cycle; the outer solver is *flexible* GMRES precisely so that
+// such an inexact inner solve is admissible.  The three GMRES drivers share their host arithmetic (Arnoldi).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -20,11 +20,54 @@
 namespace ifem {
 
 using OpFn = std::function<void(const double *, double *)>;
-using DotFn = std::function<void(int, const double *, const double *, double *)>; // out[i] = <V_i, w>, all-reduced
+using MdotFn = std::function<void(int, const double *, int64_t, const double *, double *)>; // out[i] = <V_i, w>, i < k, columns ld apart
+// ... over the n owned entries, summed over the ranks
+static MdotFn mdot_over(ifem_ctx *c, int64_t n) {
+  return [c, n](int k, const double *V, int64_t ld, const double *w, double *out) { v_mdot(c, n, k, V, ld, w, out, /*all_ranks=*/true); };
+}
 
 struct Clock {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Host arithmetic of one restart cycle, shared by the three GMRES drivers below: the Hessenberg matrix H (row-major, (m+1) x m), the Givens
+// rotations (cs, sn) that keep it triangular, the rotated right-hand side g and the solution y of the small triangular system.
+struct Arnoldi {
+  const int m;
+  std::vector<double> H, cs, sn, g, y;
+  explicit Arnoldi(int m_) : m(m_), H((size_t)(m_ + 1) * m_, 0.0), cs(m_), sn(m_), g(m_ + 1), y(m_) {}
+  void start(double beta) { std::fill(g.begin(), g.end(), 0.0); g[0] = beta; }
+  // column j = (h[0..j], hn): stored, rotated by the earlier rotations, annihilated by a new one; returns the residual estimate |g[j+1]|
+  double column(int j, const double *h, double hn) {
+    for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i];
+    H[(size_t)(j + 1) * m + j] = hn;
+    for (int i = 0; i < j; ++i) {
+      const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
+      H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
+      H[(size_t)i * m + j] = t;
+    }
+    const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
+    cs[j] = a / r; sn[j] = c / r;
+    H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
+    g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
+    return std::fabs(g[j + 1]);
+  }
+  // y[0..j) = H(0..j, 0..j)^-1 g[0..j): back substitution
+  void solve(int j) {
+    for (int i = j - 1; i >= 0; --i) {
+      double t = g[i];
+      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
+      y[i] = t / H[(size_t)i * m + i];
+    }
+  }
+};
+
+// LEFT preconditioning of gmres() (not flexible): the Krylov space of P^-1 A, the stopping test reads the PRECONDITIONED residual --
+// deal.II's SolverGMRES with its defaults (mpi_supg_solver.cpp:176-182)
+struct LeftPrecond {
+  double *stage = nullptr;  // every new basis vector is also written here and the operators read IT, so that
+  const OpFn *PA = nullptr; // ... the fused w = P^-1 A stage (a sequence with constant kernel arguments: a hipGraph) can replace the pair
 };
 
 // (flexible) right-preconditioned restarted GMRES, x0 = 0.  V: (m+1) x n, Z: m x n (flexible) or 1 x n.
@@ -33,15 +76,16 @@ struct Clock {
 static int gmres(ifem_ctx *ctx, int64_t n, int64_t ld, bool reorth, const OpFn &A, const OpFn &Pinv, bool flexible,
                  const double *b, double *x, int m, int maxit, double tol, double *V, double *Z, double *w,
                  double *res_out,
-                 const std::function<void(int, const double *, int64_t, const double *, double *)> &mdot,
+                 const MdotFn &mdot,
                  std::vector<double> *history = nullptr, // residual norm after every iteration (verbose runs)
                  const std::function<void(int, double *&, double *&)> *ensure = nullptr, // bases that grow with the iteration count: called
                                                                                         // with the V columns the next iteration needs
-                 bool left = false, // LEFT preconditioning (not flexible): the Krylov space of P^-1 A, the stopping test reads the
-                                      // PRECONDITIONED residual -- deal.II's SolverGMRES with its defaults (mpi_supg_solver.cpp:176-182)
-                 double *stage = nullptr,    // left only: every new basis vector is also written here and the operators read IT, so that
-                 const OpFn *PA = nullptr) { // ... the fused w = P^-1 A stage (a sequence with constant kernel arguments: a hipGraph) can replace the pair
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), h(m + 1), h2(m + 1);
+                 const LeftPrecond *left_pc = nullptr) {
+  const bool left = left_pc != nullptr;
+  double *stage = left ? left_pc->stage : nullptr;
+  const OpFn *PA = left ? left_pc->PA : nullptr;
+  Arnoldi K(m);
+  std::vector<double> h(m + 1), h2(m + 1);
   v_zero(ctx, n, x);
   int it = 0;
   double res = 0;
@@ -58,8 +102,7 @@ static int gmres(ifem_ctx *ctx, int64_t n, int64_t ld, bool reorth, const OpFn &
     if (res <= tol || it >= maxit || !std::isfinite(res)) break; // (deal.II's SolverControl::check fails on a NaN as well)
     if (left && stage) v_scale_to2(ctx, n, 1.0 / beta, r0, V, stage);
     else v_scale_to(ctx, n, 1.0 / beta, r0, V);
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
+    K.start(beta);
     int j = 0;
     bool done = false;
     for (; j < m && it < maxit; ++j) {
@@ -81,39 +124,25 @@ static int gmres(ifem_ctx *ctx, int64_t n, int64_t ld, bool reorth, const OpFn &
         v_maxpy(ctx, n, j + 1, V, ld, h.data(), w, &ww, true);
         std::fill(h2.begin(), h2.end(), 0.0);
       }
-      for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i] + h2[i];
+      for (int i = 0; i <= j; ++i) h[i] += h2[i]; // column j of H: the coefficients of both passes
       const double hn = std::sqrt(ww);
-      H[(size_t)(j + 1) * m + j] = hn;
       if (hn > 0) {
         if (left && stage) v_scale_to2(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld, stage);
         else v_scale_to(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
       }
-      for (int i = 0; i < j; ++i) {
-        const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = t;
-      }
-      const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
-      cs[j] = a / r; sn[j] = c / r;
-      H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
-      g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
-      res = std::fabs(g[j + 1]);
+      res = K.column(j, h.data(), hn);
       ++it;
       if (history) history->push_back(res);
       if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
     }
-    for (int i = j - 1; i >= 0; --i) {
-      double t = g[i];
-      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
-      y[i] = t / H[(size_t)i * m + i];
-    }
+    K.solve(j);
     if (flexible || left) {
-      for (int i = 0; i < j; ++i) h[i] = -y[i];
+      for (int i = 0; i < j; ++i) h[i] = -K.y[i];
       v_maxpy(ctx, n, j, left ? V : Z, ld, h.data(), x); // x += sum y_i z_i   (left preconditioning: x += V y)
     } else {
       // x += P^-1 (V y): one preconditioner application instead of storing every z_j
       v_zero(ctx, n, w);
-      for (int i = 0; i < j; ++i) h[i] = -y[i];
+      for (int i = 0; i < j; ++i) h[i] = -K.y[i];
       v_maxpy(ctx, n, j, V, ld, h.data(), w);
       Pinv(w, Z);
       v_axpy(ctx, n, 1.0, Z, x);
@@ -159,7 +188,8 @@ using OpF32 = std::function<void(const float *, double *)>;
 static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32 &Pinv, const double *b, double *x,
                           int m, int maxit, double tol, float *V, double *z, double *w, double *res_out,
                           const std::function<void(double *, int)> &allreduce) {
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), h(m + 4);
+  Arnoldi K(m);
+  std::vector<double> h(m + 4);
   v_zero(ctx, n, x);
   int it = 0;
   double res = 0;
@@ -173,8 +203,7 @@ static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, c
     res = beta;
     if (res <= tol || it >= maxit || !std::isfinite(res)) break;
     v_scale_store_f32(ctx, n, 1.0 / beta, w, V);
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
+    K.start(beta);
     int j = 0;
     bool done = false;
     for (; j < m && it < maxit; ++j) {
@@ -185,31 +214,16 @@ static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, c
       double ww;
       v_maxpy_f32(ctx, n, j + 1, V, ld, h.data(), w, &ww);
       allreduce(&ww, 1);
-      for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i];
       const double hn = std::sqrt(ww);
-      H[(size_t)(j + 1) * m + j] = hn;
       if (hn > 0) v_scale_store_f32(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
-      for (int i = 0; i < j; ++i) {
-        const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = t;
-      }
-      const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
-      cs[j] = a / r; sn[j] = c / r;
-      H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
-      g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
-      res = std::fabs(g[j + 1]);
+      res = K.column(j, h.data(), hn);
       ++it;
       if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
     }
-    for (int i = j - 1; i >= 0; --i) {
-      double t = g[i];
-      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
-      y[i] = t / H[(size_t)i * m + i];
-    }
+    K.solve(j);
     // x += P^-1 (V y): round V y to the basis precision (column m+1 of the basis is free at this point)
     v_zero(ctx, n, w);
-    for (int i = 0; i < j; ++i) h[i] = -y[i];
+    for (int i = 0; i < j; ++i) h[i] = -K.y[i];
     v_maxpy_f32(ctx, n, j, V, ld, h.data(), w, nullptr);
     float *vy = V + (int64_t)(m + 1) * ld;
     v_scale_store_f32(ctx, n, 1.0, w, vy);
@@ -226,12 +240,12 @@ static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, c
 // cell arithmetic) reads that Z column and writes the fp64 w.  w, b, x, the Hessenberg arithmetic, the stopping test and the restart residual
 // b - A x are fp64; Gram-Schmidt is the single fused pass of gmres(reorth = false).  Same iteration as gmres(flexible = true) up to the rounding
 // of the stored columns.  The fused kernels take at most 64 columns per call: longer bases (the self-lengthening restart) go in chunks.
-using OpF32In = std::function<void(const float *, double *)>;
 using OpF32F32 = std::function<void(const float *, float *)>;
-static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32In &Af, const OpF32F32 &Pinv, const double *b, double *x,
+static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32 &Af, const OpF32F32 &Pinv, const double *b, double *x,
                       int m, int maxit, double tol, float *V, float *Z, double *w, double *res_out,
                       const std::function<void(double *, int)> &allreduce, const std::function<void(int, float *&, float *&)> &ensure) {
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), h(m + 4);
+  Arnoldi K(m);
+  std::vector<double> h(m + 4);
   constexpr int kChunk = 64;
   auto mdot = [&](int k, const float *B, double *out) {
     for (int k0 = 0; k0 < k; k0 += kChunk) v_mdot_f32(ctx, n, std::min(kChunk, k - k0), B + int64_t(k0) * ld, ld, w, out + k0);
@@ -258,8 +272,7 @@ static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const
     res = beta;
     if (res <= tol || it >= maxit || !std::isfinite(res)) break;
     v_scale_store_f32(ctx, n, 1.0 / beta, r0, V);
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
+    K.start(beta);
     int j = 0;
     bool done = false;
     for (; j < m && it < maxit; ++j) {
@@ -270,29 +283,14 @@ static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const
       mdot(j + 1, V, h.data());
       double ww = 0;
       maxpy(j + 1, V, h.data(), w, &ww);
-      for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i];
       const double hn = std::sqrt(ww);
-      H[(size_t)(j + 1) * m + j] = hn;
       if (hn > 0) v_scale_store_f32(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
-      for (int i = 0; i < j; ++i) {
-        const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = t;
-      }
-      const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
-      cs[j] = a / r; sn[j] = c / r;
-      H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
-      g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
-      res = std::fabs(g[j + 1]);
+      res = K.column(j, h.data(), hn);
       ++it;
       if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
     }
-    for (int i = j - 1; i >= 0; --i) {
-      double t = g[i];
-      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
-      y[i] = t / H[(size_t)i * m + i];
-    }
-    for (int i = 0; i < j; ++i) h[i] = -y[i];
+    K.solve(j);
+    for (int i = 0; i < j; ++i) h[i] = -K.y[i];
     maxpy(j, Z, h.data(), x, nullptr); // x += sum y_i z_i
     if (done || it >= maxit) break;
   }
@@ -369,7 +367,7 @@ static int cg_device(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag
 // r and z must be adjacent (z = r + ld) so that <r,r> and <z,r> come out of one fused reduction.
 static int pcg_jacobi(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag, const double *b, double *x, double tol,
                       int maxit, double *r, int64_t ld, double *p, double *q,
-                      const std::function<void(int, const double *, int64_t, const double *, double *)> &mdot) {
+                      const MdotFn &mdot) {
   double *z = r + ld;
   v_zero(ctx, n, x);
   v_copy(ctx, n, b, r);
@@ -615,6 +613,37 @@ static bool profiler_attached() {
 static inline void key_ptr(std::vector<uint64_t> &key, const void *p) { key.push_back(uint64_t(reinterpret_cast<uintptr_t>(p))); }
 static inline void key_f64(std::vector<uint64_t> &key, double v) { uint64_t b; std::memcpy(&b, &v, 8); key.push_back(b); }
 
+// May the cycle over `levels` (level 0 = c) be replayed as a hipGraph (ctx.hpp::VcGraph)?  Small single-rank chains outside of any profiling;
+// what else a level must satisfy is its caller's (S_m: the explicit matrix; A_uu: no per-level profiling)
+static bool cycle_graph_ok(ifem_ctx *c, const std::vector<SolveState> &levels) {
+  bool ok = c->tune.vcycle_graph_cells > 0 && c->n_cells <= c->tune.vcycle_graph_cells && !c->profile && !kprof_root(c).on && !profiler_attached();
+  for (const SolveState &L : levels) ok = ok && L.ctx->halo.nranks == 1 && !L.ctx->mg_replica;
+  return ok;
+}
+// the smoother's B of a level of the A_uu V-cycle: 0 inverse node blocks, 1 the vertex-patch sum of patch.hip (chosen by mg_uu_setup)
+static int smoother_kind(const ifem_ctx *c) { return patch_active(c) ? 1 : 0; }
+// per-level part of the replay keys: every pointer, count, bound and parameter the level's launches of the cycle are made of
+static void sm_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
+  for (auto &v : lc->mg_vec) key_ptr(key, v.p);
+  key_ptr(key, lc->sm_dinv.p); key_ptr(key, lc->Sm.val.p); key_ptr(key, lc->Sm_f32.p); key_ptr(key, lc->Sm.rowptr.p);
+  key_ptr(key, lc->mg_Rp.col.p); key_ptr(key, lc->mg_Pp.col.p);
+  key.push_back(uint64_t(lc->nPo)); key.push_back(uint64_t(lc->sm_version)); key.push_back(uint64_t(lc->tune.sm_lanes)); key.push_back(uint64_t(lc->Sm_f32.valid));
+  key_f64(key, lc->sm_lmax);
+}
+static void uu_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
+  (void)bjac_f32_ptr(lc); // lazy state (the single-precision copy of the inverse node blocks) stays outside the graph
+  for (auto &v : lc->mguf_vec) key_ptr(key, v.p);
+  key_ptr(key, lc->bjac_f32.p); key_ptr(key, lc->mf_eval.p); key_ptr(key, lc->mf_ycell.p); key_ptr(key, lc->mg_Ru_mask.p); key_ptr(key, lc->mg_Pu_mask.p);
+  key_ptr(key, lc->has_c[lc->asm_constraint_set] ? lc->is_c[lc->asm_constraint_set].p : nullptr);
+  key.push_back(uint64_t(lc->nUo)); key.push_back(uint64_t(lc->n_cells)); key.push_back(uint64_t(lc->mf_noconv)); key.push_back(uint64_t(lc->tune.xcd_swizzle));
+  // everything else the captured launches are made of: the epoch moves with ifem_set_tuning / ifem_set_profiling / ifem_mg_attach
+  key.push_back(lc->graph_epoch); key.push_back(uint64_t(lc->tune.mf_f32));
+  key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) key_f64(key, hd); // which cell kernels, and their constants
+  key_ptr(key, lc->bjac.p); key_ptr(key, lc->vcoords.p); key_ptr(key, lc->cell_unodes.p); key_ptr(key, lc->uinc.col.p);
+  key.push_back(uint64_t(smoother_kind(lc))); key_ptr(key, lc->patch.tab.p); key_ptr(key, lc->patch.inv.p); key_ptr(key, lc->patch.work.p); // the level's smoother and its tables
+  key_f64(key, lc->uu_lmax()); key_f64(key, lc->mf_params.viscosity); key_f64(key, lc->mf_params.rho); key_f64(key, lc->mf_params.grad_div); key_f64(key, lc->mf_params.dt);
+}
+
 // A replicated coarse level (a single-rank context of the whole coarse mesh below a partitioned level) is computed by every rank
 // on its own device: its operators carry float / double atomics whose order differs between devices, so the replicas agree to
 // rounding only, and replica-local decisions (the 1 % early exit of a power iteration) may differ.  Quantities that steer the
@@ -758,20 +787,13 @@ static int pcg_mg_sm(MgSm &M, const double *b, double *x, double tol, int maxit,
   };
   double *zin = c->mg_vec[0].p, *z = c->mg_vec[1].p;
   // the cycle: eagerly, or replayed as a hipGraph on small single-rank chains (as the A_uu V-cycle, precond_vmult)
-  bool graph_ok = c->tune.vcycle_graph_cells > 0 && c->n_cells <= c->tune.vcycle_graph_cells && !c->profile && !kprof_root(c).on && !profiler_attached();
-  for (const SolveState &L : M.L) graph_ok = graph_ok && L.ctx->halo.nranks == 1 && !L.ctx->mg_replica && sm_is_explicit(L);
+  bool graph_ok = cycle_graph_ok(c, M.L);
+  for (const SolveState &L : M.L) graph_ok = graph_ok && sm_is_explicit(L);
   auto sm_cycle = [&]() {
     if (!graph_ok) { mg_sm_vcycle(M, 0); return; }
     std::vector<uint64_t> key;
     key.push_back(M.L.size()); key.push_back(uint64_t(M.nu)); key_f64(key, M.ratio); key.push_back(uint64_t(M.lowp));
-    for (const SolveState &L : M.L) {
-      ifem_ctx *lc = L.ctx;
-      for (auto &v : lc->mg_vec) key_ptr(key, v.p);
-      key_ptr(key, lc->sm_dinv.p); key_ptr(key, lc->Sm.val.p); key_ptr(key, lc->Sm_f32.p); key_ptr(key, lc->Sm.rowptr.p);
-      key_ptr(key, lc->mg_Rp.col.p); key_ptr(key, lc->mg_Pp.col.p);
-      key.push_back(uint64_t(lc->nPo)); key.push_back(uint64_t(lc->sm_version)); key.push_back(uint64_t(lc->tune.sm_lanes)); key.push_back(uint64_t(lc->Sm_f32.valid));
-      key_f64(key, lc->sm_lmax);
-    }
+    for (const SolveState &L : M.L) sm_level_key(L.ctx, key);
     if (!graph_run(c, c->sm_graph, key, [&]() { mg_sm_vcycle(M, 0); })) { c->tune.vcycle_graph_cells = 0; graph_ok = false; }
   };
   if (sv && c->tune.cg_single_reduction) {
@@ -833,10 +855,28 @@ static void carve_workspace(SolveState &S, bool krylov = true);
 // residual, 1 solution, 2 direction, 3 (unused: the operator product is consumed inside the fused gather), 4 prolongated
 // correction; compact owned entries first, so the buffers double as ghost-extended velocity vectors.  The double vectors
 // ctx->mgu_vec[1..3] remain as scratch of the eigenvalue estimates.
+// One application of A~^-1 is one MgUu: the level chain below the context being solved, the cycle on it (eager or replayed as a hipGraph),
+// and the inner solve around the cycle with its retry and fallback ladder.
 struct MgUu {
-  std::vector<SolveState> L;
+  SolveState &S;             // the context being solved (statistics and workspace of the application)
+  ifem_ctx *const c;
+  const ifem_solver_opts *const o;
+  std::vector<SolveState> L; // level 0 = a copy of S, then the attached coarser levels with velocity transfers
   int nu = 3, nu_post = 3;
   double ratio = 8.0;
+  bool trim = false;     // ifem_tuning::inner_f32: single-precision bases around the cycle, and the cycle without the passes nothing reads
+  bool graph_ok = false; // the cycle may be replayed as a hipGraph (decided by solve(), withdrawn when the runtime refuses a capture)
+  double res = 0;        // residual estimate of the last Krylov attempt
+  OpFn Amf;              // the matrix-free A_uu of level 0 on a compact owned vector
+  MdotFn mdot;           // all-reduced multi-dot over the owned velocity entries
+
+  explicit MgUu(SolveState &S);
+  void cycle();                               // mguf_vec[1] = V(mguf_vec[0]) of level 0
+  void apply(const double *x, double *y);     // y = V x on whatever vectors: they only appear in the entry and exit kernels around cycle()
+  void apply(const float *x, float *y);       // column j of V -> column j of Z (trim only)
+  bool solve_once(const double *b, double *x, double tol);
+  void lengthen_restart(int its, int mi);
+  void solve(const double *b, double *x, double tol);
 };
 
 // matrix-free A_uu of one level on a compact owned vector.  Several ranks: the cells whose nodes are all owned are
@@ -892,6 +932,32 @@ void uu_apply_f32col(ifem_ctx *c, const float *z, double *y) {
   apply_uu_mf_f32in(c, ext.p, y);
 }
 
+// ---- the smoother's B of a level, as the cycle sees it (the kind itself: smoother_kind above).
+// d = a d + b B r.  The node blocks are only asked for a == 0: their other directions ride in the fused gather of the product
+static void smoother_dir(ifem_ctx *c, double a, double b, const float *r, float *d) {
+  if (smoother_kind(c) == 1) patch_apply(c, a, b, r, d);
+  else cheb_init_block_f32(c, b, r, d);
+}
+// the fused epilogue (MfFuseT::mode) the level's B supports for a wanted one.  The node blocks ride in the gather of the product: the mode stays.
+// The patch sum cannot: modes 2 and 3 become mode 1 (x and r only), and the return value says that the direction pass smoother_dir must follow
+static bool smoother_fuse_mode(const ifem_ctx *c, int &mode) {
+  if (smoother_kind(c) == 0 || mode == 1) return false;
+  mode = 1;
+  return true;
+}
+// entry of the trimmed cycle: r = float(src) and the first direction d = c0 B r (node blocks: one pass, mg.hip::k_vc_entry)
+static void smoother_entry(ifem_ctx *c, double c0, const double *src, float *r, float *d) {
+  if (smoother_kind(c) == 0) { vc_entry(c, c0, src, r, d); return; }
+  v_cvt_d2f(c, int64_t(c->dim) * c->nUo, src, r);
+  smoother_dir(c, 0.0, c0, r, d);
+}
+static void smoother_entry(ifem_ctx *c, double c0, const float *src, float *r, float *d) {
+  if (smoother_kind(c) == 0) { vc_entry_f32(c, c0, src, r, d); return; }
+  const int64_t nuo = int64_t(c->dim) * c->nUo;
+  if (nuo) IFEM_HIP_CHECK(hipMemcpyAsync(r, src, size_t(nuo) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  smoother_dir(c, 0.0, c0, r, d);
+}
+
 static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
   ifem_ctx *f0 = M.L[0].ctx;
   // size of the evaluation point the bounds below were estimated at: A_uu carries rho C(u), so a bound taken at a small
@@ -940,30 +1006,28 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
     }
     // the smoother's B of this level: the inverse node blocks, or (ifem_tuning::uu_smoother = 1 on an eligible level) the vertex-patch
     // sum of patch.hip, whose tables are made here, outside of any captured cycle.  The bound below is one of B A_uu: each kind keeps its own
+    // (ctx.hpp::UuBound)
     const int kind = (c->tune.uu_smoother == 1 && patch_setup(c)) ? 1 : 0;
-    if (kind != c->uu_bound_kind) {
-      auto &o = c->uu_bound_other;
-      std::swap(c->uu_lmax, o.lmax); std::swap(c->uu_lmax_evn, o.evn); c->uu_eig.swap(o.eig);
-      for (int i = 0; i < 6; ++i) std::swap(c->uu_lmax_key[i], o.key[i]);
-      c->uu_bound_kind = kind;
-    }
+    c->uu_bound_kind = kind;
+    ifem_ctx::UuBound &B = c->uu_bound[kind];
     // eigenvalue bound of (block D)^-1 A_uu: depends on the parameters and the constrained-dof set, hardly on the evaluation
     // point (the viscous and mass terms carry the top of the spectrum): estimated once per such state
     const double key[6] = {f0->mf_params.viscosity, f0->mf_params.rho, f0->mf_params.grad_div, f0->mf_params.dt,
                            double(f0->mf_noconv), double(c->flag_id[c->asm_constraint_set])};
-    bool same = c->uu_lmax > 0 && !force_bounds;
-    for (int i = 0; i < 6; ++i) same = same && key[i] == c->uu_lmax_key[i];
-    same = same && std::fabs(f0->uu_evn - c->uu_lmax_evn) <= 0.1 * std::max(c->uu_lmax_evn, 1e-300);
-    if (c->tune.geo_cache == 2 && c->uu_lmax_asm != f0->asm_version) same = false; // measurement mode: a new set per assembly
-    c->uu_lmax_asm = f0->asm_version;
+    bool same = B.lmax > 0 && !force_bounds;
+    for (int i = 0; i < 6; ++i) same = same && key[i] == B.key[i];
+    same = same && std::fabs(f0->uu_evn - B.evn) <= 0.1 * std::max(B.evn, 1e-300);
+    // measurement mode: a new set per assembly.  The stamp is the entry's own: a kind that sat out an assembly has a bound of the set before
+    if (c->tune.geo_cache == 2 && B.asm_stamp != f0->asm_version) same = false;
+    B.asm_stamp = f0->asm_version;
     if (same) continue;
-    if (force_bounds) c->uu_lmax = 0; // cold estimate: all 12 steps from a rough vector
+    if (force_bounds) B.lmax = 0; // cold estimate: all 12 steps from a rough vector
     // power iteration on B A_uu.  A level that has an estimate from another constrained-dof set starts from that run's last
     // iterate and stops once the estimate moves by less than 1 % (the top of this spectrum belongs to the mesh, not to the
     // set); the first estimate starts from a fixed rough vector and runs all 12 steps.
     double *x = c->mgu_vec[1].p, *y = c->mgu_vec[3].p, *z = c->mgu_vec[2].p;
-    const bool warm = c->uu_lmax > 0 && (int64_t)c->uu_eig.n == S.nuo && S.nuo > 0;
-    if (warm) v_copy(c, S.nuo, c->uu_eig.p, x);
+    const bool warm = B.lmax > 0 && (int64_t)B.eig.n == S.nuo && S.nuo > 0;
+    if (warm) v_copy(c, S.nuo, B.eig.p, x);
     else vec_rough(c, S.nuo, int64_t(c->halo.rank) * 7000003, x);
     double lam = 0;
     const int n_pow = c->tune.eig_steps > 0 ? c->tune.eig_steps : 12;
@@ -975,7 +1039,7 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
       uu_apply_level(S, x, y);
       if (kind == 1) { // the patch B acts on the single-precision level vectors (3 and 4 are idle outside of a cycle)
         v_cvt_d2f(c, S.nuo, y, c->mguf_vec[3].p);
-        patch_apply(c, 0.0, 1.0, c->mguf_vec[3].p, c->mguf_vec[4].p);
+        smoother_dir(c, 0.0, 1.0, c->mguf_vec[3].p, c->mguf_vec[4].p);
         v_cvt_f2d(c, S.nuo, c->mguf_vec[4].p, z);
       } else
       bjac_apply(c, y, z);
@@ -987,74 +1051,74 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
       if (warm && it >= 1 && std::fabs(lam - prev) <= 0.01 * lam) break;
     }
     if (S.nuo > 0) {
-      if ((int64_t)c->uu_eig.n != S.nuo) c->uu_eig.alloc((size_t)S.nuo);
-      v_copy(c, S.nuo, x, c->uu_eig.p);
+      if ((int64_t)B.eig.n != S.nuo) B.eig.alloc((size_t)S.nuo);
+      v_copy(c, S.nuo, x, B.eig.p);
     }
     if (ifem_ctx *w = replica_world(c)) allreduce_max(w, &lam, 1);
-    c->uu_lmax = lam > 0 && std::isfinite(lam) ? lam : 1.0;
-    if (S.o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle level %zu (%lld cells): lambda_max estimate %.4f (%s)\n", l, (long long)c->n_cells, c->uu_lmax, warm ? "warm" : "cold");
-    c->uu_lmax_evn = f0->uu_evn;
-    for (int i = 0; i < 6; ++i) c->uu_lmax_key[i] = key[i];
+    B.lmax = lam > 0 && std::isfinite(lam) ? lam : 1.0;
+    if (S.o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle level %zu (%lld cells): lambda_max estimate %.4f (%s)\n", l, (long long)c->n_cells, c->uu_lmax(), warm ? "warm" : "cold");
+    B.evn = f0->uu_evn;
+    for (int i = 0; i < 6; ++i) B.key[i] = key[i];
   }
 }
 
-// d_ready: the first direction d = (1/theta) B r is already in place (written by the fused residual update, MfFuse mode 3, or by the
-// entry kernel of the cycle)
+// One Chebyshev sweep of mg_uu_smooth.  keep_r: the residual is kept up to date on exit (one operator product per step), without it the
+// last product is skipped.  d_ready: the first direction d = (1/theta) B r is already in place (written by the fused residual update, MfFuse
+// mode 3, or by the entry of the cycle).
 // trim (ifem_tuning::inner_f32): the passes nothing reads are left out -- x_fresh: x holds nothing yet, the first fused step stores xs = x
 // instead of adding to a zeroed vector; the last step of a keep_r sweep updates x and r only (mode 1: its new direction would be
 // overwritten by the residual update after the coarse correction); no_exit: the closing x += d is the caller's (it delivers x + d elsewhere)
-static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, float *x, float *r, bool keep_r, bool d_ready = false,
-                         bool trim = false, bool x_fresh = false, bool no_exit = false) {
+struct SmoothOpts {
+  bool keep_r = false, d_ready = false, trim = false, x_fresh = false, no_exit = false;
+};
+static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, float *x, float *r, const SmoothOpts &o) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *d = c->mguf_vec[2].p;
   const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
   double rho_old = 1.0 / sigma;
-  const bool patch = patch_active(c); // B = the vertex-patch sum: the fused product updates x and r (mode 1), the patch kernel the direction
-  if (!d_ready) { if (patch) patch_apply(c, 0.0, 1.0 / theta, r, d); else cheb_init_block_f32(c, 1.0 / theta, r, d); }
+  if (!o.d_ready) smoother_dir(c, 0.0, 1.0 / theta, r, d);
   for (int k = 0; k < nsteps; ++k) {
     const bool last = k == nsteps - 1;
-    if (last && !keep_r) {
-      if (no_exit) break;
-      if (k == 0 && x_fresh) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream)); // (a one-step sweep from zero)
+    if (last && !o.keep_r) {
+      if (o.no_exit) break;
+      if (k == 0 && o.x_fresh) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream)); // (a one-step sweep from zero)
       v_axpy_f32v(c, S.nuo, 1.0f, d, x);
       break;
     }
     const double rho_new = 1.0 / (2.0 * sigma - rho_old);
-    if (patch) {
-      MfFuseT<float> f;
-      f.mode = 1; f.xs = x; f.r = r; f.d = d; f.first = (k == 0 && x_fresh) ? 1 : 0;
-      uu_apply_level_f32(S, d, &f);
-      // (the direction of the last step of a keep_r sweep is never read: the residual update after the coarse correction writes a new one)
-      if (!last) patch_apply(c, rho_new * rho_old, 2.0 * rho_new / delta, r, d);
-      rho_old = rho_new;
-      continue;
-    }
-    // x += d; r -= A d; d = rho_new rho_old d + (2 rho_new / delta) B r, fused into the node gather of the product
+    // x += d; r -= A d; d = rho_new rho_old d + (2 rho_new / delta) B r: fused into the node gather of the product as far as B allows
     MfFuseT<float> f;
-    f.mode = (trim && last) ? 1 : 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
-    f.first = (k == 0 && x_fresh) ? 1 : 0;
+    f.mode = (o.trim && last) ? 1 : 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
+    f.first = (k == 0 && o.x_fresh) ? 1 : 0;
+    const bool dir_follows = smoother_fuse_mode(c, f.mode);
     uu_apply_level_f32(S, d, &f);
+    // (the direction of the last step of a keep_r sweep is never read: the residual update after the coarse correction writes a new one)
+    if (dir_follows && !last) smoother_dir(c, f.a, f.b, r, d);
     rho_old = rho_new;
   }
 }
 
 // level l: mguf_vec[1] = V(mguf_vec[0]); mguf_vec[0] is overwritten by the residual
-// trim = false: every pass of the cycle as it was written first (ifem_tuning::inner_f32 = 0).  trim = true: level 0 starts from r AND the first
-// direction d (vc_entry) and ends BEFORE its last update x += d (vc_exit delivers x + d); no level zeroes its x (see mg_uu_smooth)
-static void mg_uu_vcycle(MgUu &M, size_t l, bool trim = false) {
+// M.trim = false: every pass of the cycle as it was written first (ifem_tuning::inner_f32 = 0).  M.trim = true: level 0 starts from r AND the
+// first direction d (smoother_entry) and ends BEFORE its last update x += d (vc_exit delivers x + d); no level zeroes its x (see SmoothOpts)
+static void mg_uu_vcycle(MgUu &M, size_t l) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *r = c->mguf_vec[0].p, *x = c->mguf_vec[1].p;
-  const double hi = 1.1 * c->uu_lmax;
-  const bool top = trim && l == 0;
+  const double hi = 1.1 * c->uu_lmax();
+  const bool trim = M.trim, top = trim && l == 0;
   if (!trim) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream));
   if (l + 1 == M.L.size()) {
-    mg_uu_smooth(M, l, 24, hi / 400.0, hi, x, r, false, top, trim, trim, top);
+    SmoothOpts coarsest;
+    coarsest.d_ready = top; coarsest.trim = trim; coarsest.x_fresh = trim; coarsest.no_exit = top;
+    mg_uu_smooth(M, l, 24, hi / 400.0, hi, x, r, coarsest);
     return;
   }
   const double lo = hi / M.ratio;
-  mg_uu_smooth(M, l, M.nu, lo, hi, x, r, true, top, trim, trim);
+  SmoothOpts pre;
+  pre.keep_r = true; pre.d_ready = top; pre.trim = trim; pre.x_fresh = trim;
+  mg_uu_smooth(M, l, M.nu, lo, hi, x, r, pre);
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
   mg_csr_apply_nodes_f32(c, c->mg_Ru, r, c->mg_Ru_mask, cc->mguf_vec[0].p);
@@ -1062,35 +1126,323 @@ static void mg_uu_vcycle(MgUu &M, size_t l, bool trim = false) {
   // sum over the ranks; from there down nothing is exchanged and the prolongation reads the replica directly
   if (c->mg_replica) allreduce_sum_vec_f32(c, cc->mguf_vec[0].p, int64_t(cc->dim) * cc->nUo, cc->mguf_vec[4].p);
   else halo_reverse_add_f32(cc, cc->mguf_vec[0].p);
-  mg_uu_vcycle(M, l + 1, trim);
+  mg_uu_vcycle(M, l + 1);
   halo_exchange_f32(cc, cc->mguf_vec[1].p);
   float *e = c->mguf_vec[4].p;
   mg_csr_apply_nodes_f32(c, c->mg_Pu, cc->mguf_vec[1].p, c->mg_Pu_mask, e);
   MfFuseT<float> f; // x += e; r -= A e; d = (1/theta) B r: the first direction of the post-smoothing sweep
   f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = 1.0 / (0.5 * (hi + lo));
-  if (patch_active(c)) f.mode = 1; // x += e; r -= A e here, the first direction from the patch kernel
+  const bool dir_follows = smoother_fuse_mode(c, f.mode);
   uu_apply_level_f32(S, e, &f);
-  if (patch_active(c)) patch_apply(c, 0.0, f.b, r, f.d);
-  mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, false, true, trim, false, top);
+  if (dir_follows) smoother_dir(c, 0.0, f.b, r, f.d);
+  SmoothOpts post;
+  post.d_ready = true; post.trim = trim; post.no_exit = top;
+  mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, post);
 }
 // the first direction of level 0 is (1 / theta) B r with the theta of the sweep the cycle starts with
 static double mg_uu_entry_c0(const MgUu &M) {
-  const double hi = 1.1 * M.L[0].ctx->uu_lmax;
+  const double hi = 1.1 * M.L[0].ctx->uu_lmax();
   const double lo = M.L.size() == 1 ? hi / 400.0 : hi / M.ratio;
   return 1.0 / (0.5 * (hi + lo));
+}
+
+// the level chain of this application: every attached coarser level that has velocity transfers from the one above
+MgUu::MgUu(SolveState &S_) : S(S_), c(S_.ctx), o(S_.o) {
+  nu = std::max(1, o->mg_smooth_u); nu_post = o->mg_smooth_u_post > 0 ? o->mg_smooth_u_post : nu; ratio = std::max(1.5, o->mg_cheb_ratio_u);
+  L.push_back(S);
+  for (ifem_ctx *p = c; p->mg_coarse && p->mg_Pu.n_rows == p->nUo && p->nUo > 0; p = p->mg_coarse) {
+    SolveState Sc{p->mg_coarse, S.P, o};
+    carve_workspace(Sc, false);
+    L.push_back(Sc);
+  }
+  if (!c->mf_valid) throw Error(IFEM_E_BADPARAM, "IFEM_AINV_MG needs the operator state of ifem_ins_assemble / ifem_imex_assemble");
+  trim = c->tune.inner_f32 != 0;
+  Amf = [this](const double *x, double *y) { uu_apply_level(S, x, y); };
+  mdot = mdot_over(c, S.nuo);
+}
+
+// the cycle itself: eagerly, or as a captured hipGraph (ctx.hpp::VcGraph) on small single-rank chains
+void MgUu::cycle() {
+  if (!graph_ok) { mg_uu_vcycle(*this, 0); return; }
+  std::vector<uint64_t> key;
+  key.push_back(L.size()); key.push_back(uint64_t(nu)); key.push_back(uint64_t(nu_post)); key_f64(key, ratio);
+  key.push_back(uint64_t(trim)); // which passes the captured cycle consists of
+  for (const SolveState &l : L) uu_level_key(l.ctx, key);
+  if (!graph_run(c, c->vc_graph, key, [&]() { mg_uu_vcycle(*this, 0); })) {
+    c->tune.vcycle_graph_cells = 0;
+    graph_ok = false;
+    if (o->verbose) fprintf(stderr, "[ifem] hipGraph capture of the A_uu V-cycle failed: eager launches from now on\n");
+  }
+}
+
+// the cycle between its entry and exit runs on the fixed level vectors (and is what a hipGraph captures): whatever vector it is
+// applied to only appears as an argument of the entry and exit kernels outside of it
+void MgUu::apply(const double *x, double *y) {
+  if (!trim) {
+    v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
+    cycle();
+    v_cvt_f2d(c, S.nuo, c->mguf_vec[1].p, y);
+    return;
+  }
+  smoother_entry(c, mg_uu_entry_c0(*this), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
+  cycle();
+  vc_exit(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
+}
+void MgUu::apply(const float *x, float *y) {
+  smoother_entry(c, mg_uu_entry_c0(*this), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
+  cycle();
+  vc_exit_f32(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
+}
+
+// one attempt of A~^-1 with the V-cycle; returns false when the result is not finite (a Chebyshev bound below the
+// spectral radius turns the smoothers into amplifiers)
+bool MgUu::solve_once(const double *b, double *x, double tol) {
+  const OpFn Vc = [this](const double *u, double *y) { apply(u, y); };
+  if (o->inner_maxit == 0) { // A~^-1 := one V-cycle, no inner Krylov iteration (the outer solver is flexible)
+    apply(b, x);
+    S.st.inner_iters += 1;
+  } else if (o->inner_maxit < 0) { // -k: k stationary V-cycle sweeps x += V(b - A x): no Arnoldi process, k - 1 operator products
+    const int k = -o->inner_maxit;
+    apply(b, x);
+    for (int it = 1; it < k; ++it) {
+      Amf(x, S.inner_w);
+      v_axpby(c, S.nuo, 1.0, b, -1.0, S.inner_w); // r = b - A x
+      apply(S.inner_w, S.inner_z);
+      v_axpy(c, S.nuo, 1.0, S.inner_z, x);
+    }
+    S.st.inner_iters += k;
+  } else { // flexible GMRES: the preconditioned directions are kept, so the update needs no extra V-cycle
+    const int64_t ld = basis_ld(c, S.nuo);
+    // restart length: the caller's, lengthened by the context when an application needed more than two restart cycles (lengthen_restart)
+    const int mi = std::max(std::max(1, o->inner_restart), c->inner_restart_eff);
+    int its;
+    // one pair of bases per context: a change of ifem_tuning::inner_f32 gives the other pair back (a no-op when it is empty).  The fp64
+    // basis the node-block-Jacobi fallback of solve() grows under inner_f32 = 1 is deliberately temporary: the next application frees it here
+    if (trim) {
+      c->innerV.release(); c->innerZ.release();
+      grow_basis(c, c->innerVf, ld, std::min(mi + 1, kBasisStart), mi + 1);
+      grow_basis(c, c->innerZf, ld, std::min(mi, kBasisStart), mi);
+      const auto grow = basis_grower(c, c->innerVf, c->innerZf, ld, mi + 1);
+      const OpF32 Amf32 = [this](const float *z, double *y) { uu_apply_f32col(c, z, y); }; // the product on a Z column of fgmres_f32
+      const OpF32F32 Vcf = [this](const float *u, float *y) { apply(u, y); };
+      its = fgmres_f32(c, S.nuo, ld, Amf, Amf32, Vcf, b, x, mi, o->inner_maxit, tol, c->innerVf.p, c->innerZf.p,
+                       S.inner_w, &res, [this](double *v, int k) { allreduce_sum(c, v, k); }, grow);
+    } else {
+      c->innerVf.release(); c->innerZf.release();
+      grow_basis(c, c->innerV, ld, std::min(mi + 1, kBasisStart), mi + 1);
+      grow_basis(c, c->innerZ, ld, std::min(mi, kBasisStart), mi);
+      const auto grow = basis_grower(c, c->innerV, c->innerZ, ld, mi + 1);
+      its = gmres(c, S.nuo, ld, /*reorth=*/false, Amf, Vc, true, b, x, mi, o->inner_maxit, tol,
+                  c->innerV.p, c->innerZ.p, S.inner_w, &res, mdot, nullptr, &grow);
+    }
+    S.st.inner_iters += its;
+    lengthen_restart(its, mi);
+  }
+  if (o->inner_maxit > 0) return std::isfinite(res); // the Arnoldi recurrence carries any NaN / Inf of the V-cycle
+  double dn;
+  mdot(1, x, S.nuo, x, &dn);
+  return std::isfinite(dn);
+}
+
+// An application that needed more than two restart cycles of GMRES(mi) lengthens the context's restart -- a V-cycle that has lost its mesh
+// independence (the refined cylinder, DESIGN section 6: 147 inner iterations with GMRES(16), 75 with GMRES(40), 59 with GMRES(100))
+// stagnates across restarts; the bases grow on demand, so the longer cycle costs memory only where it is used.  Capped at 128 columns and
+// at a quarter of the free device memory.
+void MgUu::lengthen_restart(int its, int mi) {
+  if (!(its > 2 * mi && mi < 128)) return;
+  size_t fr = 0, tot = 0;
+  (void)hipMemGetInfo(&fr, &tot);
+  int want = std::min(128, 2 * mi);
+  const double per_col = 2.0 * double(basis_ld(c, S.nuo)) * (trim ? sizeof(float) : sizeof(double));
+  int fits = int(std::min<double>(128.0, 0.25 * double(fr) / std::max(per_col, 1.0)));
+  if (c->test_restart_fits > 0) fits = c->test_restart_fits; // test aid (ifem_test_restart_fits): a rank that is short of memory
+  want = std::min(want, std::max(fits, mi));
+  // `its` and `mi` are the same on every rank, free memory and `ld` are not: the restart length must be (the ranks restart
+  // together -- their all-reduces and halo exchanges pair up), so the smallest wish of all ranks wins
+  if (c->halo.nranks > 1) { double w = -double(want); allreduce_max(c, &w, 1); want = int(-w); }
+  if (want > mi) {
+    if (o->verbose) fprintf(stderr, "[ifem] inner GMRES(%d) needed %d iterations: restart length %d from now on\n", mi, its, want);
+    c->inner_restart_eff = want;
+  }
+}
+
+// x = A~^-1 b: inner GMRES on the matrix-free operator with one V-cycle as its preconditioner, to the absolute tolerance tol
+void MgUu::solve(const double *b, double *x, double tol) {
+  mg_uu_setup(*this);
+  graph_ok = cycle_graph_ok(c, L);
+  for (const SolveState &l : L) graph_ok = graph_ok && !l.ctx->profile;
+  if (solve_once(b, x, tol)) return;
+  // re-estimate every level's bound from scratch and try once more; if that fails too, this application falls back to
+  // the node-block Jacobi preconditioned inner solve (the preconditioner degrades, the outer solver stays correct)
+  if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle returned non-finite values: re-estimating the Chebyshev bounds\n");
+  mg_uu_setup(*this, /*force_bounds=*/true);
+  res = 0;
+  // the fused single-precision kernels read, with zero coefficients, up to 3 columns past the ones in use: none may keep a NaN
+  if (c->innerVf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerVf.p, 0, c->innerVf.n * sizeof(float), c->stream));
+  if (c->innerZf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerZf.p, 0, c->innerZf.n * sizeof(float), c->stream));
+  if (solve_once(b, x, tol)) return;
+  if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle still non-finite: node-block Jacobi for this application\n");
+  const OpFn Pbj = [this](const double *u, double *y) { bjac_apply(c, u, y); };
+  res = 0;
+  const int64_t ldj = basis_ld(c, S.nuo);
+  const int mj = std::max(1, o->inner_restart);
+  const std::function<void(int, double *&, double *&)> growv = [&](int cols, double *&V, double *&) {
+    grow_basis(c, c->innerV, ldj, std::min(cols, mj + 1), mj + 1); // (not flexible: one z vector)
+    V = c->innerV.p;
+  };
+  // gmres() stores its first basis vector before it asks `growv` for columns: the fp64 basis must exist here (with
+  // ifem_tuning::inner_f32 the context has not allocated it before this fallback)
+  grow_basis(c, c->innerV, ldj, std::min(mj + 1, kBasisStart), mj + 1);
+  if (S.nuo > 0 && !c->innerV.p) throw Error(IFEM_E_BADPARAM, "inner GMRES: no basis storage");
+  S.st.inner_iters += gmres(c, S.nuo, ldj, /*reorth=*/false, Amf, Pbj, false, b, x, mj,
+                            std::max(o->inner_maxit, 50), tol, c->innerV.p, S.inner_z, S.inner_w, &res, mdot, nullptr, &growv);
+}
+
+// ---- the statements of InsIM::BlockSchurPreconditioner::vmult (mpi_insim.cpp:57-128), one function each.
+// approx_kind: the approximate-preconditioner kinds, which stream M_p and S_m in single precision
+static bool approx_kind(const ifem_solver_opts *o) {
+  return o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF || o->ainv_kind == IFEM_AINV_MG;
+}
+static int p_maxit(const ifem_ctx *c) { return (int)std::min<int64_t>(std::max<int64_t>(c->n_global_p, 1), 1 << 30); }
+
+// CG for Mp (:69-84): x = M_p^-1 b to max(mp_abs, mp_rel ||b||)
+static void solve_mp(SolveState &S, const double *b, double *x) {
+  ifem_ctx *c = S.ctx;
+  const ifem_solver_opts *o = S.o;
+  // the approximate-preconditioner kinds stream M_p in single precision like S_m (the solve is to 1e-6, the rounding of the
+  // values 6e-8).  (p.q fused into this SpMV was measured: a block reduction in each of its 67 k small blocks costs more
+  // than the separate pass over the two vectors.)
+  const bool approx = approx_kind(o);
+  const OpFn mp = [&](const double *u, double *y) {
+    if (halo_overlap_ok(c)) {
+      build_row_split(c, c->Mp, c->nPo);
+      v_copy(c, S.npo, u, S.xp_ext);
+      halo_start(c, S.xp_ext, 1);
+      spmv_mp(c, S.xp_ext, y, 1, approx);
+      halo_wait(c);
+      spmv_mp(c, S.xp_ext, y, 2, approx);
+      return;
+    }
+    const double *ue; extend_p(S, u, &ue);
+    spmv_mp(c, ue, y, 0, approx);
+  };
+  // ... and put a Jacobi preconditioner on this solve: same stopping rule on the true residual, fewer iterations (the reference uses
+  // PreconditionNone; counts are no parity target)
+  const bool pjac = approx;
+  const double tol = std::max(o->mp_abs, o->mp_rel * S.p_src_norm);
+  // device-resident recurrences on any number of ranks: the dot products are all-reduced on the stream (comm.hip::allreduce_sum_dev)
+  if (pjac) scalar_diag(c, c->Mp, c->Mp.val.p, S.tp[5]);
+  if (o->device_cg != 0)
+    S.st.cg_mp_iters += cg_device(c, S.npo, mp, pjac ? S.tp[5] : nullptr, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], S.tp[4], 4, S.tp[6]);
+  else if (pjac)
+    S.st.cg_mp_iters += pcg_jacobi(c, S.npo, mp, S.tp[5], b, x, tol, p_maxit(c), S.tp[1], c->nPl, S.tp[3], S.tp[4], mdot_over(c, S.npo)); // r = tp[1], z = tp[2]
+  else
+    S.st.cg_mp_iters += cg(c, S.npo, mp, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], [&](const double *u, const double *v) { return dot_all(S, S.npo, u, v); });
+}
+
+// CG for Sm (:86-112): x = S_m^-1 b to max(sm_abs, sm_rel ||b||)
+static void solve_sm(SolveState &S, const double *b, double *x) {
+  ifem_ctx *c = S.ctx;
+  const ifem_solver_opts *o = S.o;
+  const bool lowp = approx_kind(o);
+  const double tol = std::max(o->sm_abs, o->sm_rel * S.p_src_norm);
+  sm_ensure(S);
+  const OpFn sm = [&](const double *u, double *y) { sm_apply(S, u, y, lowp); };
+  // multigrid-preconditioned CG when coarser levels are attached (every level needs its S_m explicitly: Jacobi smoothing)
+  // (the finest level may apply S_m as two SpMVs -- several ranks without the 2-deep pressure halo, e.g. the strips of an unstructured
+  // mesh above replicated coarse levels: the V-cycle needs the operator and its diagonal there, not the matrix)
+  bool use_mg = o->sm_mg && c->mg_coarse && (sm_is_explicit(S) || (o->explicit_schur && c->halo.nranks > 1));
+  MgSm M;
+  if (use_mg) {
+    M.lowp = lowp; M.nu = std::max(1, o->mg_smooth); M.ratio = std::max(1.5, o->mg_cheb_ratio);
+    M.L.push_back(S);
+    for (ifem_ctx *cc = c->mg_coarse; cc; cc = cc->mg_coarse) {
+      SolveState Sc{cc, S.P, o};
+      carve_workspace(Sc, false);
+      if (!sm_is_explicit(Sc)) { use_mg = false; break; }
+      M.L.push_back(Sc);
+    }
+  }
+  if (use_mg) {
+    mg_sm_setup(M, c->asm_constraint_set);
+    S.st.cg_sm_iters += pcg_mg_sm(M, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], S.tp[4]);
+    S.st.sm_mg_levels = (uint32_t)M.L.size();
+  } else if (o->device_cg != 0) // (Jacobi on S_m was measured too: 176 instead of 172 iterations -- its diagonal is nearly constant)
+    S.st.cg_sm_iters += cg_device(c, S.npo, sm, nullptr, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], S.tp[4], 4, S.tp[6]);
+  else
+    S.st.cg_sm_iters += cg(c, S.npo, sm, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], [&](const double *u, const double *v) { return dot_all(S, S.npo, u, v); });
+}
+
+// The relative tolerance of this application's inner solve: the first application of a solve may ask for a tighter one
+// (ifem_solver_opts::inner_rel_first)
+// ... when the residual it is applied to is velocity-dominated.  The block-triangular preconditioner leaves O(0.1) of the
+// pressure part of a residual behind per outer iteration (the pressure Schur complement is only approximated, mpi_insim.cpp:
+// 57-112), so a first Krylov vector whose pressure share exceeds ~10 fgmres_rel cannot be finished in one iteration by
+// a better velocity solve -- the later Newton iterations, whose residual is almost all continuity equation (shares
+// 0.996 / 0.66 against 7e-5 in the first one at 128^3): there the cheap setting is the better one (time_step leg of
+// bench.py: 1.16 s against 1.27 s with the tight first application everywhere)
+// ... and while it pays: a solve whose tight first application did NOT end the outer iteration at its first check has spent
+// the extra inner iterations for nothing (64^3 channel: 2 outer iterations either way, 29.8 instead of 24.5 ms).  After such a
+// miss the context leaves the option off for its next 8 / 16 / 32 / 64 qualifying solves (ins_solve keeps the count), then tries again.
+static double inner_rel_now(SolveState &S) {
+  const ifem_solver_opts *o = S.o;
+  const double pshare_max = o->inner_first_pshare > 0 ? o->inner_first_pshare : 10.0 * o->fgmres_rel;
+  const bool pressure_dominated = S.p_src_norm > pshare_max * std::hypot(S.u_src_norm, S.p_src_norm);
+  bool tight = false;
+  if (S.st.precond_applies == 0 && o->inner_rel_first > 0 && !pressure_dominated) {
+    S.tight_candidate = true;
+    tight = S.tight_used = S.ctx->tight_first_backoff == 0;
+  }
+  const double rel = tight ? o->inner_rel_first : o->inner_rel;
+  if (o->verbose && S.st.precond_applies == 0)
+    fprintf(stderr, "[ifem] first preconditioner application: pressure share of the residual %.3e, inner tolerance %.1e\n",
+            S.p_src_norm / std::max(std::hypot(S.u_src_norm, S.p_src_norm), 1e-300), rel);
+  return rel;
+}
+
+// A~^-1 (:124-127): x = A~^-1 b to rel ||b||, by the inner solver of ifem_solver_opts::ainv_kind
+static void ainv_apply(SolveState &S, const double *b, double *x, double rel) {
+  ifem_ctx *c = S.ctx;
+  const ifem_solver_opts *o = S.o;
+  if (!c->uu_is_stored && o->ainv_kind != IFEM_AINV_GMRES_BJACOBI_MF && o->ainv_kind != IFEM_AINV_MG)
+    throw Error(IFEM_E_BADPARAM, "ifem_tuning::stored_uu = 0 keeps no A_uu values: use IFEM_AINV_MG or IFEM_AINV_GMRES_BJACOBI_MF (the matrix-free inner operators)");
+  const bool scalar_op = o->ainv_kind == IFEM_AINV_SCALAR_GMRES;
+  if (scalar_op) shat_refresh(c, true);
+  const MdotFn mdot = mdot_over(c, S.nuo);
+  double bn;
+  mdot(1, b, S.nuo, b, &bn);
+  const double tol = rel * std::sqrt(bn);
+  if (o->ainv_kind == IFEM_AINV_MG) { // inner GMRES on the matrix-free operator, one V-cycle as its preconditioner
+    MgUu(S).solve(b, x, tol);
+    return;
+  }
+  const bool f32 = o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32;
+  OpFn Auu = [&](const double *u, double *y) { const double *ue; extend_u(S, u, &ue); spmv_uu(c, ue, nullptr, y, f32); };
+  if (o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF) Auu = [&](const double *u, double *y) { uu_apply_level(S, u, y); };
+  if (scalar_op) Auu = [&](const double *u, double *y) { const double *ue; extend_u(S, u, &ue); spmv_shat(c, ue, y, true); };
+  const OpFn Pj = [&](const double *u, double *y) { if (scalar_op) shat_jacobi(c, u, y); else bjac_apply(c, u, y); };
+  // inner_maxit <= 0 means "one V-cycle / stationary sweeps" to IFEM_AINV_MG only; for the Krylov kinds it is the library default cap
+  const int inner_cap = o->inner_maxit > 0 ? o->inner_maxit : 400;
+  const bool f32_basis = (f32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF) && o->inner_restart + 6 <= 64;
+  double res = 0;
+  if (f32_basis) { // columns 0..m: basis, m+1: scratch for V y, up to the next multiple of 4: padding read by the fused kernels
+    const OpF32 Pf = [&](const float *u, double *y) { bjac_apply_f32(c, u, y); };
+    S.st.inner_iters += gmres_f32basis(c, S.nuo, basis_ld(c, S.nuo), Auu, Pf, b, x, o->inner_restart, inner_cap, tol,
+                                       reinterpret_cast<float *>(c->innerV.p), S.inner_z, S.inner_w, &res,
+                                       [&](double *v, int k) { allreduce_sum(c, v, k); });
+  } else
+    S.st.inner_iters += gmres(c, S.nuo, basis_ld(c, S.nuo), /*reorth=*/false, Auu, Pj, false, b, x, o->inner_restart,
+                              inner_cap, tol, c->innerV.p, S.inner_z, S.inner_w, &res, mdot);
 }
 
 static void precond_vmult(SolveState &S, const double *src, double *dst) {
   ifem_ctx *c = S.ctx;
   const ifem_ins_params *P = S.P;
-  const ifem_solver_opts *o = S.o;
   const double *src0 = src, *src1 = src + S.nuo;
   double *dst0 = dst, *dst1 = dst + S.nuo;
-  double *tmp = S.tp[0], *r = S.tp[1], *p = S.tp[2], *q = S.tp[3];
-  auto pdot = [&](const double *a, const double *b) { return dot_all(S, S.npo, a, b); };
-  const double n1 = std::sqrt(pdot(src1, src1));
-  S.p_src_norm = n1;
-  if (S.st.precond_applies == 0 && o->inner_rel_first > 0) { // pressure share of the first Krylov vector (see the inner solve below)
+  double *tmp = S.tp[0];
+  S.p_src_norm = std::sqrt(dot_all(S, S.npo, src1, src1));
+  if (S.st.precond_applies == 0 && S.o->inner_rel_first > 0) { // pressure share of the first Krylov vector (see inner_rel_now)
     double uu = 0;
     v_mdot(S.ctx, S.nuo, 1, src0, S.nuo, src0, &uu);
     allreduce_sum(S.ctx, &uu, 1);
@@ -1107,294 +1459,19 @@ static void precond_vmult(SolveState &S, const double *src, double *dst) {
   };
   mark();
   // CG for Mp (:69-84)
-  // the approximate-preconditioner kinds stream M_p in single precision like S_m (the solve is to 1e-6, the rounding of the
-  // values 6e-8).  (p.q fused into this SpMV was measured: a block reduction in each of its 67 k small blocks costs more
-  // than the separate pass over the two vectors.)
-  const bool mp_f32 = o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF || o->ainv_kind == IFEM_AINV_MG;
-  OpFn mp = [&](const double *x, double *y) {
-    if (halo_overlap_ok(c)) {
-      build_row_split(c, c->Mp, c->nPo);
-      v_copy(c, S.npo, x, S.xp_ext);
-      halo_start(c, S.xp_ext, 1);
-      spmv_mp(c, S.xp_ext, y, 1, mp_f32);
-      halo_wait(c);
-      spmv_mp(c, S.xp_ext, y, 2, mp_f32);
-      return;
-    }
-    const double *xe; extend_p(S, x, &xe);
-    spmv_mp(c, xe, y, 0, mp_f32);
-  };
-  // kinds 1 and 3 (approximate preconditioner) also put a Jacobi preconditioner on the two pressure CG solves: same
-  // stopping rule on the true residual, fewer iterations (the reference uses PreconditionNone; counts are no parity target)
-  const bool pjac = o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF || o->ainv_kind == IFEM_AINV_MG;
-  auto pmdot = [&](int k, const double *V, int64_t ld, const double *w, double *out) {
-    v_mdot(c, S.npo, k, V, ld, w, out, /*all_ranks=*/true);
-  };
-  const int pmax = (int)std::min<int64_t>(std::max<int64_t>(c->n_global_p, 1), 1 << 30);
-  // device-resident recurrences on any number of ranks: the dot products are all-reduced on the stream (comm.hip::allreduce_sum_dev)
-  const bool dev_cg = o->device_cg != 0;
-  if (dev_cg) {
-    if (pjac) scalar_diag(c, c->Mp, c->Mp.val.p, S.tp[5]);
-    S.st.cg_mp_iters += cg_device(c, S.npo, mp, pjac ? S.tp[5] : nullptr, src1, tmp, std::max(o->mp_abs, o->mp_rel * n1), pmax,
-                                  S.tp[1], S.tp[2], S.tp[3], S.tp[4], 4, S.tp[6]);
-  } else if (pjac) {
-    scalar_diag(c, c->Mp, c->Mp.val.p, S.tp[5]);
-    S.st.cg_mp_iters += pcg_jacobi(c, S.npo, mp, S.tp[5], src1, tmp, std::max(o->mp_abs, o->mp_rel * n1), pmax, S.tp[1], c->nPl, S.tp[3], S.tp[4], pmdot); // r = tp[1], z = tp[2]
-  } else
-  S.st.cg_mp_iters += cg(c, S.npo, mp, src1, tmp, std::max(o->mp_abs, o->mp_rel * n1), pmax, r, p, q, pdot);
+  solve_mp(S, src1, tmp);
   v_scale(c, S.npo, -(P->viscosity + P->grad_div * P->rho), tmp);
   mark();
   // CG for Sm (:86-112)
-  const bool lowp_all = o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF || o->ainv_kind == IFEM_AINV_MG;
-  sm_ensure(S);
-  OpFn sm = [&](const double *x, double *y) { sm_apply(S, x, y, lowp_all); };
-  // multigrid-preconditioned CG when coarser levels are attached (every level needs its S_m explicitly: Jacobi smoothing)
-  // (the finest level may apply S_m as two SpMVs -- several ranks without the 2-deep pressure halo, e.g. the strips of an unstructured
-  // mesh above replicated coarse levels: the V-cycle needs the operator and its diagonal there, not the matrix)
-  bool use_mg = o->sm_mg && c->mg_coarse && (sm_is_explicit(S) || (o->explicit_schur && c->halo.nranks > 1));
-  MgSm M;
-  if (use_mg) {
-    M.lowp = lowp_all; M.nu = std::max(1, o->mg_smooth); M.ratio = std::max(1.5, o->mg_cheb_ratio);
-    M.L.push_back(S);
-    for (ifem_ctx *cc = c->mg_coarse; cc; cc = cc->mg_coarse) {
-      SolveState Sc{cc, P, o};
-      carve_workspace(Sc, false);
-      if (!sm_is_explicit(Sc)) { use_mg = false; break; }
-      M.L.push_back(Sc);
-    }
-  }
-  if (use_mg) {
-    mg_sm_setup(M, c->asm_constraint_set);
-    S.st.cg_sm_iters += pcg_mg_sm(M, src1, dst1, std::max(o->sm_abs, o->sm_rel * n1), pmax, S.tp[1], S.tp[2], S.tp[3], S.tp[4]);
-    S.st.sm_mg_levels = (uint32_t)M.L.size();
-  } else if (dev_cg) // (Jacobi on S_m was measured too: 176 instead of 172 iterations -- its diagonal is nearly constant)
-    S.st.cg_sm_iters += cg_device(c, S.npo, sm, nullptr, src1, dst1, std::max(o->sm_abs, o->sm_rel * n1), pmax, S.tp[1], S.tp[2],
-                                  S.tp[3], S.tp[4], 4, S.tp[6]);
-  else
-    S.st.cg_sm_iters += cg(c, S.npo, sm, src1, dst1, std::max(o->sm_abs, o->sm_rel * n1), pmax, r, p, q, pdot);
+  solve_sm(S, src1, dst1);
   v_axpby(c, S.npo, 1.0, tmp, -P->rho / P->dt, dst1);
   // utmp = src0 - B^T dst1 (:116-120)
-  {
-    const double *xe; extend_p(S, dst1, &xe);
-    spmv_bt(c, xe, S.utmp);
-    v_axpby(c, S.nuo, 1.0, src0, -1.0, S.utmp);
-  }
+  const double *xe; extend_p(S, dst1, &xe);
+  spmv_bt(c, xe, S.utmp);
+  v_axpby(c, S.nuo, 1.0, src0, -1.0, S.utmp);
   mark();
   // A~^-1 utmp (:124-127)
-  const bool f32 = o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_F32;
-  if (!c->uu_is_stored && o->ainv_kind != IFEM_AINV_GMRES_BJACOBI_MF && o->ainv_kind != IFEM_AINV_MG)
-    throw Error(IFEM_E_BADPARAM, "ifem_tuning::stored_uu = 0 keeps no A_uu values: use IFEM_AINV_MG or IFEM_AINV_GMRES_BJACOBI_MF (the matrix-free inner operators)");
-  OpFn Auu = [&](const double *x, double *y) { const double *xe; extend_u(S, x, &xe); spmv_uu(c, xe, nullptr, y, f32); };
-  if (o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF)
-    Auu = [&](const double *x, double *y) { uu_apply_level(S, x, y); };
-  const bool scalar_op = o->ainv_kind == IFEM_AINV_SCALAR_GMRES;
-  if (scalar_op) shat_refresh(c, true);
-  if (scalar_op) Auu = [&](const double *x, double *y) { const double *xe; extend_u(S, x, &xe); spmv_shat(c, xe, y, true); };
-  OpFn Pj = [&](const double *x, double *y) { if (scalar_op) shat_jacobi(c, x, y); else bjac_apply(c, x, y); };
-  auto mdot = [&](int k, const double *V, int64_t ld, const double *w, double *out) {
-    v_mdot(c, S.nuo, k, V, ld, w, out, /*all_ranks=*/true);
-  };
-  double un;
-  mdot(1, S.utmp, S.nuo, S.utmp, &un);
-  un = std::sqrt(un);
-  // the first application of a solve may ask for a tighter inner solve (ifem_solver_opts::inner_rel_first)
-  // ... when the residual it is applied to is velocity-dominated.  The block-triangular preconditioner leaves O(0.1) of the
-  // pressure part of a residual behind per outer iteration (the pressure Schur complement is only approximated, mpi_insim.cpp:
-  // 57-112), so a first Krylov vector whose pressure share exceeds ~10 fgmres_rel cannot be finished in one iteration by
-  // a better velocity solve -- the later Newton iterations, whose residual is almost all continuity equation (shares
-  // 0.996 / 0.66 against 7e-5 in the first one at 128^3): there the cheap setting is the better one (time_step leg of
-  // bench.py: 1.16 s against 1.27 s with the tight first application everywhere)
-  const double pshare_max = o->inner_first_pshare > 0 ? o->inner_first_pshare : 10.0 * o->fgmres_rel;
-  const bool pressure_dominated = S.p_src_norm > pshare_max * std::hypot(S.u_src_norm, S.p_src_norm);
-  // ... and while it pays: a solve whose tight first application did NOT end the outer iteration at its first check has spent
-  // the extra inner iterations for nothing (64^3 channel: 2 outer iterations either way, 29.8 instead of 24.5 ms).  After such a
-  // miss the context leaves the option off for its next 8 / 16 / 32 / 64 qualifying solves (ins_solve keeps the count), then tries again.
-  bool tight = false;
-  if (S.st.precond_applies == 0 && o->inner_rel_first > 0 && !pressure_dominated) {
-    S.tight_candidate = true;
-    tight = S.tight_used = c->tight_first_backoff == 0;
-  }
-  const double inner_rel_now = tight ? o->inner_rel_first : o->inner_rel;
-  if (o->verbose && S.st.precond_applies == 0)
-    fprintf(stderr, "[ifem] first preconditioner application: pressure share of the residual %.3e, inner tolerance %.1e\n",
-            S.p_src_norm / std::max(std::hypot(S.u_src_norm, S.p_src_norm), 1e-300), inner_rel_now);
-  double res = 0;
-  if (o->ainv_kind == IFEM_AINV_MG) { // inner GMRES on the matrix-free operator, one V-cycle as its preconditioner
-    MgUu Mu;
-    Mu.nu = std::max(1, o->mg_smooth_u); Mu.nu_post = o->mg_smooth_u_post > 0 ? o->mg_smooth_u_post : Mu.nu; Mu.ratio = std::max(1.5, o->mg_cheb_ratio_u);
-    Mu.L.push_back(S);
-    for (ifem_ctx *p = c; p->mg_coarse && p->mg_Pu.n_rows == p->nUo && p->nUo > 0; p = p->mg_coarse) {
-      SolveState Sc{p->mg_coarse, P, o};
-      carve_workspace(Sc, false);
-      Mu.L.push_back(Sc);
-    }
-    if (!c->mf_valid) throw Error(IFEM_E_BADPARAM, "IFEM_AINV_MG needs the operator state of ifem_ins_assemble / ifem_imex_assemble");
-    mg_uu_setup(Mu);
-    OpFn Amf = [&](const double *x, double *y) { uu_apply_level(S, x, y); };
-    // ifem_tuning::inner_f32: single-precision bases around the cycle, and the cycle without the passes nothing reads (mg_uu_vcycle)
-    const bool trim = c->tune.inner_f32 != 0;
-    OpF32In Amf32 = [&](const float *z, double *y) { uu_apply_f32col(c, z, y); }; // the product on a Z column of fgmres_f32
-    // the cycle itself: eagerly, or as a captured hipGraph (ctx.hpp::VcGraph) on small single-rank chains
-    bool graph_ok = c->tune.vcycle_graph_cells > 0 && c->n_cells <= c->tune.vcycle_graph_cells && !c->profile && !kprof_root(c).on && !profiler_attached();
-    for (const SolveState &L : Mu.L) graph_ok = graph_ok && L.ctx->halo.nranks == 1 && !L.ctx->mg_replica && !L.ctx->profile;
-    auto run_vcycle = [&]() {
-      if (!graph_ok) { mg_uu_vcycle(Mu, 0, trim); return; }
-      std::vector<uint64_t> key;
-      auto put = [&](const void *ptr) { key_ptr(key, ptr); };
-      auto putd = [&](double v) { key_f64(key, v); };
-      key.push_back(Mu.L.size()); key.push_back(uint64_t(Mu.nu)); key.push_back(uint64_t(Mu.nu_post)); putd(Mu.ratio);
-      key.push_back(uint64_t(trim)); // which passes the captured cycle consists of
-      for (const SolveState &L : Mu.L) {
-        ifem_ctx *lc = L.ctx;
-        (void)bjac_f32_ptr(lc); // lazy state (the single-precision copy of the inverse node blocks) stays outside the graph
-        for (auto &v : lc->mguf_vec) put(v.p);
-        put(lc->bjac_f32.p); put(lc->mf_eval.p); put(lc->mf_ycell.p); put(lc->mg_Ru_mask.p); put(lc->mg_Pu_mask.p);
-        put(lc->has_c[lc->asm_constraint_set] ? lc->is_c[lc->asm_constraint_set].p : nullptr);
-        key.push_back(uint64_t(lc->nUo)); key.push_back(uint64_t(lc->n_cells)); key.push_back(uint64_t(lc->mf_noconv)); key.push_back(uint64_t(lc->tune.xcd_swizzle));
-        // everything else the captured launches are made of: the epoch moves with ifem_set_tuning / ifem_set_profiling / ifem_mg_attach
-        key.push_back(lc->graph_epoch); key.push_back(uint64_t(lc->tune.mf_f32));
-        key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) putd(hd); // which cell kernels, and their constants
-        put(lc->bjac.p); put(lc->vcoords.p); put(lc->cell_unodes.p); put(lc->uinc.col.p);
-        key.push_back(uint64_t(patch_active(lc))); put(lc->patch.tab.p); put(lc->patch.inv.p); put(lc->patch.work.p); // the level's smoother and its tables
-        putd(lc->uu_lmax); putd(lc->mf_params.viscosity); putd(lc->mf_params.rho); putd(lc->mf_params.grad_div); putd(lc->mf_params.dt);
-      }
-      if (!graph_run(c, c->vc_graph, key, [&]() { mg_uu_vcycle(Mu, 0, trim); })) {
-        c->tune.vcycle_graph_cells = 0;
-        graph_ok = false;
-        if (o->verbose) fprintf(stderr, "[ifem] hipGraph capture of the A_uu V-cycle failed: eager launches from now on\n");
-      }
-    };
-    // the cycle between its entry and exit runs on the fixed level vectors (and is what a hipGraph captures): whatever vector it is
-    // applied to only appears as an argument of the entry and exit kernels outside of it
-    OpFn Vc = [&](const double *x, double *y) {
-      if (!trim) {
-        v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
-        run_vcycle();
-        v_cvt_f2d(c, S.nuo, c->mguf_vec[1].p, y);
-        return;
-      }
-      if (patch_active(c)) { // the first direction is the patch kernel's: the entry only rounds the residual
-        v_cvt_d2f(c, S.nuo, x, c->mguf_vec[0].p);
-        patch_apply(c, 0.0, mg_uu_entry_c0(Mu), c->mguf_vec[0].p, c->mguf_vec[2].p);
-      } else
-      vc_entry(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
-      run_vcycle();
-      vc_exit(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
-    };
-    OpF32F32 Vcf = [&](const float *x, float *y) { // column j of V -> column j of Z (trim only)
-      if (patch_active(c)) {
-        if (S.nuo) IFEM_HIP_CHECK(hipMemcpyAsync(c->mguf_vec[0].p, x, size_t(S.nuo) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        patch_apply(c, 0.0, mg_uu_entry_c0(Mu), c->mguf_vec[0].p, c->mguf_vec[2].p);
-      } else
-      vc_entry_f32(c, mg_uu_entry_c0(Mu), x, c->mguf_vec[0].p, c->mguf_vec[2].p);
-      run_vcycle();
-      vc_exit_f32(c, S.nuo, c->mguf_vec[1].p, c->mguf_vec[2].p, y);
-    };
-    // one attempt of A~^-1 with the V-cycle; returns false when the result is not finite (a Chebyshev bound below the
-    // spectral radius turns the smoothers into amplifiers)
-    auto attempt = [&]() -> bool {
-      if (o->inner_maxit == 0) { // A~^-1 := one V-cycle, no inner Krylov iteration (the outer solver is flexible)
-        Vc(S.utmp, dst0);
-        S.st.inner_iters += 1;
-      } else if (o->inner_maxit < 0) { // -k: k stationary V-cycle sweeps x += V(b - A x): no Arnoldi process, k - 1 operator products
-        const int k = -o->inner_maxit;
-        Vc(S.utmp, dst0);
-        for (int it = 1; it < k; ++it) {
-          Amf(dst0, S.inner_w);
-          v_axpby(c, S.nuo, 1.0, S.utmp, -1.0, S.inner_w); // r = b - A x
-          Vc(S.inner_w, S.inner_z);
-          v_axpy(c, S.nuo, 1.0, S.inner_z, dst0);
-        }
-        S.st.inner_iters += k;
-      } else { // flexible GMRES: the preconditioned directions are kept, so the update needs no extra V-cycle
-        const int64_t ld = basis_ld(S.ctx, S.nuo);
-        // restart length: the caller's, lengthened by the context when an application needed more than two restart cycles -- a V-cycle
-        // that has lost its mesh independence (the refined cylinder, DESIGN section 6: 147 inner iterations with GMRES(16), 75 with
-        // GMRES(40), 59 with GMRES(100)) stagnates across restarts; the bases grow on demand, so the longer cycle costs memory
-        // only where it is used.  Capped at 128 columns and at a quarter of the free device memory.
-        const int mi = std::max(std::max(1, o->inner_restart), c->inner_restart_eff);
-        int its;
-        // one pair of bases per context: a change of ifem_tuning::inner_f32 gives the other pair back (a no-op when it is empty).  The fp64
-        // basis the node-block-Jacobi fallback below grows under inner_f32 = 1 is deliberately temporary: the next application frees it here
-        if (trim) { c->innerV.release(); c->innerZ.release(); } else { c->innerVf.release(); c->innerZf.release(); }
-        if (trim) {
-          grow_basis(c, c->innerVf, ld, std::min(mi + 1, kBasisStart), mi + 1);
-          grow_basis(c, c->innerZf, ld, std::min(mi, kBasisStart), mi);
-          const auto grow = basis_grower(c, c->innerVf, c->innerZf, ld, mi + 1);
-          its = fgmres_f32(c, S.nuo, ld, Amf, Amf32, Vcf, S.utmp, dst0, mi, o->inner_maxit, inner_rel_now * un, c->innerVf.p, c->innerZf.p,
-                           S.inner_w, &res, [&](double *v, int k) { allreduce_sum(c, v, k); }, grow);
-        } else {
-          grow_basis(c, c->innerV, ld, std::min(mi + 1, kBasisStart), mi + 1);
-          grow_basis(c, c->innerZ, ld, std::min(mi, kBasisStart), mi);
-          const auto grow = basis_grower(c, c->innerV, c->innerZ, ld, mi + 1);
-          its = gmres(c, S.nuo, ld, /*reorth=*/false, Amf, Vc, true, S.utmp, dst0, mi, o->inner_maxit, inner_rel_now * un,
-                      c->innerV.p, c->innerZ.p, S.inner_w, &res, mdot, nullptr, &grow);
-        }
-        S.st.inner_iters += its;
-        if (its > 2 * mi && mi < 128) {
-          size_t fr = 0, tot = 0;
-          (void)hipMemGetInfo(&fr, &tot);
-          int want = std::min(128, 2 * mi);
-          const double per_col = 2.0 * double(ld) * (trim ? sizeof(float) : sizeof(double));
-          int fits = int(std::min<double>(128.0, 0.25 * double(fr) / std::max(per_col, 1.0)));
-          if (c->test_restart_fits > 0) fits = c->test_restart_fits; // test aid (ifem_test_restart_fits): a rank that is short of memory
-          want = std::min(want, std::max(fits, mi));
-          // `its` and `mi` are the same on every rank, free memory and `ld` are not: the restart length must be (the ranks restart
-          // together -- their all-reduces and halo exchanges pair up), so the smallest wish of all ranks wins
-          if (c->halo.nranks > 1) { double w = -double(want); allreduce_max(c, &w, 1); want = int(-w); }
-          if (want > mi) {
-            if (o->verbose) fprintf(stderr, "[ifem] inner GMRES(%d) needed %d iterations: restart length %d from now on\n", mi, its, want);
-            c->inner_restart_eff = want;
-          }
-        }
-      }
-      if (o->inner_maxit > 0) return std::isfinite(res); // the Arnoldi recurrence carries any NaN / Inf of the V-cycle
-      double dn;
-      mdot(1, dst0, S.nuo, dst0, &dn);
-      return std::isfinite(dn);
-    };
-    if (!attempt()) {
-      // re-estimate every level's bound from scratch and try once more; if that fails too, this application falls back to
-      // the node-block Jacobi preconditioned inner solve (the preconditioner degrades, the outer solver stays correct)
-      if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle returned non-finite values: re-estimating the Chebyshev bounds\n");
-      mg_uu_setup(Mu, /*force_bounds=*/true);
-      res = 0;
-      // the fused single-precision kernels read, with zero coefficients, up to 3 columns past the ones in use: none may keep a NaN
-      if (c->innerVf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerVf.p, 0, c->innerVf.n * sizeof(float), c->stream));
-      if (c->innerZf.n) IFEM_HIP_CHECK(hipMemsetAsync(c->innerZf.p, 0, c->innerZf.n * sizeof(float), c->stream));
-      if (!attempt()) {
-        if (o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle still non-finite: node-block Jacobi for this application\n");
-        OpFn Pbj = [&](const double *x, double *y) { bjac_apply(c, x, y); };
-        res = 0;
-        const int64_t ldj = basis_ld(S.ctx, S.nuo);
-        const int mj = std::max(1, o->inner_restart);
-        const std::function<void(int, double *&, double *&)> growv = [&](int cols, double *&V, double *&) {
-          grow_basis(c, c->innerV, ldj, std::min(cols, mj + 1), mj + 1); // (not flexible: one z vector)
-          V = c->innerV.p;
-        };
-        // gmres() stores its first basis vector before it asks `growv` for columns: the fp64 basis must exist here (with
-        // ifem_tuning::inner_f32 the context has not allocated it before this fallback)
-        grow_basis(c, c->innerV, ldj, std::min(mj + 1, kBasisStart), mj + 1);
-        if (S.nuo > 0 && !c->innerV.p) throw Error(IFEM_E_BADPARAM, "inner GMRES: no basis storage");
-        S.st.inner_iters += gmres(c, S.nuo, ldj, /*reorth=*/false, Amf, Pbj, false, S.utmp, dst0, mj,
-                                  std::max(o->inner_maxit, 50), inner_rel_now * un, c->innerV.p, S.inner_z, S.inner_w, &res, mdot, nullptr, &growv);
-      }
-    }
-    mark();
-    S.st.precond_applies++;
-    return;
-  }
-  // inner_maxit <= 0 means "one V-cycle / stationary sweeps" to IFEM_AINV_MG only; for the Krylov kinds it is the library default cap
-  const int inner_cap = o->inner_maxit > 0 ? o->inner_maxit : 400;
-  const bool f32_basis = (f32 || o->ainv_kind == IFEM_AINV_GMRES_BJACOBI_MF) && o->inner_restart + 6 <= 64;
-  if (f32_basis) { // columns 0..m: basis, m+1: scratch for V y, up to the next multiple of 4: padding read by the fused kernels
-    OpF32 Pf = [&](const float *x, double *y) { bjac_apply_f32(c, x, y); };
-    S.st.inner_iters += gmres_f32basis(c, S.nuo, basis_ld(S.ctx, S.nuo), Auu, Pf, S.utmp, dst0, o->inner_restart, inner_cap,
-                                       inner_rel_now * un, reinterpret_cast<float *>(c->innerV.p), S.inner_z, S.inner_w, &res,
-                                       [&](double *v, int k) { allreduce_sum(c, v, k); });
-  } else
-  S.st.inner_iters += gmres(c, S.nuo, basis_ld(S.ctx, S.nuo), /*reorth=*/false, Auu, Pj, false, S.utmp, dst0, o->inner_restart,
-                            inner_cap, inner_rel_now * un, c->innerV.p, S.inner_z, S.inner_w, &res, mdot);
+  ainv_apply(S, S.utmp, dst0, inner_rel_now(S));
   mark();
   S.st.precond_applies++;
 }
@@ -1440,7 +1517,7 @@ static void carve_workspace(SolveState &S, bool krylov) {
   grow_basis(c, c->krylovV, basis_ld(S.ctx, S.n), std::min(m + 1, kBasisStart), m + 1); // the rest on demand (basis_grower)
   grow_basis(c, c->krylovZ, basis_ld(S.ctx, S.n), std::min(m, kBasisStart), m);
   // the inner solve of IFEM_AINV_MG is flexible too and grows its bases the same way; the other kinds' kernels want theirs whole
-  // (its single-precision bases, ifem_tuning::inner_f32, are the solver's own: precond_vmult allocates them where it runs that solver)
+  // (its single-precision bases, ifem_tuning::inner_f32, are the solver's own: MgUu::solve_once allocates them where it runs that solver)
   if (!(S.o->ainv_kind == IFEM_AINV_MG && c->tune.inner_f32 && S.o->inner_maxit > 0))
     grow_inner_basis(c, (int64_t)(S.o->ainv_kind == IFEM_AINV_MG ? std::min(mi + 1, kBasisStart) : mi + 1) * basis_ld(S.ctx, S.nuo));
 }
@@ -1549,12 +1626,8 @@ int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_s
   const int mt = 200;
   grow_inner_basis(ctx, (int64_t)(mt + 1) * basis_ld(S.ctx, S.npo));
   double *rhs = ctx->vec[IFEM_VEC_RHS].p, *upd = ctx->vec[IFEM_VEC_UPDATE].p;
-  auto mdot = [&](int k, const double *V, int64_t ld, const double *w, double *out) {
-    v_mdot(ctx, S.n, k, V, ld, w, out, /*all_ranks=*/true);
-  };
-  auto mdot_p = [&](int k, const double *V, int64_t ld, const double *w, double *out) {
-    v_mdot(ctx, S.npo, k, V, ld, w, out, /*all_ranks=*/true);
-  };
+  const MdotFn mdot = mdot_over(ctx, S.n);
+  const MdotFn mdot_p = mdot_over(ctx, S.npo);
   double bn;
   mdot(1, rhs, S.n, rhs, &bn);
   bn = std::sqrt(bn);
@@ -1659,10 +1732,9 @@ int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_s
       mdot_p(1, S.tp[6], S.npo, S.tp[0], &sc);
       const double alpha = sc != 0 && std::isfinite(sc) ? pn / sc : 0.0;
       v_axpby(ctx, S.npo, 1.0, S.tp[0], -alpha, S.tp[6]); // r0 = ptmp - alpha T_pp ptmp
-      const bool left = ctx->tune.scns_inner_left != 0;
+      const LeftPrecond left_pc{S.tp[5], pa_graph_ok ? &PAg : nullptr};
       S.st.inner_iters += gmres(ctx, S.npo, basis_ld(S.ctx, S.npo), ctx->tune.scns_inner_reorth != 0, Tpp, Jpp, false, S.tp[6], dst1, mt, 100000,
-                                inner_tol, ctx->innerV.p, S.tp[1], S.tp[2], &res, mdot_p, nullptr, nullptr, left, left ? S.tp[5] : nullptr,
-                                left && pa_graph_ok ? &PAg : nullptr);
+                                inner_tol, ctx->innerV.p, S.tp[1], S.tp[2], &res, mdot_p, nullptr, nullptr, ctx->tune.scns_inner_left != 0 ? &left_pc : nullptr);
       v_axpy(ctx, S.npo, alpha, S.tp[0], dst1);
     } else
       S.st.inner_iters += gmres(ctx, S.npo, basis_ld(S.ctx, S.npo), /*reorth=*/true, Tpp, Jpp, false, S.tp[0], dst1, mt, 100000, inner_tol,
@@ -1701,9 +1773,7 @@ int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o
   ctx->mf_ms_total = 0;
   ctx->timing.mf_calls = 0;
   double *rhs = ctx->vec[IFEM_VEC_RHS].p, *upd = ctx->vec[IFEM_VEC_UPDATE].p;
-  auto mdot = [&](int k, const double *V, int64_t ld, const double *w, double *out) {
-    v_mdot(ctx, S.n, k, V, ld, w, out, /*all_ranks=*/true);
-  };
+  const MdotFn mdot = mdot_over(ctx, S.n);
   double bn;
   mdot(1, rhs, S.n, rhs, &bn);
   bn = std::sqrt(bn);
@@ -1720,7 +1790,7 @@ int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o
   apply_constraints(ctx, use_nonzero ? 1 : 0, upd); // constraints_used.distribute(newton_update)
   hanging_distribute(ctx, upd);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  // inner_rel_first pays only when it ends the outer iteration at its first check (precond_vmult); `it` is the same on all ranks
+  // inner_rel_first pays only when it ends the outer iteration at its first check (inner_rel_now); `it` is the same on all ranks
   if (S.tight_used) {
     if (it <= 1) ctx->tight_first_misses = 0;
     else { ctx->tight_first_misses = std::min(ctx->tight_first_misses + 1, 4); ctx->tight_first_backoff = 4 << ctx->tight_first_misses; }

@@ -11,6 +11,7 @@ import pytest
 
 from boxmesh import BoxMesh
 from partmesh import local_dirichlet, partition_mesh, run_virtual_ranks
+from test_gpu_inner_f32 import channel16  # noqa: F401  (fixture: the 16^3 bench channel with its three levels, assembled once for this module)
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +181,27 @@ def test_patch_vcycle_is_deterministic_and_replays_as_a_graph():
             assert np.array_equal(a, b)
     finally:
         s.close()
+
+
+def test_each_smoother_kind_keeps_its_bound_and_graph_across_a_switch(channel16):
+    """ifem_precond_vmult (IFEM_AINV_MG, default options) with uu_smoother = 0, 1, 0, 1 in turn on one context, three applications each
+    (eager, capture, replay): a kind that comes back finds its own Chebyshev bound again (ifem_ctx::uu_bound[kind]) and its graph is
+    captured anew for the tuning epoch -- the first and third settings are the same bits, and so are the second and fourth"""
+    from openifem_amd import capi
+    s, n_u, n_p, v, defaults = channel16
+    for k, val in defaults.items():
+        setattr(s.opts, k, val)
+    ip = capi.make_params(mu=1.0, rho=1.0, gamma=0.1, dt=1e-3)
+    z = []
+    for knob in (0, 1, 0, 1):
+        _set_tuning(s, uu_smoother=knob)
+        z.append([_precond(s, ip, v) for _ in range(3)])
+    _set_tuning(s)
+    assert all(np.isfinite(a).all() for zs in z for a in zs) and np.abs(z[0][0][:n_u]).max() > 0
+    assert not np.array_equal(z[0][0][:n_u], z[1][0][:n_u])  # it is another smoother
+    for first, again in ((z[0], z[2]), (z[1], z[3])):
+        for a in first + again:
+            assert np.array_equal(a, first[0])
 
 
 def test_patch_smoother_needs_fewer_inner_iterations_in_the_cavity_regime():
