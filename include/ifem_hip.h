@@ -234,6 +234,12 @@ typedef struct {
                             term that the node blocks miss at large gamma rho / mu.  Other levels keep the node blocks.  Same Chebyshev
                             recurrence, interval [lambda_max / ratio, 1.1 lambda_max] with lambda_max(B A_uu) estimated per smoother kind.
                             Any other value: IFEM_E_BADPARAM */
+  int32_t uu_patch_levels; /* which levels uu_smoother = 1 reaches.  0 (default): uniform box levels only, as above.  1: every level of Q2
+                            velocity on one rank without hanging-node lines: uniform box levels keep the shared inverses of their patch types,
+                            all other levels (curved or graded cells: the cylinder) store one inverse per patch, integrated and inverted on the
+                            device (patch.hip: at most 13 / 39 nodes per patch in 2D / 3D and 16 colours; a level beyond a cap, or whose
+                            inverses would not fit into the free device memory, keeps its node blocks).  No effect while uu_smoother = 0.
+                            Any other value: IFEM_E_BADPARAM */
 } ifem_tuning;
 /* Initialise an ifem_tuning with ifem_default_tuning before changing fields: a zero-initialised struct gets the documented defaults
  * only for the fields where 0 is not a meaningful value (asm3_cpb, scns_pc, pvv_sweeps, b2pp_sweeps). */

@@ -46,7 +46,8 @@ int ifem_test_mf_uniform(ifem_ctx *ctx, double *h);
 int ifem_test_uu_vmult_f32col(ifem_ctx *ctx, int dst, int src);
 
 /* The vertex-patch smoother of ifem_tuning::uu_smoother = 1 (patch.hip) for the operator state of the last ifem_ins_assemble /
- * ifem_imex_assemble, whatever the tuning says.  ifem_test_uu_patch_vmult: velocity part of the context vector dst = B times the velocity
+ * ifem_imex_assemble, whatever uu_smoother says (a level that is not a uniform box takes part only with ifem_tuning::uu_patch_levels = 1; there
+ * out[2] is the number of stored inverses, one per patch).  ifem_test_uu_patch_vmult: velocity part of the context vector dst = B times the velocity
  * part of src (src rounded to float, single-precision product, as inside the V-cycle); IFEM_E_BADPARAM on a level that is not eligible.
  * ifem_test_uu_patch_info: out = {eligible (0 / 1), patches, patch types, bytes of the inverse tables}; the last three are 0 before an assembly
  * or on a level that is not eligible.  Both build the tables when they are not there yet. */

@@ -119,7 +119,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
 void ifem_default_tuning(ifem_tuning *t) {
   t->geo_cache = 1; t->xcd_swizzle = 1; t->asm_skip = 0; t->spmv_lanes = 32; t->sm_lanes = 32; t->mf_f32 = 1;
   t->tpp_operator = 0; t->spmv_pipe = 1; t->halo_overlap = 1; t->asm3_variant = 0; t->cg_single_reduction = 1; t->asm3_cpb = 2; t->tpp_milu_permille = 950; t->tpp_ilu_order = 2; t->basis_pad = 32 * 33; t->tpp_tri_sweeps = 0; t->uu_row_order = 1; t->eig_steps = 0; t->vcycle_graph_cells = 262144;
-  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->uu_smoother = 0;
+  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->uu_smoother = 0; t->uu_patch_levels = 0;
 }
 
 int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
@@ -133,6 +133,7 @@ int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
   if (t->tpp_ilu_order < -1 || t->tpp_ilu_order > 2) throw Error(IFEM_E_BADPARAM, "tpp_ilu_order must be -1, 0, 1 or 2");
   if (t->scns_pc != 0 && t->scns_pc != 1 && t->scns_pc != 2) throw Error(IFEM_E_BADPARAM, "scns_pc must be 1 (explicit T_pp) or 2 (the reference's structure); 0 = default");
   if (t->uu_smoother != 0 && t->uu_smoother != 1) throw Error(IFEM_E_BADPARAM, "uu_smoother must be 0 (node-block Jacobi) or 1 (vertex patches on uniform box levels)");
+  if (t->uu_patch_levels != 0 && t->uu_patch_levels != 1) throw Error(IFEM_E_BADPARAM, "uu_patch_levels must be 0 (uniform box levels only) or 1 (per-patch inverses on all other eligible levels)");
   ctx->tune = *t;
   ++ctx->graph_epoch;
   if (ctx->tune.asm3_cpb <= 0) ctx->tune.asm3_cpb = 2; // a zero-initialised struct: the defaults of the fields added after round 4
@@ -854,7 +855,7 @@ int ifem_test_uu_patch_info(ifem_ctx *ctx, int64_t out[4]) {
   const bool tables = ok && ctx->patch.valid;
   out[0] = ok ? 1 : 0;
   out[1] = tables ? ctx->patch.n_patches : 0;
-  out[2] = tables ? ctx->patch.n_types : 0;
+  out[2] = tables ? (ctx->patch.form == 1 ? ctx->patch.n_patches : ctx->patch.n_types) : 0; // stored inverses
   out[3] = tables ? ctx->patch.inv_bytes : 0;
   IFEM_API_END
 }

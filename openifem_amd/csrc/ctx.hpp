@@ -280,18 +280,37 @@ struct MgCsr {
 } // namespace ifem
 
 namespace ifem {
-// Vertex-patch smoother of the A_uu V-cycle on a uniform box level (patch.hip; ifem_tuning::uu_smoother = 1): the patch of a mesh
-// vertex is the lattice box of +-1 velocity node around it, clipped at the domain.  All patches with the same present nodes and the
-// same constrained dofs (a "type") share one inverse.  Built on the host once per (mu, rho, gamma, dt, h, constrained-dof set).
+// Vertex-patch smoother of the A_uu V-cycle (patch.hip; ifem_tuning::uu_smoother = 1): the patch of a mesh vertex holds the velocity nodes
+// within one node spacing of it in every cell that contains it.  Two forms of the tables, chosen per level:
+// form 0, a uniform box level: the patch is the lattice box of +-1 node, clipped at the domain; all patches with the same present nodes and
+//   the same constrained dofs (a "type") share one inverse.  Built on the host once per (mu, rho, gamma, dt, h, constrained-dof set).
+// form 1, any other level (ifem_tuning::uu_patch_levels = 1): patches of 4..13 / 8..39 nodes (2D / 3D) from the cell tables alone, one stored
+//   inverse per patch.  The topology (gen_*) is built on the host once per context, the inverses on the device once per
+//   (mu, rho, gamma, dt, constrained-dof set).
 struct PatchSmoother {
   bool eligible = false, valid = false; // the level can take the patch smoother / the tables below belong to `key`
-  double key[8] = {0, 0, 0, 0, 0, 0, 0, -1};
+  double key[9] = {0, 0, 0, 0, 0, 0, 0, -1, -1}; // mu, rho, gamma, dt, h[3], constrained-dof set, form
+  int form = 0;
   int64_t n_patches = 0, inv_bytes = 0;
   int n_types = 0;
-  DBuf<int32_t> tab;   // [n_patches][3^dim] velocity nodes of every patch (-1: clipped), patches sorted by (colour, type)
-  DBuf<float> inv;     // [n_types][N][N] inverse patch matrices, N = dim 3^dim (symmetric; clipped nodes: identity rows)
-  DBuf<int32_t> work;  // [n_work][3] work items of the kernel: type, first patch, patches (one colour, one type each)
-  int work_ptr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // work items of colour c: [work_ptr[c], work_ptr[c + 1])
+  DBuf<int32_t> tab;   // form 0: [n_patches][3^dim] velocity nodes of every patch (-1: clipped), patches sorted by (colour, type)
+  DBuf<float> inv;     // form 0: [n_types][N][N] inverse patch matrices, N = dim 3^dim (symmetric; clipped nodes: identity rows)
+                       // form 1: the [N_v][N_v] inverse of patch v at gen_inv_off[v], N_v = dim x its nodes (symmetric)
+  DBuf<int32_t> work;  // form 0: [n_work][3] work items of the kernel: type, first patch, patches (one colour, one type each)
+  int work_ptr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // form 0: work items of colour c: [work_ptr[c], work_ptr[c + 1])
+  // form 1: patches sorted by (colour, nodes)
+  int gen_state = 0;            // topology of this context: 0 not looked at, 1 built, -1 beyond a cap (the level keeps its node blocks)
+  DBuf<int64_t> gen_node_ptr;   // [n_patches + 1] into gen_nodes
+  DBuf<int32_t> gen_nodes;      // velocity node | 1 << 31 when this patch has the lowest colour among the patches that hold the node
+  DBuf<int64_t> gen_cell_ptr;   // [n_patches + 1] into gen_cells
+  DBuf<int32_t> gen_cells;      // cell << 3 | corner at which the patch's vertex sits in that cell
+  DBuf<int64_t> gen_inv_off;    // [n_patches] offset of the patch's inverse in `inv`, in floats
+  DBuf<int32_t> gen_bad;        // [1] set by the setup kernel: a non-positive pivot
+  int64_t gen_col_ptr[17] = {0}; // patches of colour c: [gen_col_ptr[c], gen_col_ptr[c + 1])
+  int gen_colours = 0;
+  int64_t gen_entries = 0, gen_inv_floats = 0; // patch nodes over all patches; floats of the inverse store
+  double gen_rejected_key[9] = {0, 0, 0, 0, 0, 0, 0, -1, -1}; // the last key the device setup refused (pivot / memory): not tried again
+  bool gen_rejected = false;
 };
 } // namespace ifem
 

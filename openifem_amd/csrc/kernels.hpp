@@ -204,9 +204,10 @@ void vc_entry_f32(ifem_ctx *ctx, double c0, const float *src, float *r, float *d
 void vc_exit(ifem_ctx *ctx, int64_t n, const float *x, const float *d, double *out);
 void vc_exit_f32(ifem_ctx *ctx, int64_t n, const float *x, const float *d, float *out);
 
-// patch.hip: the vertex-patch smoother B = sum_v R_v^T A_v^-1 R_v of a uniform box level (ifem_tuning::uu_smoother = 1)
-bool patch_eligible(const ifem_ctx *ctx);  // uniform box level, Q2 velocity, one rank, no hanging-node lines
-bool patch_setup(ifem_ctx *ctx);           // tables for the level's operator state (host, cached on its key); false: not eligible
+// patch.hip: the vertex-patch smoother B = sum_v R_v^T A_v^-1 R_v of a level (ifem_tuning::uu_smoother = 1): shared inverses per patch type on a
+// uniform box level, one inverse per patch on the others (ifem_tuning::uu_patch_levels = 1)
+bool patch_eligible(const ifem_ctx *ctx);  // Q2 velocity, one rank, no hanging-node lines; a uniform box level, or uu_patch_levels = 1
+bool patch_setup(ifem_ctx *ctx);           // tables for the level's operator state (cached on its key); false: not eligible (or beyond a cap of its form)
 void patch_apply(ifem_ctx *ctx, double a, double b, const float *r, float *d); // d = a d + b B r, one launch per colour
 inline bool patch_active(const ifem_ctx *c) { return c->tune.uu_smoother == 1 && c->patch.eligible && c->patch.valid; }
 

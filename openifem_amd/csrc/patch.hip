@@ -1,4 +1,5 @@
-// patch.hip -- vertex-patch smoother of the A_uu V-cycle on uniform box levels (ifem_tuning::uu_smoother = 1).
+// patch.hip -- vertex-patch smoother of the A_uu V-cycle (ifem_tuning::uu_smoother = 1): the shared-type form of uniform box levels, and
+// (at the end of this file, ifem_tuning::uu_patch_levels = 1) the general form with one inverse per patch for every other level.
 //
 // The patch of mesh vertex v holds every Q2 velocity node n such that each cell containing n also contains v: on a box the lattice box
 // of +-1 node around v, clipped at the domain (27 nodes in 3D, 9 in 2D; 18 / 12 / 8 on a face / edge / corner).  With A0 = mu K +
@@ -30,6 +31,7 @@
 #include <cstring>
 #include <map>
 #include <vector>
+#include "assemble_common.hpp"
 #include "ctx.hpp"
 #include "kernels.hpp"
 
@@ -122,9 +124,17 @@ __global__ __launch_bounds__(256) void k_patch_apply(const int32_t *__restrict__
   }
 }
 
-bool patch_eligible(const ifem_ctx *c) {
-  return mf_takes_uniform(c) && c->kv == 2 && c->halo.nranks == 1 && !c->hang.active && c->hang.n == 0 && c->n_cells > 0 && c->nUl == c->nUo;
+// what every form needs: Q2 velocity on one rank without hanging-node lines
+static bool patch_level_ok(const ifem_ctx *c) {
+  return c->kv == 2 && c->halo.nranks == 1 && !c->hang.active && c->hang.n == 0 && c->n_cells > 0 && c->nUl == c->nUo;
 }
+// the form of the tables a level takes: 0 shared types (a uniform box level), 1 one inverse per patch (ifem_tuning::uu_patch_levels = 1), -1 none
+static int patch_form(const ifem_ctx *c) {
+  if (!patch_level_ok(c)) return -1;
+  if (mf_takes_uniform(c)) return 0;
+  return c->tune.uu_patch_levels == 1 && c->patch.gen_state >= 0 ? 1 : -1;
+}
+bool patch_eligible(const ifem_ctx *c) { return patch_form(c) >= 0; }
 
 // dense inverse by LU with partial pivoting (fp64, n <= 81); false: singular
 static bool invert_dense(int n, std::vector<double> &A, std::vector<double> &Ai) {
@@ -323,18 +333,26 @@ static bool patch_build(int dim, int64_t nc, int64_t nV, int64_t nU, const std::
   return true;
 }
 
+static bool patch_gen_setup(ifem_ctx *ctx, const double key[9]);
+static void patch_gen_apply(ifem_ctx *ctx, double a, double b, const float *r, float *d);
+
 bool patch_setup(ifem_ctx *ctx) {
   PatchSmoother &S = ctx->patch;
-  S.eligible = patch_eligible(ctx);
+  const int form = patch_form(ctx);
+  S.eligible = form >= 0;
   if (!S.eligible) return false;
   if (!ctx->mf_valid) throw Error(IFEM_E_BADPARAM, "vertex-patch smoother: no operator state on this level");
   const int dim = ctx->dim, nu = ctx->nu, np = ctx->np;
   const int cs = ctx->asm_constraint_set;
   const ifem_ins_params &Pm = ctx->mf_params;
-  const double key[8] = {Pm.viscosity, Pm.rho, Pm.grad_div, Pm.dt, ctx->mf_h[0], ctx->mf_h[1], ctx->mf_h[2],
-                         ctx->has_c[cs] ? double(ctx->flag_id[cs]) : -2.0};
+  const double key[9] = {Pm.viscosity, Pm.rho, Pm.grad_div, Pm.dt, form == 0 ? ctx->mf_h[0] : 0.0, form == 0 ? ctx->mf_h[1] : 0.0,
+                         form == 0 ? ctx->mf_h[2] : 0.0, ctx->has_c[cs] ? double(ctx->flag_id[cs]) : -2.0, double(form)};
   if (S.valid && std::memcmp(key, S.key, sizeof(key)) == 0) return true;
   S.valid = false;
+  if (form == 1) {
+    S.eligible = patch_gen_setup(ctx, key);
+    return S.eligible;
+  }
   hipStream_t s = ctx->stream;
   const int64_t nc = ctx->n_cells, nV = ctx->nPl, nU = ctx->nUo;
   const std::vector<int32_t> cu = ctx->cell_unodes.download(s), cp = ctx->cell_pnodes.download(s);
@@ -354,6 +372,7 @@ bool patch_setup(ifem_ctx *ctx) {
   S.n_types = T.n_types;
   S.inv_bytes = int64_t(T.inv.size() * sizeof(float));
   std::memcpy(S.key, key, sizeof(key));
+  S.form = 0;
   S.valid = true;
   return true;
 }
@@ -361,6 +380,7 @@ bool patch_setup(ifem_ctx *ctx) {
 void patch_apply(ifem_ctx *ctx, double a, double b, const float *r, float *d) {
   const PatchSmoother &S = ctx->patch;
   if (!S.valid || !S.eligible) throw Error(IFEM_E_BADPARAM, "vertex-patch smoother applied without its tables (patch_setup)");
+  if (S.form == 1) { patch_gen_apply(ctx, a, b, r, d); return; }
   const int dim = ctx->dim, ncol = 1 << dim, N = dim * (dim == 3 ? 27 : 9);
   // per patch: its node table, the gathered residual and the read-modify-write of d; 2 N^2 flops
   KScope ks(ctx, IFEM_KC_VECTOR, double(S.n_patches) * (N / dim) * (4.0 + 12.0 * dim), 2.0 * double(S.n_patches) * N * N);
@@ -370,6 +390,434 @@ void patch_apply(ifem_ctx *ctx, double a, double b, const float *r, float *d) {
     const int32_t *w = S.work.p + size_t(S.work_ptr[c]) * 3;
     if (dim == 3) hipLaunchKernelGGL((k_patch_apply<3>), dim3(unsigned(nw)), dim3(256), 0, ctx->stream, S.tab.p, S.inv.p, w, c, float(a), float(b), r, d);
     else hipLaunchKernelGGL((k_patch_apply<2>), dim3(unsigned(nw)), dim3(256), 0, ctx->stream, S.tab.p, S.inv.p, w, c, float(a), float(b), r, d);
+  }
+  IFEM_HIP_CHECK(hipGetLastError());
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The general form (ifem_tuning::uu_patch_levels = 1): levels whose cells differ -- curved or graded meshes, the cylinder.
+//
+// Same patch, stated without a lattice: for every cell that holds vertex v at its corner b, the 2^dim local nodes within one node spacing
+// of b in the cell's reference lattice.  A vertex of valence 1, 2, 4, 5 in 2D gives 4 / 6 / 9 / 11 nodes; the extruded 3D cylinder 8 / 12 /
+// 18 / 22 / 27 / 33 nodes (up to 99 dofs).  Every cell that holds a node of the patch holds v, so A_v = R_v A0 R_v^T is the sum of those cells'
+// sub-blocks (the host checks that a cell's nodes inside the patch are exactly the 2^dim near its corner; a level where they are not is refused).
+// Caps: at most 13 (2D) / 39 (3D) nodes per patch, at most 16 colours, fewer than 2^28 cells.  A level beyond a cap is not eligible and
+// keeps its node blocks; nothing throws.
+//
+// Tables (host, topology only, once per context): per patch its node list, its (cell, corner) list and the 64-bit offset of its inverse;
+// per (patch, node) one bit that says that this patch has the lowest colour among the patches holding the node -- it applies the term a d,
+// which the box kernel derives from lattice parity.  Colours: greedy in vertex order under "no two vertices of one cell share a colour"
+// (two patches share a node only if their vertices share a cell): deterministic, 5 colours on the 2D cylinder, 10 on the extruded one.
+// Patches are sorted by colour, then by size.
+//
+// Setup kernel (fp64, once per (mu, rho, gamma, dt, constrained-dof set)): one workgroup per patch.  Per cell of the patch the
+// (2^dim dim)^2 sub-block of A0 is integrated over the cell's quadrature points (J^-1 and JxW from the Q1 vertex map, the 1D tables of the
+// matrix-free kernels) and added to the patch matrix, which lives in LDS as a packed lower triangle (117 x 118 / 2 doubles = 54 kB: the
+// whole kernel stays below the 64 kB a workgroup gets without opt-in).  Constrained dofs become decoupled 1 x 1 rows with |a_ii|, then
+// the matrix is inverted in place by symmetric Gauss-Jordan sweeps without pivoting (A_v is symmetric positive definite: the rho / dt mass
+// term; condition number <= 41 on the cylinder at gamma rho / mu = 100).  A pivot that is not positive sets a flag: the level is refused.
+// The inverse goes out as a full float [N_v][N_v] (symmetric by construction).
+//
+// Apply kernel (fp32): d <- a d + b B r, one launch per colour, plain stores in a fixed order.  Every patch streams its own inverse from
+// memory once -- 2 flops per 4 bytes, bound by bandwidth -- so the layout serves the loads: a group of G lanes (64 in 3D, 32 in 2D; 4 / 8
+// patches per workgroup) takes a patch, lane i accumulates row i (and i + 64 in 3D), and for each column j reads float j N + i: consecutive
+// lanes, consecutive floats (the symmetric inverse read by column).  The patch's residual is gathered into LDS once.  Lanes beyond the patch's
+// size read nothing and store nothing.
+template <int DIM>
+struct GenDims {
+  static constexpr int CAPNN = DIM == 3 ? 39 : 13; // most nodes of a patch
+  static constexpr int CAPN = DIM * CAPNN;         // most dofs: 117 / 26
+  static constexpr int NK = 1 << DIM;              // nodes of a cell within one node spacing of a corner
+  static constexpr int NQ = DIM == 3 ? 27 : 9;     // quadrature points = nodes of a Q2 cell
+  static constexpr int G = DIM == 3 ? 64 : 32;     // apply: lanes per patch
+  static constexpr int ROWS = DIM == 3 ? 2 : 1;    // apply: rows per lane, G ROWS >= CAPN
+  static constexpr int PPB = 256 / G;              // apply: patches per workgroup
+};
+constexpr int kPatchMaxColours = 16;
+
+struct PatchGenArgs {
+  const int64_t *node_ptr, *cell_ptr, *inv_off;
+  const int32_t *nodes, *cells;
+  const double *vcoords;
+  const int32_t *cell_unodes;
+  const uint8_t *is_c;
+  float *inv;
+  int32_t *bad;
+  double mu, rho, gamma, inv_dt;
+  Tab1D t;
+};
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_patch_gen_setup(PatchGenArgs A) {
+  using D = GenDims<DIM>;
+  constexpr int NK = D::NK, NQ = D::NQ, NV = 1 << DIM, M = NK * DIM;
+  __shared__ double sA[D::CAPN * (D::CAPN + 1) / 2]; // packed lower triangle of the patch matrix: (i, j <= i) at i (i + 1) / 2 + j
+  __shared__ double sCol[D::CAPN];
+  __shared__ double sG[NQ * NK * DIM], sN[NQ * NK], sW[NQ], sX[NV * DIM]; // per cell: physical gradients / values of its near nodes, JxW, vertices
+  __shared__ double tN[9], tD[9], tX[3], tW[3];
+  __shared__ int32_t sNode[D::CAPNN], sSlot[NK];
+  __shared__ uint8_t sCon[D::CAPN];
+  const int t = threadIdx.x;
+  const int64_t p = blockIdx.x, n0 = A.node_ptr[p];
+  const int nn = min(int(A.node_ptr[p + 1] - n0), D::CAPNN), N = nn * DIM, NP = N * (N + 1) / 2;
+  if (t < 9) { tN[t] = A.t.N[t]; tD[t] = A.t.dN[t]; }
+  if (t < 3) { tX[t] = A.t.xi[t]; tW[t] = A.t.w[t]; }
+  if (t < nn) sNode[t] = A.nodes[n0 + t] & 0x7fffffff;
+  for (int e = t; e < NP; e += 256) sA[e] = 0.0;
+  __syncthreads();
+  if (t < N) sCon[t] = A.is_c ? A.is_c[int64_t(sNode[t / DIM]) * DIM + t % DIM] : uint8_t(0);
+  for (int64_t k = A.cell_ptr[p]; k < A.cell_ptr[p + 1]; ++k) {
+    const int32_t cb = A.cells[k];
+    const int64_t cell = cb >> 3;
+    const int b = cb & 7;
+    __syncthreads(); // the previous cell's tables are consumed
+    if (t < NV * DIM) sX[t] = A.vcoords[cell * NV * DIM + t];
+    if (t < NK) { // the near node t of corner b and its place in the patch
+      int a = 0, mul = 1;
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) { a += (((b >> e) & 1) + ((t >> e) & 1)) * mul; mul *= 3; }
+      const int32_t node = A.cell_unodes[cell * NQ + a];
+      int slot = -1;
+      for (int i = 0; i < nn; ++i) slot = sNode[i] == node ? i : slot;
+      sSlot[t] = slot;
+    }
+    __syncthreads();
+    if (t < NQ * NK) { // (quadrature point, near node): the d-linear map's Jacobian at the point, the node's shape value and physical gradient
+      const int q = t / NK, kn = t - q * NK;
+      int qi[DIM];
+      double L[DIM][2], wq = 1.0;
+#pragma unroll
+      for (int e = 0, r = q; e < DIM; ++e) {
+        qi[e] = r % 3; r /= 3;
+        const double x_ = tX[qi[e]];
+        L[e][1] = x_; L[e][0] = 1.0 - x_; wq *= tW[qi[e]];
+      }
+      double J[DIM * DIM], Ji[DIM * DIM];
+#pragma unroll
+      for (int i = 0; i < DIM * DIM; ++i) J[i] = 0.0;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+#pragma unroll
+        for (int dd = 0; dd < DIM; ++dd) {
+          double g = ((v >> dd) & 1) ? 1.0 : -1.0;
+#pragma unroll
+          for (int o = 0; o < DIM; ++o) if (o != dd) g *= L[o][(v >> o) & 1];
+#pragma unroll
+          for (int e = 0; e < DIM; ++e) J[e * DIM + dd] += sX[v * DIM + e] * g;
+        }
+      }
+      const double det = inv_small<DIM, double>(J, Ji);
+      if (kn == 0) sW[q] = fabs(det) * wq;
+      double nv[DIM], dv[DIM], Nval = 1.0;
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) {
+        const int ia = ((b >> e) & 1) + ((kn >> e) & 1);
+        nv[e] = tN[qi[e] * 3 + ia]; dv[e] = tD[qi[e] * 3 + ia];
+        Nval *= nv[e];
+      }
+      double dr[DIM];
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) {
+        double g = dv[e];
+#pragma unroll
+        for (int o = 0; o < DIM; ++o) if (o != e) g *= nv[o];
+        dr[e] = g;
+      }
+      sN[q * NK + kn] = Nval;
+#pragma unroll
+      for (int dd = 0; dd < DIM; ++dd) { // physical gradient d_dd N = sum_e (d^_e N) Ji[e][dd]
+        double g = 0.0;
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) g += dr[e] * Ji[e * DIM + dd];
+        sG[(q * NK + kn) * DIM + dd] = g;
+      }
+    }
+    __syncthreads();
+    for (int e = t; e < M * M; e += 256) { // entry (near node ka, component c) x (kb, c2) of the cell's sub-block, lower triangle of the patch
+      const int ra = e / M, rb = e - ra * M, ka = ra / DIM, c = ra - ka * DIM, kb = rb / DIM, c2 = rb - kb * DIM;
+      const int sa = sSlot[ka], sb = sSlot[kb];
+      const int I = sa * DIM + c, Jx = sb * DIM + c2;
+      if (sa < 0 || sb < 0 || I < Jx) continue;
+      double sum = 0.0;
+      for (int q = 0; q < NQ; ++q) {
+        const double *ga = &sG[(q * NK + ka) * DIM], *gb = &sG[(q * NK + kb) * DIM];
+        double gg = 0.0;
+#pragma unroll
+        for (int dd = 0; dd < DIM; ++dd) gg += ga[dd] * gb[dd];
+        const double sc = c == c2 ? A.mu * gg + A.rho * A.inv_dt * sN[q * NK + ka] * sN[q * NK + kb] : 0.0;
+        sum += sW[q] * (sc + A.gamma * A.rho * ga[c] * gb[c2]);
+      }
+      sA[I * (I + 1) / 2 + Jx] += sum; // (one entry of this cell per place: no two threads meet)
+    }
+  }
+  __syncthreads();
+  // my entries of the packed triangle: t, t + 256, ...; (i, j) walks along with them
+  int i0 = 0, j0 = t;
+  while (j0 > i0) { j0 -= i0 + 1; ++i0; }
+  // the constraint rule of the assembly: a constrained dof is a decoupled 1 x 1 row / column with |a_ii|
+  for (int e = t, i = i0, j = j0; e < NP; e += 256) {
+    if (sCon[i] || sCon[j]) {
+      const double v = fabs(sA[e]);
+      sA[e] = i == j ? (v > 0.0 ? v : 1.0) : 0.0;
+    }
+    j += 256;
+    while (j > i) { j -= i + 1; ++i; }
+  }
+  // in-place inverse by symmetric Gauss-Jordan sweeps: after all of them the triangle holds -A^-1
+  for (int k = 0; k < N; ++k) {
+    __syncthreads();
+    if (t < N) sCol[t] = t >= k ? sA[t * (t + 1) / 2 + k] : sA[k * (k + 1) / 2 + t];
+    __syncthreads();
+    const double dk = sCol[k];
+    if (!(dk > 0.0) || !(dk < 1e300)) { // (the same value in every thread: the whole workgroup leaves)
+      if (t == 0) atomicMax(A.bad, 1);
+      return;
+    }
+    const double idk = 1.0 / dk;
+    for (int e = t, i = i0, j = j0; e < NP; e += 256) {
+      double v;
+      if (i == k) v = j == k ? -idk : sCol[j] * idk;
+      else if (j == k) v = sCol[i] * idk;
+      else v = sA[e] - sCol[i] * sCol[j] * idk;
+      sA[e] = v;
+      j += 256;
+      while (j > i) { j -= i + 1; ++i; }
+    }
+  }
+  __syncthreads();
+  float *out = A.inv + A.inv_off[p];
+  for (int e = t; e < N * N; e += 256) {
+    const int i = e / N, j = e - i * N, hi = max(i, j), lo = min(i, j);
+    out[e] = float(-sA[hi * (hi + 1) / 2 + lo]);
+  }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_patch_gen_apply(const int64_t *__restrict__ node_ptr, const int32_t *__restrict__ nodes,
+                                                         const int64_t *__restrict__ inv_off, const float *__restrict__ inv, int64_t p0,
+                                                         int64_t cnt, float a, float b, const float *__restrict__ r, float *__restrict__ d) {
+  using D = GenDims<DIM>;
+  constexpr int G = D::G, ROWS = D::ROWS, PPB = D::PPB, LD = G * ROWS;
+  __shared__ float sR[PPB * LD];
+  __shared__ int32_t sNode[PPB * D::CAPNN];
+  const int g = threadIdx.x / G, l = threadIdx.x - g * G;
+  const int64_t pi = int64_t(blockIdx.x) * PPB + g;
+  const bool live = pi < cnt;
+  const int64_t p = p0 + (live ? pi : 0);
+  const int64_t n0 = node_ptr[p];
+  const int N = live ? DIM * min(int(node_ptr[p + 1] - n0), D::CAPNN) : 0;
+  if (l * DIM < N && l < D::CAPNN) sNode[g * D::CAPNN + l] = nodes[n0 + l];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < ROWS; ++k) {
+    const int i = l + k * G;
+    if (i < N) sR[g * LD + i] = r[int64_t(sNode[g * D::CAPNN + i / DIM] & 0x7fffffff) * DIM + i % DIM];
+  }
+  __syncthreads();
+  const float *__restrict__ m = inv + inv_off[p];
+  float acc[ROWS];
+#pragma unroll
+  for (int k = 0; k < ROWS; ++k) acc[k] = 0.0f;
+#pragma unroll 4
+  for (int j = 0; j < N; ++j) {
+    const float rj = sR[g * LD + j];
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+      const int i = l + k * G;
+      if (i < N) acc[k] = fmaf(m[j * N + i], rj, acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < ROWS; ++k) {
+    const int i = l + k * G;
+    if (i >= N) continue;
+    const int32_t e = sNode[g * D::CAPNN + i / DIM];
+    const int64_t idx = int64_t(e & 0x7fffffff) * DIM + i % DIM;
+    float v = b * acc[k];
+    if (e >= 0) v += d[idx];                 // a patch of a lower colour has been here
+    else if (a != 0.0f) v += a * d[idx];     // the first one applies a d (a = 0: d holds nothing yet and is not read)
+    d[idx] = v;
+  }
+}
+
+// topology of the general form, once per context (the mesh never changes).  false: the level is beyond a cap
+static bool patch_gen_topology(ifem_ctx *ctx) {
+  PatchSmoother &S = ctx->patch;
+  if (S.gen_state) return S.gen_state > 0;
+  S.gen_state = -1;
+  const int dim = ctx->dim, nu = ctx->nu, np = ctx->np, nk = 1 << dim, cap = dim == 3 ? GenDims<3>::CAPNN : GenDims<2>::CAPNN;
+  const int64_t nc = ctx->n_cells, nV = ctx->nPl, nU = ctx->nUo;
+  if (nc >= (int64_t(1) << 28) || nV <= 0) return false;
+  hipStream_t s = ctx->stream;
+  const std::vector<int32_t> cu = ctx->cell_unodes.download(s), cp = ctx->cell_pnodes.download(s);
+  if ((int64_t)cu.size() != nc * nu || (int64_t)cp.size() != nc * np) throw Error(IFEM_E_BADPARAM, "vertex-patch smoother: cell tables of unexpected size");
+  for (int32_t v : cp) if (v < 0 || v >= nV) throw Error(IFEM_E_BADPARAM, "vertex-patch smoother: vertex id outside the level");
+  for (int32_t n : cu) if (n < 0 || n >= nU) throw Error(IFEM_E_BADPARAM, "vertex-patch smoother: node id outside the owned range");
+  // vertex -> (cell, corner)
+  std::vector<int64_t> vptr(size_t(nV) + 1, 0);
+  for (int32_t v : cp) ++vptr[size_t(v) + 1];
+  for (int64_t v = 0; v < nV; ++v) vptr[v + 1] += vptr[v];
+  std::vector<int32_t> vcell(size_t(nc) * np);
+  {
+    std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
+    for (int64_t c = 0; c < nc; ++c)
+      for (int b = 0; b < np; ++b) vcell[size_t(fill[cp[c * np + b]]++)] = int32_t(c << 3 | b);
+  }
+  int near[8][8]; // local node k of the 2^dim within one node spacing of corner b
+  for (int b = 0; b < np; ++b)
+    for (int k = 0; k < nk; ++k) {
+      int a = 0, mul = 1;
+      for (int e = 0; e < dim; ++e) { a += (((b >> e) & 1) + ((k >> e) & 1)) * mul; mul *= 3; }
+      near[b][k] = a;
+    }
+  // nodes of every patch in the order its cells bring them; greedy colours in vertex order
+  std::vector<int64_t> nptr(size_t(nV) + 1, 0);
+  std::vector<int32_t> pn;
+  pn.reserve(size_t(nV) * (dim == 3 ? 27 : 9));
+  std::vector<int32_t> stamp(size_t(nU), -1);
+  std::vector<int8_t> colour(size_t(nV), -1);
+  int n_colours = 0;
+  for (int64_t v = 0; v < nV; ++v) {
+    if (vptr[v + 1] == vptr[v]) return false; // a vertex without a cell
+    uint32_t used = 0;
+    for (int64_t k = vptr[v]; k < vptr[v + 1]; ++k) {
+      const int64_t c = vcell[k] >> 3;
+      const int b = vcell[k] & 7;
+      for (int k2 = 0; k2 < nk; ++k2) {
+        const int32_t node = cu[c * nu + near[b][k2]];
+        if (stamp[node] != v) { stamp[node] = int32_t(v); pn.push_back(node); }
+      }
+      for (int b2 = 0; b2 < np; ++b2) {
+        const int8_t cw = colour[cp[c * np + b2]];
+        if (cw >= 0) used |= 1u << cw;
+      }
+    }
+    nptr[v + 1] = int64_t(pn.size());
+    if (nptr[v + 1] - nptr[v] > cap) return false;
+    // every node of a cell of the patch that lies in the patch must be one of the 2^dim near its corner: then the cells' sub-blocks sum to A_v
+    for (int64_t k = vptr[v]; k < vptr[v + 1]; ++k) {
+      const int64_t c = vcell[k] >> 3;
+      int inside = 0;
+      for (int a = 0; a < nu; ++a) inside += stamp[cu[c * nu + a]] == v;
+      if (inside != nk) return false;
+    }
+    int col = 0;
+    while (col < kPatchMaxColours && ((used >> col) & 1u)) ++col;
+    if (col >= kPatchMaxColours) return false;
+    colour[v] = int8_t(col);
+    n_colours = std::max(n_colours, col + 1);
+  }
+  // the patch of the lowest colour among those that hold a node applies a d there
+  std::vector<int8_t> minc(static_cast<size_t>(nU), static_cast<int8_t>(kPatchMaxColours));
+  for (int64_t v = 0; v < nV; ++v)
+    for (int64_t k = nptr[v]; k < nptr[v + 1]; ++k) minc[pn[k]] = std::min(minc[pn[k]], colour[v]);
+  for (int64_t n = 0; n < nU; ++n)
+    if (minc[n] >= kPatchMaxColours) return false; // a node no patch covers
+  // sorted by (colour, nodes)
+  std::vector<int32_t> order(static_cast<size_t>(nV));
+  for (int64_t v = 0; v < nV; ++v) order[v] = int32_t(v);
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+    if (colour[x] != colour[y]) return colour[x] < colour[y];
+    return nptr[x + 1] - nptr[x] < nptr[y + 1] - nptr[y];
+  });
+  std::vector<int64_t> node_ptr(size_t(nV) + 1, 0), cell_ptr(size_t(nV) + 1, 0), inv_off(static_cast<size_t>(nV), 0);
+  std::vector<int32_t> nodes(pn.size()), cells(vcell.size());
+  int64_t floats = 0;
+  for (int c = 0; c <= kPatchMaxColours; ++c) S.gen_col_ptr[c] = 0;
+  for (int64_t k = 0; k < nV; ++k) {
+    const int64_t v = order[k], nn = nptr[v + 1] - nptr[v], ncl = vptr[v + 1] - vptr[v];
+    for (int64_t i = 0; i < nn; ++i) {
+      const int32_t node = pn[nptr[v] + i];
+      nodes[node_ptr[k] + i] = minc[node] == colour[v] ? int32_t(uint32_t(node) | 0x80000000u) : node;
+    }
+    std::memcpy(&cells[cell_ptr[k]], &vcell[vptr[v]], size_t(ncl) * sizeof(int32_t));
+    node_ptr[k + 1] = node_ptr[k] + nn;
+    cell_ptr[k + 1] = cell_ptr[k] + ncl;
+    inv_off[k] = floats;
+    floats += (nn * dim) * (nn * dim);
+    S.gen_col_ptr[colour[v] + 1] = k + 1;
+  }
+  for (int c = 1; c <= kPatchMaxColours; ++c) S.gen_col_ptr[c] = std::max(S.gen_col_ptr[c], S.gen_col_ptr[c - 1]);
+  S.gen_node_ptr.upload(node_ptr.data(), node_ptr.size(), s);
+  S.gen_cell_ptr.upload(cell_ptr.data(), cell_ptr.size(), s);
+  S.gen_inv_off.upload(inv_off.data(), inv_off.size(), s);
+  S.gen_nodes.upload(nodes.data(), nodes.size(), s);
+  S.gen_cells.upload(cells.data(), cells.size(), s);
+  S.gen_bad.alloc(1);
+  IFEM_HIP_CHECK(hipStreamSynchronize(s)); // (the host arrays leave scope)
+  S.gen_colours = n_colours;
+  S.gen_entries = int64_t(pn.size());
+  S.gen_inv_floats = floats;
+  S.gen_state = 1;
+  return true;
+}
+
+// inverses of the general form for the level's operator state.  false: the level keeps its node blocks (a cap, the memory, a pivot)
+static bool patch_gen_setup(ifem_ctx *ctx, const double key[9]) {
+  PatchSmoother &S = ctx->patch;
+  if (S.gen_rejected && std::memcmp(key, S.gen_rejected_key, sizeof(S.gen_rejected_key)) == 0) return false;
+  if (!patch_gen_topology(ctx)) return false;
+  hipStream_t s = ctx->stream;
+  const int dim = ctx->dim, cs = ctx->asm_constraint_set;
+  const int64_t nV = ctx->nPl;
+  auto refuse = [&] {
+    S.gen_rejected = true;
+    std::memcpy(S.gen_rejected_key, key, sizeof(S.gen_rejected_key));
+    return false;
+  };
+  if (S.form != 1 || (int64_t)S.inv.n != S.gen_inv_floats) { // the store of the other form, or none yet: does this one fit?
+    S.inv.release();
+    size_t fr = 0, tot = 0;
+    IFEM_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if (double(S.gen_inv_floats) * sizeof(float) + double(256u << 20) > double(fr)) return refuse();
+    S.inv.alloc(size_t(S.gen_inv_floats), "the inverse store of the vertex-patch smoother");
+    S.tab.release(); S.work.release();
+  }
+  S.form = 1;
+  PatchGenArgs a{};
+  a.node_ptr = S.gen_node_ptr.p; a.cell_ptr = S.gen_cell_ptr.p; a.inv_off = S.gen_inv_off.p;
+  a.nodes = S.gen_nodes.p; a.cells = S.gen_cells.p;
+  a.vcoords = ctx->vcoords.p; a.cell_unodes = ctx->cell_unodes.p;
+  a.is_c = ctx->has_c[cs] ? ctx->is_c[cs].p : nullptr;
+  a.inv = S.inv.p; a.bad = S.gen_bad.p;
+  a.mu = ctx->mf_params.viscosity; a.rho = ctx->mf_params.rho; a.gamma = ctx->mf_params.grad_div; a.inv_dt = 1.0 / ctx->mf_params.dt;
+  tab1d(a.t, ctx->kv);
+  int32_t bad = 0;
+  {
+    const double N = dim * (dim == 3 ? 27.0 : 9.0); // a typical patch: integration of its cells + N^3 of the sweeps
+    KScope ks(ctx, IFEM_KC_SMOOTHER_SETUP, double(S.gen_inv_floats) * sizeof(float) + double(S.gen_cells.n) * (4.0 + 8.0 * ctx->np * dim + 4.0 * ctx->nu),
+              double(nV) * N * N * N);
+    IFEM_HIP_CHECK(hipMemsetAsync(S.gen_bad.p, 0, sizeof(int32_t), s));
+    if (dim == 3) hipLaunchKernelGGL((k_patch_gen_setup<3>), dim3(unsigned(nV)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_patch_gen_setup<2>), dim3(unsigned(nV)), dim3(256), 0, s, a);
+    IFEM_HIP_CHECK(hipGetLastError());
+    IFEM_HIP_CHECK(hipMemcpyAsync(&bad, S.gen_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (bad) return refuse(); // a patch matrix that is not positive definite
+  S.n_patches = nV;
+  S.n_types = 0;
+  S.inv_bytes = S.gen_inv_floats * int64_t(sizeof(float));
+  std::memcpy(S.key, key, sizeof(S.key));
+  S.valid = true;
+  return true;
+}
+
+static void patch_gen_apply(ifem_ctx *ctx, double a, double b, const float *r, float *d) {
+  const PatchSmoother &S = ctx->patch;
+  const int dim = ctx->dim;
+  // every patch streams its inverse once; its node list; the gathered residual and the read-modify-write of d.  2 N_v^2 flops per patch
+  KScope ks(ctx, IFEM_KC_VECTOR, double(S.inv_bytes) + double(S.gen_entries) * (4.0 + 12.0 * dim) + double(S.n_patches) * 24.0, 2.0 * double(S.gen_inv_floats));
+  for (int c = 0; c < S.gen_colours; ++c) {
+    const int64_t p0 = S.gen_col_ptr[c], cnt = S.gen_col_ptr[c + 1] - p0;
+    if (cnt <= 0) continue;
+    if (dim == 3)
+      hipLaunchKernelGGL((k_patch_gen_apply<3>), dim3(unsigned((cnt + GenDims<3>::PPB - 1) / GenDims<3>::PPB)), dim3(256), 0, ctx->stream, S.gen_node_ptr.p,
+                         S.gen_nodes.p, S.gen_inv_off.p, S.inv.p, p0, cnt, float(a), float(b), r, d);
+    else
+      hipLaunchKernelGGL((k_patch_gen_apply<2>), dim3(unsigned((cnt + GenDims<2>::PPB - 1) / GenDims<2>::PPB)), dim3(256), 0, ctx->stream, S.gen_node_ptr.p,
+                         S.gen_nodes.p, S.gen_inv_off.p, S.inv.p, p0, cnt, float(a), float(b), r, d);
   }
   IFEM_HIP_CHECK(hipGetLastError());
 }

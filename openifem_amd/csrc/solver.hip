@@ -641,6 +641,7 @@ static void uu_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) key_f64(key, hd); // which cell kernels, and their constants
   key_ptr(key, lc->bjac.p); key_ptr(key, lc->vcoords.p); key_ptr(key, lc->cell_unodes.p); key_ptr(key, lc->uinc.col.p);
   key.push_back(uint64_t(smoother_kind(lc))); key_ptr(key, lc->patch.tab.p); key_ptr(key, lc->patch.inv.p); key_ptr(key, lc->patch.work.p); // the level's smoother and its tables
+  key.push_back(uint64_t(lc->patch.form)); key_ptr(key, lc->patch.gen_nodes.p); key_ptr(key, lc->patch.gen_node_ptr.p); key_ptr(key, lc->patch.gen_inv_off.p); key.push_back(uint64_t(lc->patch.gen_colours)); // (the per-patch form)
   key_f64(key, lc->uu_lmax()); key_f64(key, lc->mf_params.viscosity); key_f64(key, lc->mf_params.rho); key_f64(key, lc->mf_params.grad_div); key_f64(key, lc->mf_params.dt);
 }
 
