@@ -54,6 +54,33 @@ int ifem_test_uu_vmult_f32col(ifem_ctx *ctx, int dst, int src);
 int ifem_test_uu_patch_vmult(ifem_ctx *ctx, int dst, int src);
 int ifem_test_uu_patch_info(ifem_ctx *ctx, int64_t out[4]);
 
+/* ONE host launcher of the Krylov vector kernels (linalg.hip, as declared in kernels.hpp: the dispatch between the kernels is part of what
+ * runs) on host data: device scratch, upload, the call, a stream synchronisation, download.  Needs a created context only (single rank; all_ranks
+ * is passed as the solvers pass it and is the identity there).  n entries per vector, columns ld >= n entries apart; w: n doubles.
+ *   IFEM_TVK_MDOT            out[i] = <V_i, w>, i < k                          V: k double columns
+ *   IFEM_TVK_MDOT_SELF       out[0] = <w, w> through the aliased call v_mdot(n, 1, w, n, w)
+ *   IFEM_TVK_MAXPY[_NORM]    w -= sum_i coef[i] V_i  [out[0] = ||w||^2 of the result]   V: k double columns
+ *   IFEM_TVK_MDOT_F32        as MDOT                                            V: pad4(k) float columns, pad4(k) = (k + 3) & ~3
+ *   IFEM_TVK_MAXPY_F32[_NORM]  as MAXPY[_NORM]                                  V: pad4(k) float columns
+ *   IFEM_TVK_SCALE_STORE_F32 V (n floats) = float(coef[0] * w)
+ *   IFEM_TVK_AXPY            w += coef[0] V_0                                   V: one double column
+ *   IFEM_TVK_AXPBY           w = coef[0] V_0 + coef[1] w                        V: one double column
+ *   IFEM_TVK_SCALE_TO2       V_0 = V_1 = coef[0] w                              V: two double columns (output)
+ *   IFEM_TVK_DIV             w = w ./ V_0 (a zero divisor counts as 1)          V: one double column
+ *   IFEM_TVK_MINMAX          out[0] = min w, out[1] = max w
+ * Arguments an op does not use may be NULL. */
+enum {
+  IFEM_TVK_MDOT = 0, IFEM_TVK_MDOT_SELF, IFEM_TVK_MAXPY, IFEM_TVK_MAXPY_NORM, IFEM_TVK_MDOT_F32, IFEM_TVK_MAXPY_F32, IFEM_TVK_MAXPY_F32_NORM,
+  IFEM_TVK_SCALE_STORE_F32, IFEM_TVK_AXPY, IFEM_TVK_AXPBY, IFEM_TVK_SCALE_TO2, IFEM_TVK_DIV, IFEM_TVK_MINMAX, IFEM_TVK_COUNT
+};
+int ifem_test_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int k, int64_t ld, void *V, const double *coef, double *w, double *out);
+
+/* The device-resident CG of the pressure solves (solver.hip::cg_device; ifem_tuning::cg_single_reduction selects the form, as in production) on
+ * A = diag(a) (applied through vec_mul), zero initial guess: x (n doubles, host) = the iterate after exactly `iters` iterations (tolerance 0, the
+ * residual read every iteration, the work vector of the single-reduction form present).  jac (may be NULL): the Jacobi diagonal; a zero entry
+ * counts as 1.  Single rank, a created context only. */
+int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,7 +140,11 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_get_constraints", "ifem_fsi_fluid_at_points", "ifem_comm_stats_get", "ifem_comm_stats_level", "ifem_true_residual", "ifem_tpp_ilu_probe", "ifem_tpp_override", "ifem_scns_pc_probe", "ifem_test_restart_fits",
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
-           "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info"]
+           "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device"]
+
+# ops of ifem_test_vec_kernel (IFEM_TVK_*)
+(TVK_MDOT, TVK_MDOT_SELF, TVK_MAXPY, TVK_MAXPY_NORM, TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32, TVK_AXPY,
+ TVK_AXPBY, TVK_SCALE_TO2, TVK_DIV, TVK_MINMAX) = range(13)
 
 # ifem_abi_sizeof(which): the ctypes mirror of every struct of the header
 ABI_STRUCTS = None  # filled below (needs every class defined)
@@ -229,6 +233,8 @@ def load():
     L.ifem_test_uu_vmult_f32col.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_vmult.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_info.argtypes = [C.c_void_p, C.c_void_p]
+    L.ifem_test_vec_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_test_cg_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -553,6 +559,23 @@ class Context:
         self.vec_set(VEC_TMP, x)
         self._chk(self.L.ifem_test_uu_patch_vmult(self.h, VEC_UPDATE, VEC_TMP))
         return self.vec_get(VEC_UPDATE)
+
+    def test_vec_kernel(self, op, n, k, ld, V=None, coef=None, w=None, out=None):
+        """one host launcher of the Krylov vector kernels on host arrays (C-contiguous; V float32 for the _F32 ops, everything else float64);
+        w, V and out are updated in place as the op says -- ifem_test_vec_kernel"""
+        for a, t in ((V, np.float32 if op in (TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32) else np.float64),
+                     (coef, np.float64), (w, np.float64), (out, np.float64)):
+            assert a is None or (a.dtype == t and a.flags.c_contiguous)
+        self._chk(self.L.ifem_test_vec_kernel(self.h, op, n, k, ld, _ptr(V), _ptr(coef), _ptr(w), _ptr(out)))
+
+    def test_cg_device(self, a, jac, b, iters):
+        """the iterate of solver.hip::cg_device on diag(a) x = b after exactly `iters` iterations (jac: Jacobi diagonal or None) --
+        ifem_test_cg_device"""
+        a, b = np.ascontiguousarray(a, float), np.ascontiguousarray(b, float)
+        jac = None if jac is None else np.ascontiguousarray(jac, float)
+        x = np.zeros(len(a))
+        self._chk(self.L.ifem_test_cg_device(self.h, len(a), _ptr(a), _ptr(jac), _ptr(b), iters, _ptr(x)))
+        return x
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

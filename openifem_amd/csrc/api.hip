@@ -860,6 +860,68 @@ int ifem_test_uu_patch_info(ifem_ctx *ctx, int64_t out[4]) {
   IFEM_API_END
 }
 
+int ifem_test_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int k, int64_t ld, void *V, const double *coef, double *w, double *out) {
+  IFEM_API_BEGIN
+  if (op < 0 || op >= IFEM_TVK_COUNT || n < 0 || k < 0 || ld < n) throw Error(IFEM_E_BADPARAM, "ifem_test_vec_kernel: op, n >= 0, k >= 0, ld >= n");
+  if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_vec_kernel: single-rank contexts");
+  const bool f32 = op == IFEM_TVK_MDOT_F32 || op == IFEM_TVK_MAXPY_F32 || op == IFEM_TVK_MAXPY_F32_NORM || op == IFEM_TVK_SCALE_STORE_F32;
+  const bool multi = op == IFEM_TVK_MDOT || op == IFEM_TVK_MAXPY || op == IFEM_TVK_MAXPY_NORM;
+  const bool multi32 = op == IFEM_TVK_MDOT_F32 || op == IFEM_TVK_MAXPY_F32 || op == IFEM_TVK_MAXPY_F32_NORM;
+  const bool v_out = op == IFEM_TVK_SCALE_STORE_F32 || op == IFEM_TVK_SCALE_TO2; // V is written, not read
+  const bool w_out = op == IFEM_TVK_MAXPY || op == IFEM_TVK_MAXPY_NORM || op == IFEM_TVK_MAXPY_F32 || op == IFEM_TVK_MAXPY_F32_NORM ||
+                     op == IFEM_TVK_AXPY || op == IFEM_TVK_AXPBY || op == IFEM_TVK_DIV;
+  const int64_t ncols = multi ? k : multi32 ? ((k + 3) & ~3) : op == IFEM_TVK_SCALE_TO2 ? 2 : (op == IFEM_TVK_MDOT_SELF || op == IFEM_TVK_MINMAX) ? 0 : 1;
+  const bool maxpy = op == IFEM_TVK_MAXPY || op == IFEM_TVK_MAXPY_NORM || op == IFEM_TVK_MAXPY_F32 || op == IFEM_TVK_MAXPY_F32_NORM;
+  const bool scalars = op == IFEM_TVK_MDOT || op == IFEM_TVK_MDOT_SELF || op == IFEM_TVK_MDOT_F32 || op == IFEM_TVK_MAXPY_NORM ||
+                       op == IFEM_TVK_MAXPY_F32_NORM || op == IFEM_TVK_MINMAX;
+  const size_t nV = size_t(ld) * size_t(ncols);
+  if ((op == IFEM_TVK_MDOT || op == IFEM_TVK_MDOT_F32) && k < 1) throw Error(IFEM_E_BADPARAM, "ifem_test_vec_kernel: a multi-dot of at least one column");
+  if ((n > 0 && !w) || (nV && !V) || (scalars && !out) || (maxpy && k > 0 && !coef) ||
+      ((op == IFEM_TVK_SCALE_STORE_F32 || op == IFEM_TVK_AXPY || op == IFEM_TVK_AXPBY || op == IFEM_TVK_SCALE_TO2) && !coef))
+    throw Error(IFEM_E_BADPARAM, "ifem_test_vec_kernel: a null array this op uses");
+  hipStream_t s = ctx->stream;
+  DBuf<double> dV, dw, dy;
+  DBuf<float> dVf;
+  if (f32) dVf.alloc(nV); else dV.alloc(nV);
+  dw.alloc((size_t)n);
+  if (nV && !v_out) IFEM_HIP_CHECK(hipMemcpyAsync(f32 ? (void *)dVf.p : (void *)dV.p, V, nV * (f32 ? sizeof(float) : sizeof(double)), hipMemcpyHostToDevice, s));
+  if (nV && v_out) IFEM_HIP_CHECK(hipMemsetAsync(f32 ? (void *)dVf.p : (void *)dV.p, 0xff, nV * (f32 ? sizeof(float) : sizeof(double)), s)); // NaN: an entry left out shows
+  if (n) IFEM_HIP_CHECK(hipMemcpyAsync(dw.p, w, size_t(n) * sizeof(double), hipMemcpyHostToDevice, s));
+  const bool all_ranks = true; // as the Krylov solvers pass it: the identity on one rank
+  switch (op) {
+  case IFEM_TVK_MDOT: v_mdot(ctx, n, k, dV.p, ld, dw.p, out, all_ranks); break;
+  case IFEM_TVK_MDOT_SELF: v_mdot(ctx, n, 1, dw.p, n, dw.p, out, all_ranks); break;
+  case IFEM_TVK_MAXPY: v_maxpy(ctx, n, k, dV.p, ld, coef, dw.p, nullptr, all_ranks); break;
+  case IFEM_TVK_MAXPY_NORM: v_maxpy(ctx, n, k, dV.p, ld, coef, dw.p, out, all_ranks); break;
+  case IFEM_TVK_MDOT_F32: v_mdot_f32(ctx, n, k, dVf.p, ld, dw.p, out); break;
+  case IFEM_TVK_MAXPY_F32: v_maxpy_f32(ctx, n, k, dVf.p, ld, coef, dw.p, nullptr); break;
+  case IFEM_TVK_MAXPY_F32_NORM: v_maxpy_f32(ctx, n, k, dVf.p, ld, coef, dw.p, out); break;
+  case IFEM_TVK_SCALE_STORE_F32: v_scale_store_f32(ctx, n, coef[0], dw.p, dVf.p); break;
+  case IFEM_TVK_AXPY: v_axpy(ctx, n, coef[0], dV.p, dw.p); break;
+  case IFEM_TVK_AXPBY: v_axpby(ctx, n, coef[0], dV.p, coef[1], dw.p); break;
+  case IFEM_TVK_SCALE_TO2: v_scale_to2(ctx, n, coef[0], dw.p, dV.p, dV.p + ld); break;
+  case IFEM_TVK_DIV:
+    dy.alloc((size_t)n);
+    vec_div(ctx, n, dV.p, dw.p, dy.p);
+    dw.swap(dy);
+    break;
+  default: v_minmax(ctx, n, dw.p, &out[0], &out[1]); break;
+  }
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  if (n && w_out) IFEM_HIP_CHECK(hipMemcpyAsync(w, dw.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (nV && v_out) IFEM_HIP_CHECK(hipMemcpyAsync(V, f32 ? (void *)dVf.p : (void *)dV.p, nV * (f32 ? sizeof(float) : sizeof(double)), hipMemcpyDeviceToHost, s));
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  IFEM_API_END
+}
+
+int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x) {
+  IFEM_API_BEGIN
+  if (n <= 0 || iters < 0 || !a || !b || !x) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: n > 0, iters >= 0, a, b and x");
+  if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: single-rank contexts");
+  test_cg_device(ctx, n, a, jac, b, iters, x);
+  IFEM_API_END
+}
+
 int ifem_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int dst, int src) {
   IFEM_API_BEGIN
   if (!vec_ok(dst) || !vec_ok(src) || is_ext(dst) || is_ext(src)) throw Error(IFEM_E_BADPARAM, "use non-ghosted vectors");

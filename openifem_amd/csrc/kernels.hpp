@@ -155,6 +155,8 @@ void cg1_init(ifem_ctx *ctx, int64_t n, const double *b, const double *diag, dou
 void cg1_dots(ifem_ctx *ctx, int64_t n, const double *r, const double *u, const double *w, bool first);
 void cg1_update(ifem_ctx *ctx, int64_t n, const double *diag, double *u, const double *w, double *p, double *s, double *x, double *r);
 void v_minmax(ifem_ctx *ctx, int64_t n, const double *x, double *mn, double *mx);
+// test aid (ifem_test_cg_device): solver.hip::cg_device on A = diag(a), host arrays in and out, exactly `iters` iterations
+void test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x);
 // x[dof] = value for constrained dofs (AffineConstraints::distribute, Dirichlet lines)
 void apply_constraints(ifem_ctx *ctx, int which, double *x);
 void spmv_planar_scalar(ifem_ctx *ctx, const PlanarCsr &M, const double *val, const double *xp, double *yp);

@@ -1125,8 +1125,13 @@ void v_mdot_f32(ifem_ctx *ctx, int64_t n, int k, const float *V, int64_t ld, con
 
 // w -= sum_{i<k} h[i] V_i; when norm2_out != nullptr also returns ||w||^2 of the result (local, not all-reduced)
 void v_maxpy_f32(ifem_ctx *ctx, int64_t n, int k, const float *V, int64_t ld, const double *h_host, double *w, double *norm2_out) {
-  if (n == 0 || k == 0) { if (norm2_out) *norm2_out = 0; return; }
+  if (n == 0) { if (norm2_out) *norm2_out = 0; return; }
+  if (k == 0) { // nothing to subtract: the plain norm, as v_maxpy
+    if (norm2_out) v_mdot(ctx, n, 1, w, n, w, norm2_out);
+    return;
+  }
   if (pad4(k) > 64) throw Error(IFEM_E_BADPARAM, "single-precision basis: at most 64 vectors");
+  if (norm2_out && ctx->partials.n == 0) ctx->partials.alloc(size_t(64) * MDOT_MAXB); // (a first call with the norm finds no partials yet)
   hipStream_t s = ctx->stream;
   const int kp = pad4(k);
   for (int i = 0; i < kp; ++i) ctx->h_scal[64 + i] = i < k ? h_host[i] : 0.0;

@@ -363,6 +363,26 @@ static int cg_device(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag
   return it;
 }
 
+// test aid (ifem_test_cg_device): cg_device as the pressure solves call it -- the s work vector present, the form chosen by
+// ifem_tuning::cg_single_reduction -- on A = diag(a), host data in and out; tol = 0 and chk = 1: exactly `iters` iterations
+void test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x) {
+  hipStream_t s = ctx->stream;
+  DBuf<double> da, dj, db, dx, w[5];
+  auto up = [&](DBuf<double> &d, const double *h) {
+    d.alloc((size_t)n);
+    IFEM_HIP_CHECK(hipMemcpyAsync(d.p, h, size_t(n) * sizeof(double), hipMemcpyHostToDevice, s));
+  };
+  up(da, a);
+  up(db, b);
+  if (jac) up(dj, jac);
+  dx.alloc((size_t)n);
+  for (auto &v : w) v.alloc((size_t)n);
+  const OpFn A = [&](const double *in, double *out) { vec_mul(ctx, n, da.p, in, out); };
+  cg_device(ctx, n, A, jac ? dj.p : nullptr, db.p, dx.p, 0.0, iters, w[0].p, w[1].p, w[2].p, w[3].p, 1, w[4].p);
+  IFEM_HIP_CHECK(hipMemcpyAsync(x, dx.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, s));
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // Jacobi-preconditioned CG, zero initial guess, same stopping rule (absolute tolerance on the TRUE residual ||r||_2).
 // r and z must be adjacent (z = r + ld) so that <r,r> and <z,r> come out of one fused reduction.
 static int pcg_jacobi(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag, const double *b, double *x, double tol,
