@@ -75,7 +75,7 @@ enum {
 };
 int ifem_test_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int k, int64_t ld, void *V, const double *coef, double *w, double *out);
 
-/* The device-resident CG of the pressure solves (solver.hip::cg_device; ifem_tuning::cg_single_reduction selects the form, as in production) on
+/* The device-resident CG of the pressure solves (krylov.hip::cg_device; ifem_tuning::cg_single_reduction selects the form, as in production) on
  * A = diag(a) (applied through vec_mul), zero initial guess: x (n doubles, host) = the iterate after exactly `iters` iterations (tolerance 0, the
  * residual read every iteration, the work vector of the single-reduction form present).  jac (may be NULL): the Jacobi diagonal; a zero entry
  * counts as 1.  Single rank, a created context only. */

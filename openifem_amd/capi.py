@@ -569,7 +569,7 @@ class Context:
         self._chk(self.L.ifem_test_vec_kernel(self.h, op, n, k, ld, _ptr(V), _ptr(coef), _ptr(w), _ptr(out)))
 
     def test_cg_device(self, a, jac, b, iters):
-        """the iterate of solver.hip::cg_device on diag(a) x = b after exactly `iters` iterations (jac: Jacobi diagonal or None) --
+        """the iterate of krylov.hip::cg_device on diag(a) x = b after exactly `iters` iterations (jac: Jacobi diagonal or None) --
         ifem_test_cg_device"""
         a, b = np.ascontiguousarray(a, float), np.ascontiguousarray(b, float)
         jac = None if jac is None else np.ascontiguousarray(jac, float)

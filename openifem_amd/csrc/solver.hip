@@ -1,11 +1,11 @@
-// solver.hip -- host drivers of the Krylov path; every vector/matrix operation is a HIP kernel on ctx->stream.
-//   gmres(flexible)     deal.II SolverFGMRES as used by InsIM::solve            (mpi_insim.cpp:379-388)
-//   cg()                PETSc KSPCG + PreconditionNone                          (mpi_insim.cpp:73-82,88-108)
+// solver.hip -- host drivers of the linear solves; every vector/matrix operation is a HIP kernel on ctx->stream.
 //   precond_vmult()     InsIM::BlockSchurPreconditioner::vmult                  (mpi_insim.cpp:57-128): solve_mp(), solve_sm(), ainv_apply()
 //   ins_solve()         InsIM::solve                                            (mpi_insim.cpp:365-395)
+// The Krylov drivers themselves are krylov.hip: gmres(flexible) is deal.II's SolverFGMRES as used by InsIM::solve (mpi_insim.cpp:379-388),
+// cg() PETSc's KSPCG + PreconditionNone (mpi_insim.cpp:73-82,88-108).
 // A~^-1 (MUMPS in the reference, ainv_apply() here) is an inner right-preconditioned GMRES(m): on the BSR A_uu with node-block Jacobi, or
 // (IFEM_AINV_MG, the type MgUu) on the matrix-free A_uu with a multigrid V-cycle; the outer solver is *flexible* GMRES precisely so that
-// such an inexact inner solve is admissible.  The three GMRES drivers share their host arithmetic (Arnoldi).
+// such an inexact inner solve is admissible.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,12 +16,11 @@
 #include <vector>
 #include "ctx.hpp"
 #include "kernels.hpp"
+#include "krylov.hpp"
 
 namespace ifem {
 
-using OpFn = std::function<void(const double *, double *)>;
-using MdotFn = std::function<void(int, const double *, int64_t, const double *, double *)>; // out[i] = <V_i, w>, i < k, columns ld apart
-// ... over the n owned entries, summed over the ranks
+// all-reduced multi-dot over the n owned entries, summed over the ranks
 static MdotFn mdot_over(ifem_ctx *c, int64_t n) {
   return [c, n](int k, const double *V, int64_t ld, const double *w, double *out) { v_mdot(c, n, k, V, ld, w, out, /*all_ranks=*/true); };
 }
@@ -30,392 +29,6 @@ struct Clock {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
-
-// Host arithmetic of one restart cycle, shared by the three GMRES drivers below: the Hessenberg matrix H (row-major, (m+1) x m), the Givens
-// rotations (cs, sn) that keep it triangular, the rotated right-hand side g and the solution y of the small triangular system.
-struct Arnoldi {
-  const int m;
-  std::vector<double> H, cs, sn, g, y;
-  explicit Arnoldi(int m_) : m(m_), H((size_t)(m_ + 1) * m_, 0.0), cs(m_), sn(m_), g(m_ + 1), y(m_) {}
-  void start(double beta) { std::fill(g.begin(), g.end(), 0.0); g[0] = beta; }
-  // column j = (h[0..j], hn): stored, rotated by the earlier rotations, annihilated by a new one; returns the residual estimate |g[j+1]|
-  double column(int j, const double *h, double hn) {
-    for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = h[i];
-    H[(size_t)(j + 1) * m + j] = hn;
-    for (int i = 0; i < j; ++i) {
-      const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-      H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-      H[(size_t)i * m + j] = t;
-    }
-    const double a = H[(size_t)j * m + j], c = H[(size_t)(j + 1) * m + j], r = std::hypot(a, c);
-    cs[j] = a / r; sn[j] = c / r;
-    H[(size_t)j * m + j] = r; H[(size_t)(j + 1) * m + j] = 0;
-    g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
-    return std::fabs(g[j + 1]);
-  }
-  // y[0..j) = H(0..j, 0..j)^-1 g[0..j): back substitution
-  void solve(int j) {
-    for (int i = j - 1; i >= 0; --i) {
-      double t = g[i];
-      for (int k = i + 1; k < j; ++k) t -= H[(size_t)i * m + k] * y[k];
-      y[i] = t / H[(size_t)i * m + i];
-    }
-  }
-};
-
-// LEFT preconditioning of gmres() (not flexible): the Krylov space of P^-1 A, the stopping test reads the PRECONDITIONED residual --
-// deal.II's SolverGMRES with its defaults (mpi_supg_solver.cpp:176-182)
-struct LeftPrecond {
-  double *stage = nullptr;  // every new basis vector is also written here and the operators read IT, so that
-  const OpFn *PA = nullptr; // ... the fused w = P^-1 A stage (a sequence with constant kernel arguments: a hipGraph) can replace the pair
-};
-
-// (flexible) right-preconditioned restarted GMRES, x0 = 0.  V: (m+1) x n, Z: m x n (flexible) or 1 x n.
-// Orthogonalisation: classical Gram-Schmidt with one re-orthogonalisation pass (two fused multi-dot /
-// multi-axpy sweeps instead of deal.II's j+1 sequential dots; same Krylov space, fewer host round trips).
-static int gmres(ifem_ctx *ctx, int64_t n, int64_t ld, bool reorth, const OpFn &A, const OpFn &Pinv, bool flexible,
-                 const double *b, double *x, int m, int maxit, double tol, double *V, double *Z, double *w,
-                 double *res_out,
-                 const MdotFn &mdot,
-                 std::vector<double> *history = nullptr, // residual norm after every iteration (verbose runs)
-                 const std::function<void(int, double *&, double *&)> *ensure = nullptr, // bases that grow with the iteration count: called
-                                                                                        // with the V columns the next iteration needs
-                 const LeftPrecond *left_pc = nullptr) {
-  const bool left = left_pc != nullptr;
-  double *stage = left ? left_pc->stage : nullptr;
-  const OpFn *PA = left ? left_pc->PA : nullptr;
-  Arnoldi K(m);
-  std::vector<double> h(m + 1), h2(m + 1);
-  v_zero(ctx, n, x);
-  int it = 0;
-  double res = 0;
-  bool first = true;
-  while (true) {
-    const double *r0 = w; // the residual the cycle starts from: b itself in the first cycle (x = 0), b - A x after a restart
-    if (first) { r0 = b; first = false; }
-    else { A(x, w); v_axpby(ctx, n, 1.0, b, -1.0, w); }
-    if (left) { Pinv(r0, Z); r0 = Z; }
-    double bb;
-    mdot(1, r0, n, r0, &bb);
-    const double beta = std::sqrt(bb);
-    res = beta;
-    if (res <= tol || it >= maxit || !std::isfinite(res)) break; // (deal.II's SolverControl::check fails on a NaN as well)
-    if (left && stage) v_scale_to2(ctx, n, 1.0 / beta, r0, V, stage);
-    else v_scale_to(ctx, n, 1.0 / beta, r0, V);
-    K.start(beta);
-    int j = 0;
-    bool done = false;
-    for (; j < m && it < maxit; ++j) {
-      if (ensure) (*ensure)(j + 2, V, Z); // columns 0 .. j + 1 of V, 0 .. j of Z
-      double *vj = V + (int64_t)j * ld;
-      double *zj = flexible ? Z + (int64_t)j * ld : Z;
-      if (left && stage && PA) (*PA)(stage, w);
-      else if (left) { A(stage ? stage : vj, zj); Pinv(zj, w); }
-      else { Pinv(vj, zj); A(zj, w); }
-      // classical Gram-Schmidt (twice with reorth); ||w||^2 comes out of the last multi-axpy pass (summed over the ranks like the
-      // dot products of `mdot`): per iteration the host waits for the device once per pass, not three / five times
-      double ww = 0;
-      mdot(j + 1, V, ld, w, h.data());
-      if (reorth) {
-        v_maxpy(ctx, n, j + 1, V, ld, h.data(), w);
-        mdot(j + 1, V, ld, w, h2.data());
-        v_maxpy(ctx, n, j + 1, V, ld, h2.data(), w, &ww, true);
-      } else {
-        v_maxpy(ctx, n, j + 1, V, ld, h.data(), w, &ww, true);
-        std::fill(h2.begin(), h2.end(), 0.0);
-      }
-      for (int i = 0; i <= j; ++i) h[i] += h2[i]; // column j of H: the coefficients of both passes
-      const double hn = std::sqrt(ww);
-      if (hn > 0) {
-        if (left && stage) v_scale_to2(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld, stage);
-        else v_scale_to(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
-      }
-      res = K.column(j, h.data(), hn);
-      ++it;
-      if (history) history->push_back(res);
-      if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
-    }
-    K.solve(j);
-    if (flexible || left) {
-      for (int i = 0; i < j; ++i) h[i] = -K.y[i];
-      v_maxpy(ctx, n, j, left ? V : Z, ld, h.data(), x); // x += sum y_i z_i   (left preconditioning: x += V y)
-    } else {
-      // x += P^-1 (V y): one preconditioner application instead of storing every z_j
-      v_zero(ctx, n, w);
-      for (int i = 0; i < j; ++i) h[i] = -K.y[i];
-      v_maxpy(ctx, n, j, V, ld, h.data(), w);
-      Pinv(w, Z);
-      v_axpy(ctx, n, 1.0, Z, x);
-    }
-    if (done || it >= maxit) break;
-  }
-  if (res_out) *res_out = res;
-  return it;
-}
-
-// Krylov bases of the flexible solvers grow with the iteration count instead of being sized for the restart length: FGMRES(30) at
-// 128^3 would hold 61 vectors of 425 MB where the bench's solves use 2 to 14.  Contents are kept; new columns are zero.
-// max_cols: the most columns the solver can ever ask for (restart length + 1): growth never goes beyond it (rounded up to the
-// multiple of 4 the fused kernels read), so FGMRES(30) ends at 32 columns, not at 36
-template <typename T>
-static void grow_basis(ifem_ctx *c, DBuf<T> &B, int64_t ld, int64_t cols, int64_t max_cols) {
-  const int64_t have = ld > 0 ? int64_t(B.n) / ld : 0;
-  if (have >= cols || ld <= 0) return;
-  const int64_t cap = std::max<int64_t>((std::max(max_cols, cols) + 3) / 4 * 4, cols);
-  const int64_t want = std::min(cap, std::max<int64_t>((cols + 7) / 8 * 8, have + have / 2));
-  DBuf<T> nb;
-  nb.alloc(size_t(want) * size_t(ld));
-  if (have > 0) IFEM_HIP_CHECK(hipMemcpyAsync(nb.p, B.p, size_t(have) * size_t(ld) * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  IFEM_HIP_CHECK(hipMemsetAsync(nb.p + size_t(have) * size_t(ld), 0, size_t(want - have) * size_t(ld) * sizeof(T), c->stream));
-  IFEM_HIP_CHECK(hipStreamSynchronize(c->stream));
-  B.swap(nb);
-}
-// the callback gmres() gets for the pair (V: up to max_v columns, Z: up to max_v - 1)
-template <typename T>
-static std::function<void(int, T *&, T *&)> basis_grower(ifem_ctx *c, DBuf<T> &Vb, DBuf<T> &Zb, int64_t ld, int max_v) {
-  return [c, &Vb, &Zb, ld, max_v](int cols, T *&V, T *&Z) {
-    grow_basis(c, Vb, ld, std::min(cols, max_v), max_v);
-    grow_basis(c, Zb, ld, std::min(cols - 1, max_v - 1), max_v - 1);
-    V = Vb.p; Z = Zb.p;
-  };
-}
-constexpr int kBasisStart = 8; // columns a basis starts with
-
-// Inner solver of the preconditioner: right-preconditioned restarted GMRES, x0 = 0, Krylov basis stored in single
-// precision (half the Gram-Schmidt traffic; everything else fp64), single-pass classical Gram-Schmidt with the norm of
-// the orthogonalised vector fused into the multi-axpy sweep.  Only used where an approximate A^-1 is admissible.
-using OpF32 = std::function<void(const float *, double *)>;
-static int gmres_f32basis(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32 &Pinv, const double *b, double *x,
-                          int m, int maxit, double tol, float *V, double *z, double *w, double *res_out,
-                          const std::function<void(double *, int)> &allreduce) {
-  Arnoldi K(m);
-  std::vector<double> h(m + 4);
-  v_zero(ctx, n, x);
-  int it = 0;
-  double res = 0;
-  bool first = true;
-  while (true) {
-    if (first) { v_copy(ctx, n, b, w); first = false; }
-    else { A(x, w); v_axpby(ctx, n, 1.0, b, -1.0, w); }
-    double bb = v_dot(ctx, n, w, w);
-    allreduce(&bb, 1);
-    const double beta = std::sqrt(bb);
-    res = beta;
-    if (res <= tol || it >= maxit || !std::isfinite(res)) break;
-    v_scale_store_f32(ctx, n, 1.0 / beta, w, V);
-    K.start(beta);
-    int j = 0;
-    bool done = false;
-    for (; j < m && it < maxit; ++j) {
-      Pinv(V + (int64_t)j * ld, z);
-      A(z, w);
-      v_mdot_f32(ctx, n, j + 1, V, ld, w, h.data());
-      allreduce(h.data(), j + 1);
-      double ww;
-      v_maxpy_f32(ctx, n, j + 1, V, ld, h.data(), w, &ww);
-      allreduce(&ww, 1);
-      const double hn = std::sqrt(ww);
-      if (hn > 0) v_scale_store_f32(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
-      res = K.column(j, h.data(), hn);
-      ++it;
-      if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
-    }
-    K.solve(j);
-    // x += P^-1 (V y): round V y to the basis precision (column m+1 of the basis is free at this point)
-    v_zero(ctx, n, w);
-    for (int i = 0; i < j; ++i) h[i] = -K.y[i];
-    v_maxpy_f32(ctx, n, j, V, ld, h.data(), w, nullptr);
-    float *vy = V + (int64_t)(m + 1) * ld;
-    v_scale_store_f32(ctx, n, 1.0, w, vy);
-    Pinv(vy, z);
-    v_axpy(ctx, n, 1.0, z, x);
-    if (done || it >= maxit) break;
-  }
-  if (res_out) *res_out = res;
-  return it;
-}
-
-// Flexible inner solver of IFEM_AINV_MG (ifem_tuning::inner_f32): right-preconditioned restarted FGMRES, x0 = 0, with BOTH bases in single
-// precision -- the preconditioner (a single-precision V-cycle) reads column j of V and writes column j of Z, the operator (single-precision
-// cell arithmetic) reads that Z column and writes the fp64 w.  w, b, x, the Hessenberg arithmetic, the stopping test and the restart residual
-// b - A x are fp64; Gram-Schmidt is the single fused pass of gmres(reorth = false).  Same iteration as gmres(flexible = true) up to the rounding
-// of the stored columns.  The fused kernels take at most 64 columns per call: longer bases (the self-lengthening restart) go in chunks.
-using OpF32F32 = std::function<void(const float *, float *)>;
-static int fgmres_f32(ifem_ctx *ctx, int64_t n, int64_t ld, const OpFn &A, const OpF32 &Af, const OpF32F32 &Pinv, const double *b, double *x,
-                      int m, int maxit, double tol, float *V, float *Z, double *w, double *res_out,
-                      const std::function<void(double *, int)> &allreduce, const std::function<void(int, float *&, float *&)> &ensure) {
-  Arnoldi K(m);
-  std::vector<double> h(m + 4);
-  constexpr int kChunk = 64;
-  auto mdot = [&](int k, const float *B, double *out) {
-    for (int k0 = 0; k0 < k; k0 += kChunk) v_mdot_f32(ctx, n, std::min(kChunk, k - k0), B + int64_t(k0) * ld, ld, w, out + k0);
-    allreduce(out, k);
-  };
-  auto maxpy = [&](int k, const float *B, const double *coef, double *dst, double *norm2) { // dst -= sum coef_i B_i
-    for (int k0 = 0; k0 < k; k0 += kChunk) {
-      const bool last = k0 + kChunk >= k;
-      v_maxpy_f32(ctx, n, std::min(kChunk, k - k0), B + int64_t(k0) * ld, ld, coef + k0, dst, last ? norm2 : nullptr);
-    }
-    if (norm2) allreduce(norm2, 1);
-  };
-  v_zero(ctx, n, x);
-  int it = 0;
-  double res = 0;
-  bool first = true;
-  while (true) {
-    const double *r0 = w;
-    if (first) { r0 = b; first = false; }
-    else { A(x, w); v_axpby(ctx, n, 1.0, b, -1.0, w); }
-    double bb = v_dot(ctx, n, r0, r0);
-    allreduce(&bb, 1);
-    const double beta = std::sqrt(bb);
-    res = beta;
-    if (res <= tol || it >= maxit || !std::isfinite(res)) break;
-    v_scale_store_f32(ctx, n, 1.0 / beta, r0, V);
-    K.start(beta);
-    int j = 0;
-    bool done = false;
-    for (; j < m && it < maxit; ++j) {
-      ensure(j + 2, V, Z); // columns 0 .. j + 1 of V, 0 .. j of Z
-      float *zj = Z + (int64_t)j * ld;
-      Pinv(V + (int64_t)j * ld, zj);
-      Af(zj, w);
-      mdot(j + 1, V, h.data());
-      double ww = 0;
-      maxpy(j + 1, V, h.data(), w, &ww);
-      const double hn = std::sqrt(ww);
-      if (hn > 0) v_scale_store_f32(ctx, n, 1.0 / hn, w, V + (int64_t)(j + 1) * ld);
-      res = K.column(j, h.data(), hn);
-      ++it;
-      if (res <= tol || hn == 0 || !std::isfinite(res)) { ++j; done = true; break; }
-    }
-    K.solve(j);
-    for (int i = 0; i < j; ++i) h[i] = -K.y[i];
-    maxpy(j, Z, h.data(), x, nullptr); // x += sum y_i z_i
-    if (done || it >= maxit) break;
-  }
-  if (res_out) *res_out = res;
-  return it;
-}
-
-// plain CG, zero initial guess, absolute tolerance on ||r||_2
-static int cg(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *b, double *x, double tol, int maxit, double *r,
-              double *p, double *q, const std::function<double(const double *, const double *)> &dot) {
-  v_zero(ctx, n, x);
-  v_copy(ctx, n, b, r);
-  v_copy(ctx, n, b, p);
-  double rr = dot(r, r);
-  int it = 0;
-  while (std::sqrt(rr) > tol && it < maxit) {
-    A(p, q);
-    const double al = rr / dot(p, q);
-    v_axpy(ctx, n, al, p, x);
-    v_axpy(ctx, n, -al, q, r);
-    const double rn = dot(r, r);
-    v_axpby(ctx, n, 1.0, r, rn / rr, p);
-    rr = rn;
-    ++it;
-  }
-  return it;
-}
-
-// CG / Jacobi-PCG whose recurrence scalars stay on the device: five launches and no host round trip per iteration; the
-// host reads ||r||^2 every `chk` iterations, so up to chk - 1 iterations run beyond the tolerance (harmless: they only
-// tighten the solve).  Same iterates as cg() / pcg_jacobi() up to that point.  On several ranks the partial sums are
-// all-reduced on the stream (RCCL) between the reduction and the scalar update: still no host round trip per iteration.
-static int cg_device(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag, const double *b, double *x, double tol,
-                     int maxit, double *r, double *z, double *p, double *q, int chk, double *s = nullptr) {
-  if (s && ctx->tune.cg_single_reduction) {
-    // one reduction per iteration (linalg.hip::cg1_*): u = D^-1 r lives in z (or IS r), w = A u in q, s = A p
-    double *u = diag ? z : r, *w = q;
-    cg1_init(ctx, n, b, diag, x, r, u, p, s);
-    A(u, w);
-    cg1_dots(ctx, n, r, u, w, true);
-    int it = 0;
-    double rr = cgd_rr(ctx);
-    while (std::sqrt(rr) > tol && it < maxit) {
-      const int burst = std::min(chk, maxit - it);
-      for (int k = 0; k < burst; ++k) {
-        cg1_update(ctx, n, diag, u, w, p, s, x, r);
-        A(u, w);
-        cg1_dots(ctx, n, r, u, w, false);
-      }
-      it += burst;
-      rr = cgd_rr(ctx);
-      if (!(rr == rr)) break; // NaN guard
-    }
-    return it;
-  }
-  cgd_init(ctx, n, b, diag, x, r, z, p);
-  int it = 0;
-  double rr = cgd_rr(ctx);
-  while (std::sqrt(rr) > tol && it < maxit) {
-    const int burst = std::min(chk, maxit - it);
-    for (int k = 0; k < burst; ++k) {
-      A(p, q);
-      cgd_alpha(ctx, n, p, q);
-      cgd_update(ctx, n, diag, p, q, x, r, z);
-    }
-    it += burst;
-    rr = cgd_rr(ctx);
-    if (!(rr == rr)) break; // NaN guard
-  }
-  return it;
-}
-
-// test aid (ifem_test_cg_device): cg_device as the pressure solves call it -- the s work vector present, the form chosen by
-// ifem_tuning::cg_single_reduction -- on A = diag(a), host data in and out; tol = 0 and chk = 1: exactly `iters` iterations
-void test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x) {
-  hipStream_t s = ctx->stream;
-  DBuf<double> da, dj, db, dx, w[5];
-  auto up = [&](DBuf<double> &d, const double *h) {
-    d.alloc((size_t)n);
-    IFEM_HIP_CHECK(hipMemcpyAsync(d.p, h, size_t(n) * sizeof(double), hipMemcpyHostToDevice, s));
-  };
-  up(da, a);
-  up(db, b);
-  if (jac) up(dj, jac);
-  dx.alloc((size_t)n);
-  for (auto &v : w) v.alloc((size_t)n);
-  const OpFn A = [&](const double *in, double *out) { vec_mul(ctx, n, da.p, in, out); };
-  cg_device(ctx, n, A, jac ? dj.p : nullptr, db.p, dx.p, 0.0, iters, w[0].p, w[1].p, w[2].p, w[3].p, 1, w[4].p);
-  IFEM_HIP_CHECK(hipMemcpyAsync(x, dx.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, s));
-  IFEM_HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// Jacobi-preconditioned CG, zero initial guess, same stopping rule (absolute tolerance on the TRUE residual ||r||_2).
-// r and z must be adjacent (z = r + ld) so that <r,r> and <z,r> come out of one fused reduction.
-static int pcg_jacobi(ifem_ctx *ctx, int64_t n, const OpFn &A, const double *diag, const double *b, double *x, double tol,
-                      int maxit, double *r, int64_t ld, double *p, double *q,
-                      const MdotFn &mdot) {
-  double *z = r + ld;
-  v_zero(ctx, n, x);
-  v_copy(ctx, n, b, r);
-  vec_div(ctx, n, diag, r, z);
-  v_copy(ctx, n, z, p);
-  double d2[2];
-  mdot(2, r, ld, r, d2);
-  double rr = d2[0], rz = d2[1];
-  int it = 0;
-  while (std::sqrt(rr) > tol && it < maxit) {
-    A(p, q);
-    double pq;
-    mdot(1, p, n, q, &pq);
-    const double al = rz / pq;
-    v_axpy(ctx, n, al, p, x);
-    v_axpy(ctx, n, -al, q, r);
-    vec_div(ctx, n, diag, r, z);
-    mdot(2, r, ld, r, d2);
-    v_axpby(ctx, n, 1.0, z, d2[1] / rz, p);
-    rr = d2[0]; rz = d2[1];
-    ++it;
-  }
-  return it;
-}
-
-// leading dimension of a Krylov basis: a multiple of 64 doubles plus an odd number of 256-byte lines, so that the
-// K+1 streams of a fused multi-dot do not start on the same HBM channel
-static int64_t basis_ld(const ifem_ctx *ctx, int64_t n) { return ((n + 63) / 64) * 64 + ctx->tune.basis_pad; }
 
 struct SolveState {
   ifem_ctx *ctx;
@@ -448,28 +61,32 @@ static void extend_p(SolveState &S, const double *xp, const double **out) {
 // the assembled operator A^ = [A_uu B^T; B A_pp]: ghost-extended input (xu [dim*nUl], xp [nPl]), compact owned output
 static void system_apply_ext(SolveState &S, const double *xu, const double *xp, double *y, bool time_it);
 
+// The halo protocol of an operator on a compact owned vector, written once.  Overlapped (several ranks, comm.hip::halo_start / halo_wait, and
+// the site's own condition `overlap`): `start` copies into the ghost-extended buffer and sends the halo off on the halo stream, op(1) is the
+// part that reads no ghost entry, op(2) the rest once the halo has arrived.  Otherwise `refresh` makes the ghost-extended view (extend_* /
+// halo_exchange*: on one rank the caller's own vector, no copy) and op(0) is the whole operator.
+template <typename Start, typename Refresh, typename Op>
+static void halo_apply(ifem_ctx *c, bool overlap, const Start &start, const Refresh &refresh, const Op &op) {
+  if (overlap && halo_overlap_ok(c)) { start(); op(1); halo_wait(c); op(2); return; }
+  refresh(); op(0);
+}
+
 // the same on a compact owned vector (ghosts refreshed here).  Several ranks: both halos travel on the halo stream while the
-// rows without a ghost column are multiplied (comm.hip::halo_start / halo_wait, PlanarCsr::split_rows)
+// rows without a ghost column are multiplied (PlanarCsr::split_rows)
 static void system_apply_raw(SolveState &S, const double *x, double *y, bool time_it) {
   ifem_ctx *c = S.ctx;
-  if (halo_overlap_ok(c) && !c->has_app && !((S.o->outer_matrix_free || !c->uu_is_stored) && c->mf_valid)) {
-    build_row_split(c, c->Auu, c->nUo, &c->Bt, c->nPo);
-    build_row_split(c, c->B, c->nUo);
-    v_copy(c, S.nuo, x, S.xu_ext);
-    v_copy(c, S.npo, x + S.nuo, S.xp_ext);
-    halo_start(c, S.xu_ext, 0);
-    halo_start(c, S.xp_ext, 1);
-    spmv_uu(c, S.xu_ext, S.xp_ext, y, false, 1);
-    spmv_b(c, S.xu_ext, y + S.nuo, 1);
-    halo_wait(c);
-    spmv_uu(c, S.xu_ext, S.xp_ext, y, false, 2);
-    spmv_b(c, S.xu_ext, y + S.nuo, 2);
-    return;
-  }
-  const double *xu, *xp;
-  extend_u(S, x, &xu);
-  extend_p(S, x + S.nuo, &xp);
-  system_apply_ext(S, xu, xp, y, time_it);
+  const double *xu = S.xu_ext, *xp = S.xp_ext;
+  halo_apply(c, !c->has_app && !((S.o->outer_matrix_free || !c->uu_is_stored) && c->mf_valid),
+    [&] {
+      build_row_split(c, c->Auu, c->nUo, &c->Bt, c->nPo); build_row_split(c, c->B, c->nUo);
+      v_copy(c, S.nuo, x, S.xu_ext); v_copy(c, S.npo, x + S.nuo, S.xp_ext);
+      halo_start(c, S.xu_ext, 0); halo_start(c, S.xp_ext, 1);
+    },
+    [&] { extend_u(S, x, &xu); extend_p(S, x + S.nuo, &xp); },
+    [&](int part) {
+      if (part == 0) { system_apply_ext(S, xu, xp, y, time_it); return; }
+      spmv_uu(c, xu, xp, y, false, part); spmv_b(c, xu, y + S.nuo, part);
+    });
 }
 
 // operator of the outer Krylov solver: A^, or C^T A^ C with the hanging rows replaced by their diagonal (hanging.hip)
@@ -546,16 +163,9 @@ static void sm_apply(SolveState &S, const double *x, double *y, bool lowp) {
   ifem_ctx *c = S.ctx;
   if (sm_is_explicit(S) && c->halo.nranks > 1) {
     v_copy(c, S.npo, x, c->xs_ext.p);
-    if (halo_overlap_ok(c)) { // rows of S_m without a far column while the 2-deep halo travels
-      build_row_split(c, c->Sm, c->nPo);
-      halo_start(c, c->xs_ext.p, 2);
-      spmv_sm(c, c->xs_ext.p, y, lowp, 1);
-      halo_wait(c);
-      spmv_sm(c, c->xs_ext.p, y, lowp, 2);
-      return;
-    }
-    halo_exchange_s(c, c->xs_ext.p);
-    spmv_sm(c, c->xs_ext.p, y, lowp);
+    // (rows of S_m without a far column while the 2-deep halo travels)
+    halo_apply(c, true, [&] { build_row_split(c, c->Sm, c->nPo); halo_start(c, c->xs_ext.p, 2); }, [&] { halo_exchange_s(c, c->xs_ext.p); },
+               [&](int part) { spmv_sm(c, c->xs_ext.p, y, lowp, part); });
     return;
   }
   // the approximate-preconditioner kinds (1, 3) also stream S_m in single precision: it only ever acts inside CG to
@@ -677,6 +287,60 @@ static ifem_ctx *replica_world(ifem_ctx *c) {
   return nullptr;
 }
 
+// a level vector of at least n entries: (re)allocated and zero-filled when it is too short (set-up: never inside a captured cycle)
+template <typename T>
+static void ensure_zeroed(ifem_ctx *c, DBuf<T> &v, int64_t n) {
+  if ((int64_t)v.n >= n) return;
+  v.alloc((size_t)n);
+  IFEM_HIP_CHECK(hipMemsetAsync(v.p, 0, v.n * sizeof(T), c->stream));
+}
+
+// Largest eigenvalue of a smoothed operator B A over n owned entries: power iteration (set-up only: host-synchronised norms), BA(x, y) writes
+// y = B A x.  Cold -- no estimate yet (lmax_prev <= 0) or no stored iterate of this length -- it starts from a fixed rough vector (seed) and
+// runs all `steps`; warm -- the operator was re-formed for another constrained-dof set of the same mesh -- it starts from the previous run's last
+// iterate `eig` and stops once the estimate moves by less than 1 %.  Returns the raw estimate (0 or non-finite ones are the caller's to replace).
+template <typename Op>
+static double estimate_lmax(ifem_ctx *c, int64_t n, int steps, int64_t seed, double lmax_prev, DBuf<double> &eig, double *x, double *y, const Op &BA,
+                            bool *was_warm = nullptr) {
+  const bool warm = lmax_prev > 0 && (int64_t)eig.n == n && n > 0;
+  if (was_warm) *was_warm = warm;
+  if (warm) v_copy(c, n, eig.p, x);
+  else vec_rough(c, n, seed, x);
+  double lam = 0;
+  for (int it = 0; it < steps; ++it) {
+    double nx = v_dot(c, n, x, x);
+    allreduce_sum(c, &nx, 1);
+    if (!(nx > 0)) break;
+    v_scale(c, n, 1.0 / std::sqrt(nx), x);
+    BA(x, y);
+    double ny = v_dot(c, n, y, y);
+    allreduce_sum(c, &ny, 1);
+    const double prev = lam;
+    lam = std::sqrt(ny);
+    v_copy(c, n, y, x);
+    if (warm && it >= 1 && std::fabs(lam - prev) <= 0.01 * lam) break;
+  }
+  if (n > 0) {
+    if ((int64_t)eig.n != n) eig.alloc((size_t)n);
+    v_copy(c, n, x, eig.p);
+  }
+  return lam;
+}
+
+// One Chebyshev sweep of a level's smoother: `steps` steps over the target interval [lo, hi] of B A (mg_sm_sweep, mg_uu_sweep: the one place
+// where each multigrid chooses them), and its recurrence: the first direction is d = c0() B r, step k makes d = a d + b B r with next(a, b).
+struct ChebSweep { double lo, hi; int steps; };
+struct Cheb {
+  double theta, delta, sigma, rho;
+  Cheb(double lo, double hi) : theta(0.5 * (hi + lo)), delta(0.5 * (hi - lo)), sigma(theta / delta), rho(1.0 / sigma) {}
+  explicit Cheb(const ChebSweep &w) : Cheb(w.lo, w.hi) {}
+  double c0() const { return 1.0 / theta; }
+  void next(double &a, double &b) {
+    const double rho_new = 1.0 / (2.0 * sigma - rho);
+    a = rho_new * rho; b = 2.0 * rho_new / delta; rho = rho_new;
+  }
+};
+
 struct MgSm {
   std::vector<SolveState> L; // level 0 = the context being solved
   bool lowp = false;
@@ -699,8 +363,7 @@ static void mg_sm_setup(MgSm &M, int use_nonzero) {
       }
       sm_ensure(S);
     }
-    for (auto &v : c->mg_vec)
-      if ((int64_t)v.n < c->nPl + 8) { v.alloc((size_t)c->nPl + 8); IFEM_HIP_CHECK(hipMemsetAsync(v.p, 0, v.n * sizeof(double), c->stream)); }
+    for (auto &v : c->mg_vec) ensure_zeroed(c, v, c->nPl + 8);
     // S_m in operator form (the finest level of a partition without the 2-deep pressure halo: unstructured strips): the smoother
     // needs its diagonal only, which the rows of B give; "valid" = the diagonal belongs to the present blocks
     const bool opform = !sm_is_explicit(S);
@@ -713,56 +376,37 @@ static void mg_sm_setup(MgSm &M, int use_nonzero) {
     } else
     scalar_diag(c, c->Sm, c->Sm.val.p, c->sm_dinv.p); // owned rows; the diagonal entry has a local column id on every layout
     vec_recip(c, S.npo, c->sm_dinv.p);
-    // largest eigenvalue of D^-1 S_m: power iteration (set-up only: host-synchronised norms) from a fixed rough vector, or --
-    // when S_m was re-formed for another constrained-dof set of the same mesh -- from the previous run's last iterate, then
-    // stopped once the estimate moves by less than 1 %
-    double *x = c->mg_vec[1].p, *y = c->mg_vec[3].p;
-    const bool warm = c->sm_lmax > 0 && (int64_t)c->sm_eig.n == S.npo && S.npo > 0;
-    if (warm) v_copy(c, S.npo, c->sm_eig.p, x);
-    else vec_rough(c, S.npo, int64_t(c->halo.rank) * 1000003, x);
-    double lam = 0;
-    const int n_pow = c->tune.eig_steps > 0 ? c->tune.eig_steps : 14;
-    for (int it = 0; it < n_pow; ++it) {
-      double nx = v_dot(c, S.npo, x, x);
-      allreduce_sum(c, &nx, 1);
-      if (!(nx > 0)) break;
-      v_scale(c, S.npo, 1.0 / std::sqrt(nx), x);
-      sm_apply(S, x, y, false);
-      vec_mul(c, S.npo, c->sm_dinv.p, y, y);
-      double ny = v_dot(c, S.npo, y, y);
-      allreduce_sum(c, &ny, 1);
-      const double prev = lam;
-      lam = std::sqrt(ny);
-      v_copy(c, S.npo, y, x);
-      if (warm && it >= 1 && std::fabs(lam - prev) <= 0.01 * lam) break;
-    }
-    if (S.npo > 0) {
-      if ((int64_t)c->sm_eig.n != S.npo) c->sm_eig.alloc((size_t)S.npo);
-      v_copy(c, S.npo, x, c->sm_eig.p);
-    }
+    // largest eigenvalue of D^-1 S_m (estimate_lmax: 14 steps when cold)
+    double lam = estimate_lmax(c, S.npo, c->tune.eig_steps > 0 ? c->tune.eig_steps : 14, int64_t(c->halo.rank) * 1000003, c->sm_lmax, c->sm_eig, c->mg_vec[1].p,
+                               c->mg_vec[3].p, [&](const double *x, double *y) { sm_apply(S, x, y, false); vec_mul(c, S.npo, c->sm_dinv.p, y, y); });
     if (ifem_ctx *w = replica_world(c)) allreduce_max(w, &lam, 1);
     c->sm_lmax = lam > 0 ? lam : 1.0;
     c->sm_mg_version = c->sm_version;
   }
 }
 
-// nsteps Chebyshev steps on S x = b from the pair (x, r = b - S x); with keep_r the residual is kept up to date on exit
-// (one operator product per step), without it the last product is skipped.  lo / hi: target interval of D^-1 S.
-static void mg_sm_smooth(MgSm &M, size_t l, int nsteps, double lo, double hi, double *x, double *r, bool keep_r) {
+// the sweep of level l over the target interval of D^-1 S_m: the coarsest level's longer polynomial over a wide interval stands in for a direct solve
+static ChebSweep mg_sm_sweep(const MgSm &M, size_t l) {
+  const double hi = 1.1 * M.L[l].ctx->sm_lmax;
+  if (l + 1 == M.L.size()) return {hi / 900.0, hi, 30};
+  return {hi / M.ratio, hi, M.nu};
+}
+// the Chebyshev sweep of level l on S x = b from the pair (x, r = b - S x); with keep_r the residual is kept up to date on exit
+// (one operator product per step), without it the last product is skipped
+static void mg_sm_smooth(MgSm &M, size_t l, double *x, double *r, bool keep_r) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   double *d = c->mg_vec[2].p, *t = c->mg_vec[3].p;
-  const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
-  double rho_old = 1.0 / sigma;
-  cheb_init(c, S.npo, 1.0 / theta, c->sm_dinv.p, r, d);
-  for (int k = 0; k < nsteps; ++k) {
-    const bool last = k == nsteps - 1;
+  const ChebSweep w = mg_sm_sweep(M, l);
+  Cheb ch(w);
+  cheb_init(c, S.npo, ch.c0(), c->sm_dinv.p, r, d);
+  for (int k = 0; k < w.steps; ++k) {
+    const bool last = k == w.steps - 1;
     if (last && !keep_r) { v_axpy(c, S.npo, 1.0, d, x); break; }
     sm_apply(S, d, t, M.lowp);
-    const double rho_new = 1.0 / (2.0 * sigma - rho_old);
+    double a, b; ch.next(a, b);
     // x += d; r -= S d; d = rho_new rho_old d + (2 rho_new / delta) D^-1 r   (the new d is unused after the last step)
-    cheb_step(c, S.npo, rho_new * rho_old, 2.0 * rho_new / delta, c->sm_dinv.p, t, x, r, d);
-    rho_old = rho_new;
+    cheb_step(c, S.npo, a, b, c->sm_dinv.p, t, x, r, d);
   }
 }
 
@@ -771,14 +415,9 @@ static void mg_sm_vcycle(MgSm &M, size_t l) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   double *r = c->mg_vec[0].p, *x = c->mg_vec[1].p;
-  const double hi = 1.1 * c->sm_lmax;
   v_zero(c, S.npo, x);
-  if (l + 1 == M.L.size()) { // coarsest level: a longer polynomial over a wide interval stands in for a direct solve
-    mg_sm_smooth(M, l, 30, hi / 900.0, hi, x, r, false);
-    return;
-  }
-  const double lo = hi / M.ratio;
-  mg_sm_smooth(M, l, M.nu, lo, hi, x, r, true);
+  if (l + 1 == M.L.size()) { mg_sm_smooth(M, l, x, r, false); return; } // coarsest level
+  mg_sm_smooth(M, l, x, r, true);
   // restriction r_c = P^T r: gather per LOCAL coarse node from the owned fine nodes, ghost rows travel to their owners
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
@@ -793,7 +432,7 @@ static void mg_sm_vcycle(MgSm &M, size_t l) {
   sm_apply(S, e, t, M.lowp);
   v_axpy(c, S.npo, 1.0, e, x);
   v_axpy(c, S.npo, -1.0, t, r);
-  mg_sm_smooth(M, l, M.nu, lo, hi, x, r, false);
+  mg_sm_smooth(M, l, x, r, false);
 }
 
 // CG preconditioned by one V-cycle, zero initial guess, absolute tolerance on the true residual ||b - S x||_2 (the
@@ -904,32 +543,16 @@ struct MgUu {
 // processed while the velocity halo travels, the cells of the ghost layer and the node gather after it has arrived
 static void uu_apply_level(SolveState &S, const double *x, double *y, const MfFuse *fuse = nullptr) {
   ifem_ctx *c = S.ctx;
-  if (halo_overlap_ok(c)) {
-    build_mf_cell_split(c);
-    v_copy(c, S.nuo, x, S.xu_ext);
-    halo_start(c, S.xu_ext, 0);
-    apply_uu_mf(c, S.xu_ext, y, true, fuse, 1);
-    halo_wait(c);
-    apply_uu_mf(c, S.xu_ext, y, true, fuse, 2);
-    return;
-  }
-  const double *xe; extend_u(S, x, &xe);
-  apply_uu_mf(c, xe, y, true, fuse);
+  const double *xe = S.xu_ext;
+  halo_apply(c, true, [&] { build_mf_cell_split(c); v_copy(c, S.nuo, x, S.xu_ext); halo_start(c, S.xu_ext, 0); },
+             [&] { extend_u(S, x, &xe); }, [&](int part) { apply_uu_mf(c, xe, y, true, fuse, part); });
 }
 
 // the same on a level vector of the V-cycle (single precision, ghost-extended in place: owned entries first), fused form
 static void uu_apply_level_f32(SolveState &S, float *x_ext, const MfFuseT<float> *fuse) {
   ifem_ctx *c = S.ctx;
-  if (halo_overlap_ok(c)) {
-    build_mf_cell_split(c);
-    halo_start_f32(c, x_ext);
-    apply_uu_mf_f32v(c, x_ext, fuse, 1);
-    halo_wait(c);
-    apply_uu_mf_f32v(c, x_ext, fuse, 2);
-    return;
-  }
-  halo_exchange_f32(c, x_ext);
-  apply_uu_mf_f32v(c, x_ext, fuse);
+  halo_apply(c, true, [&] { build_mf_cell_split(c); halo_start_f32(c, x_ext); }, [&] { halo_exchange_f32(c, x_ext); },
+             [&](int part) { apply_uu_mf_f32v(c, x_ext, fuse, part); });
 }
 
 // the plain product on a compact owned single-precision column (a Z column of fgmres_f32), fp64 result: one rank reads the column in
@@ -938,19 +561,10 @@ static void uu_apply_level_f32(SolveState &S, float *x_ext, const MfFuseT<float>
 void uu_apply_f32col(ifem_ctx *c, const float *z, double *y) {
   if (c->halo.nranks == 1) { apply_uu_mf_f32in(c, z, y); return; }
   const int64_t nuo = int64_t(c->dim) * c->nUo, nv = int64_t(c->dim) * c->nUl + 8;
-  auto &ext = c->mguf_vec[3];
-  if ((int64_t)ext.n < nv) { ext.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(ext.p, 0, ext.n * sizeof(float), c->stream)); }
+  auto &ext = c->mguf_vec[3]; ensure_zeroed(c, ext, nv);
   if (nuo) IFEM_HIP_CHECK(hipMemcpyAsync(ext.p, z, size_t(nuo) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  if (halo_overlap_ok(c)) {
-    build_mf_cell_split(c);
-    halo_start_f32(c, ext.p);
-    apply_uu_mf_f32in(c, ext.p, y, 1);
-    halo_wait(c);
-    apply_uu_mf_f32in(c, ext.p, y, 2);
-    return;
-  }
-  halo_exchange_f32(c, ext.p);
-  apply_uu_mf_f32in(c, ext.p, y);
+  halo_apply(c, true, [&] { build_mf_cell_split(c); halo_start_f32(c, ext.p); }, [&] { halo_exchange_f32(c, ext.p); },
+             [&](int part) { apply_uu_mf_f32in(c, ext.p, y, part); });
 }
 
 // ---- the smoother's B of a level, as the cycle sees it (the kind itself: smoother_kind above).
@@ -994,12 +608,8 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
     SolveState &S = M.L[l];
     ifem_ctx *c = S.ctx;
     const int64_t nv = int64_t(c->dim) * c->nUl + 8;
-    for (int k = 1; k <= 3; ++k) {
-      auto &v = c->mgu_vec[k];
-      if ((int64_t)v.n < nv) { v.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(v.p, 0, v.n * sizeof(double), c->stream)); }
-    }
-    for (auto &v : c->mguf_vec)
-      if ((int64_t)v.n < nv) { v.alloc((size_t)nv); IFEM_HIP_CHECK(hipMemsetAsync(v.p, 0, v.n * sizeof(float), c->stream)); }
+    for (int k = 1; k <= 3; ++k) ensure_zeroed(c, c->mgu_vec[k], nv);
+    for (auto &v : c->mguf_vec) ensure_zeroed(c, v, nv);
     if (l > 0 && c->uu_mg_version != f0->asm_version) { // operator state of a coarse level: rediscretisation at the injected point
       ifem_ctx *p = M.L[l - 1].ctx;
       c->mf_params = f0->mf_params;
@@ -1043,20 +653,10 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
     B.asm_stamp = f0->asm_version;
     if (same) continue;
     if (force_bounds) B.lmax = 0; // cold estimate: all 12 steps from a rough vector
-    // power iteration on B A_uu.  A level that has an estimate from another constrained-dof set starts from that run's last
-    // iterate and stops once the estimate moves by less than 1 % (the top of this spectrum belongs to the mesh, not to the
-    // set); the first estimate starts from a fixed rough vector and runs all 12 steps.
-    double *x = c->mgu_vec[1].p, *y = c->mgu_vec[3].p, *z = c->mgu_vec[2].p;
-    const bool warm = B.lmax > 0 && (int64_t)B.eig.n == S.nuo && S.nuo > 0;
-    if (warm) v_copy(c, S.nuo, B.eig.p, x);
-    else vec_rough(c, S.nuo, int64_t(c->halo.rank) * 7000003, x);
-    double lam = 0;
-    const int n_pow = c->tune.eig_steps > 0 ? c->tune.eig_steps : 12;
-    for (int it = 0; it < n_pow; ++it) {
-      double nx = v_dot(c, S.nuo, x, x);
-      allreduce_sum(c, &nx, 1);
-      if (!(nx > 0)) break;
-      v_scale(c, S.nuo, 1.0 / std::sqrt(nx), x);
+    // power iteration on B A_uu (estimate_lmax: 12 steps when cold; warm across constrained-dof sets: the top of this spectrum belongs to the mesh)
+    double *y = c->mgu_vec[3].p; bool warm;
+    double lam = estimate_lmax(c, S.nuo, c->tune.eig_steps > 0 ? c->tune.eig_steps : 12, int64_t(c->halo.rank) * 7000003, B.lmax, B.eig, c->mgu_vec[1].p,
+                               c->mgu_vec[2].p, [&](const double *x, double *z) {
       uu_apply_level(S, x, y);
       if (kind == 1) { // the patch B acts on the single-precision level vectors (3 and 4 are idle outside of a cycle)
         v_cvt_d2f(c, S.nuo, y, c->mguf_vec[3].p);
@@ -1064,17 +664,7 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
         v_cvt_f2d(c, S.nuo, c->mguf_vec[4].p, z);
       } else
       bjac_apply(c, y, z);
-      double nz = v_dot(c, S.nuo, z, z);
-      allreduce_sum(c, &nz, 1);
-      const double prev = lam;
-      lam = std::sqrt(nz);
-      v_copy(c, S.nuo, z, x);
-      if (warm && it >= 1 && std::fabs(lam - prev) <= 0.01 * lam) break;
-    }
-    if (S.nuo > 0) {
-      if ((int64_t)B.eig.n != S.nuo) B.eig.alloc((size_t)S.nuo);
-      v_copy(c, S.nuo, x, B.eig.p);
-    }
+    }, &warm);
     if (ifem_ctx *w = replica_world(c)) allreduce_max(w, &lam, 1);
     B.lmax = lam > 0 && std::isfinite(lam) ? lam : 1.0;
     if (S.o->verbose) fprintf(stderr, "[ifem] A_uu V-cycle level %zu (%lld cells): lambda_max estimate %.4f (%s)\n", l, (long long)c->n_cells, c->uu_lmax(), warm ? "warm" : "cold");
@@ -1092,31 +682,34 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
 struct SmoothOpts {
   bool keep_r = false, d_ready = false, trim = false, x_fresh = false, no_exit = false;
 };
-static void mg_uu_smooth(MgUu &M, size_t l, int nsteps, double lo, double hi, float *x, float *r, const SmoothOpts &o) {
+// the sweeps of level l over the target interval of B A_uu (post: the one after the coarse correction); the coarsest level runs one longer sweep
+static ChebSweep mg_uu_sweep(const MgUu &M, size_t l, bool post = false) {
+  const double hi = 1.1 * M.L[l].ctx->uu_lmax();
+  if (l + 1 == M.L.size()) return {hi / 400.0, hi, 24};
+  return {hi / M.ratio, hi, post ? M.nu_post : M.nu};
+}
+static void mg_uu_smooth(MgUu &M, size_t l, const ChebSweep &w, float *x, float *r, const SmoothOpts &o) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *d = c->mguf_vec[2].p;
-  const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
-  double rho_old = 1.0 / sigma;
-  if (!o.d_ready) smoother_dir(c, 0.0, 1.0 / theta, r, d);
-  for (int k = 0; k < nsteps; ++k) {
-    const bool last = k == nsteps - 1;
+  Cheb ch(w);
+  if (!o.d_ready) smoother_dir(c, 0.0, ch.c0(), r, d);
+  for (int k = 0; k < w.steps; ++k) {
+    const bool last = k == w.steps - 1;
     if (last && !o.keep_r) {
       if (o.no_exit) break;
       if (k == 0 && o.x_fresh) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream)); // (a one-step sweep from zero)
       v_axpy_f32v(c, S.nuo, 1.0f, d, x);
       break;
     }
-    const double rho_new = 1.0 / (2.0 * sigma - rho_old);
     // x += d; r -= A d; d = rho_new rho_old d + (2 rho_new / delta) B r: fused into the node gather of the product as far as B allows
     MfFuseT<float> f;
-    f.mode = (o.trim && last) ? 1 : 2; f.a = rho_new * rho_old; f.b = 2.0 * rho_new / delta; f.xs = x; f.r = r; f.d = d;
+    f.mode = (o.trim && last) ? 1 : 2; ch.next(f.a, f.b); f.xs = x; f.r = r; f.d = d;
     f.first = (k == 0 && o.x_fresh) ? 1 : 0;
     const bool dir_follows = smoother_fuse_mode(c, f.mode);
     uu_apply_level_f32(S, d, &f);
     // (the direction of the last step of a keep_r sweep is never read: the residual update after the coarse correction writes a new one)
     if (dir_follows && !last) smoother_dir(c, f.a, f.b, r, d);
-    rho_old = rho_new;
   }
 }
 
@@ -1127,19 +720,17 @@ static void mg_uu_vcycle(MgUu &M, size_t l) {
   SolveState &S = M.L[l];
   ifem_ctx *c = S.ctx;
   float *r = c->mguf_vec[0].p, *x = c->mguf_vec[1].p;
-  const double hi = 1.1 * c->uu_lmax();
   const bool trim = M.trim, top = trim && l == 0;
   if (!trim) IFEM_HIP_CHECK(hipMemsetAsync(x, 0, size_t(S.nuo) * sizeof(float), c->stream));
   if (l + 1 == M.L.size()) {
     SmoothOpts coarsest;
     coarsest.d_ready = top; coarsest.trim = trim; coarsest.x_fresh = trim; coarsest.no_exit = top;
-    mg_uu_smooth(M, l, 24, hi / 400.0, hi, x, r, coarsest);
+    mg_uu_smooth(M, l, mg_uu_sweep(M, l), x, r, coarsest);
     return;
   }
-  const double lo = hi / M.ratio;
   SmoothOpts pre;
   pre.keep_r = true; pre.d_ready = top; pre.trim = trim; pre.x_fresh = trim;
-  mg_uu_smooth(M, l, M.nu, lo, hi, x, r, pre);
+  mg_uu_smooth(M, l, mg_uu_sweep(M, l), x, r, pre);
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
   mg_csr_apply_nodes_f32(c, c->mg_Ru, r, c->mg_Ru_mask, cc->mguf_vec[0].p);
@@ -1152,20 +743,16 @@ static void mg_uu_vcycle(MgUu &M, size_t l) {
   float *e = c->mguf_vec[4].p;
   mg_csr_apply_nodes_f32(c, c->mg_Pu, cc->mguf_vec[1].p, c->mg_Pu_mask, e);
   MfFuseT<float> f; // x += e; r -= A e; d = (1/theta) B r: the first direction of the post-smoothing sweep
-  f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = 1.0 / (0.5 * (hi + lo));
+  f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = Cheb(mg_uu_sweep(M, l, true)).c0();
   const bool dir_follows = smoother_fuse_mode(c, f.mode);
   uu_apply_level_f32(S, e, &f);
   if (dir_follows) smoother_dir(c, 0.0, f.b, r, f.d);
   SmoothOpts post;
   post.d_ready = true; post.trim = trim; post.no_exit = top;
-  mg_uu_smooth(M, l, M.nu_post, lo, hi, x, r, post);
+  mg_uu_smooth(M, l, mg_uu_sweep(M, l, true), x, r, post);
 }
 // the first direction of level 0 is (1 / theta) B r with the theta of the sweep the cycle starts with
-static double mg_uu_entry_c0(const MgUu &M) {
-  const double hi = 1.1 * M.L[0].ctx->uu_lmax();
-  const double lo = M.L.size() == 1 ? hi / 400.0 : hi / M.ratio;
-  return 1.0 / (0.5 * (hi + lo));
-}
+static double mg_uu_entry_c0(const MgUu &M) { return Cheb(mg_uu_sweep(M, 0)).c0(); }
 
 // the level chain of this application: every attached coarser level that has velocity transfers from the one above
 MgUu::MgUu(SolveState &S_) : S(S_), c(S_.ctx), o(S_.o) {
@@ -1335,17 +922,9 @@ static void solve_mp(SolveState &S, const double *b, double *x) {
   // than the separate pass over the two vectors.)
   const bool approx = approx_kind(o);
   const OpFn mp = [&](const double *u, double *y) {
-    if (halo_overlap_ok(c)) {
-      build_row_split(c, c->Mp, c->nPo);
-      v_copy(c, S.npo, u, S.xp_ext);
-      halo_start(c, S.xp_ext, 1);
-      spmv_mp(c, S.xp_ext, y, 1, approx);
-      halo_wait(c);
-      spmv_mp(c, S.xp_ext, y, 2, approx);
-      return;
-    }
-    const double *ue; extend_p(S, u, &ue);
-    spmv_mp(c, ue, y, 0, approx);
+    const double *ue = S.xp_ext;
+    halo_apply(c, true, [&] { build_row_split(c, c->Mp, c->nPo); v_copy(c, S.npo, u, S.xp_ext); halo_start(c, S.xp_ext, 1); },
+               [&] { extend_p(S, u, &ue); }, [&](int part) { spmv_mp(c, ue, y, part, approx); });
   };
   // ... and put a Jacobi preconditioner on this solve: same stopping rule on the true residual, fewer iterations (the reference uses
   // PreconditionNone; counts are no parity target)
@@ -1512,11 +1091,7 @@ static void precond_section_times(ifem_ctx *c, ifem_solve_stats &st) {
 // The inner Krylov basis is shared by every solver of the context.  The single-precision-basis kernels read (with zero
 // coefficients) up to 3 columns past the ones in use, so the buffer is zero-filled whenever it is (re)allocated: 0 * NaN
 // from uninitialised memory would poison the preconditioner.
-static void grow_inner_basis(ifem_ctx *c, int64_t need) {
-  if ((int64_t)c->innerV.n >= need) return;
-  c->innerV.alloc((size_t)need);
-  IFEM_HIP_CHECK(hipMemsetAsync(c->innerV.p, 0, c->innerV.n * sizeof(double), c->stream));
-}
+static void grow_inner_basis(ifem_ctx *c, int64_t need) { ensure_zeroed(c, c->innerV, need); }
 
 static void carve_workspace(SolveState &S, bool krylov) {
   ifem_ctx *c = S.ctx;
@@ -1543,6 +1118,13 @@ static void carve_workspace(SolveState &S, bool krylov) {
     grow_inner_basis(c, (int64_t)(S.o->ainv_kind == IFEM_AINV_MG ? std::min(mi + 1, kBasisStart) : mi + 1) * basis_ld(S.ctx, S.nuo));
 }
 
+// a SolveState on the library's default options, for the entry points that are no solve.  The options it points to are this function's and outlive it
+static SolveState default_state(ifem_ctx *ctx) {
+  static const ifem_solver_opts o = [] { ifem_solver_opts d; ifem_default_solver_opts(&d); return d; }();
+  SolveState S{ctx, nullptr, &o}; carve_workspace(S);
+  return S;
+}
+
 void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, const double *src, double *dst) {
   SolveState S{ctx, P, o};
   carve_workspace(S);
@@ -1555,10 +1137,7 @@ void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solve
 // b = C^T (b^ - A^ c0) on the regular rows, d_h c0_h on the hanging rows (distribute_local_to_global semantics)
 void hanging_condense_rhs(ifem_ctx *ctx, int use_nonzero) {
   if (!ctx->hang.active) return;
-  ifem_solver_opts o;
-  ifem_default_solver_opts(&o);
-  SolveState S{ctx, nullptr, &o};
-  carve_workspace(S);
+  SolveState S = default_state(ctx);
   hanging_refresh_diag(ctx);
   double *rhs = ctx->vec[IFEM_VEC_RHS].p;
   const bool inhom = hanging_offset(ctx, use_nonzero); // c0: ghost-extended, zero away from the hanging entries
@@ -1570,10 +1149,7 @@ void hanging_condense_rhs(ifem_ctx *ctx, int use_nonzero) {
 }
 
 void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst) {
-  ifem_solver_opts o;
-  ifem_default_solver_opts(&o);
-  SolveState S{ctx, nullptr, &o};
-  carve_workspace(S);
+  SolveState S = default_state(ctx);
   system_apply(S, src, dst, false);
 }
 
@@ -1615,10 +1191,7 @@ void scns_refpc_setup(ifem_ctx *ctx, int verbose, bool *pvv_ok, bool *b2_ok) {
 
 // test hook (ifem_scns_pc_probe, single rank): the pieces of the preconditioner on device vectors
 void scns_pc_probe(ifem_ctx *ctx, int which, const double *x, double *y) {
-  ifem_solver_opts o;
-  ifem_default_solver_opts(&o);
-  SolveState S{ctx, nullptr, &o};
-  carve_workspace(S);
+  SolveState S = default_state(ctx);
   bool pvv_ok = false, b2_ok = false;
   scns_refpc_setup(ctx, 0, &pvv_ok, &b2_ok);
   if (!pvv_ok || !b2_ok) throw Error(IFEM_E_KRYLOV_NOCONV, "ILU(0) broke down");

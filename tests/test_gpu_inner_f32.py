@@ -1,5 +1,5 @@
-"""The single-precision flexible inner solver of IFEM_AINV_MG and the trimmed A_uu V-cycle (ifem_tuning::inner_f32; solver.hip::fgmres_f32,
-mg_uu_vcycle(trim), mg.hip::k_vc_entry / k_vc_exit, the `first` flag and mode 1 of apply_mf.hip::k_mf_gather), through the C ABI.
+"""The single-precision flexible inner solver of IFEM_AINV_MG and the trimmed A_uu V-cycle (ifem_tuning::inner_f32; krylov.hip::fgmres_f32,
+solver.hip::mg_uu_vcycle(trim), mg.hip::k_vc_entry / k_vc_exit, the `first` flag and mode 1 of apply_mf.hip::k_mf_gather), through the C ABI.
 
 inner_f32 = 0 is the path as it was before the knob existed (fp64 bases, conversion passes, zero fills, every smoothing step in full), so
 one build is compared with itself.  What the trimmed cycle leaves out is never read: with inner_maxit = 0 (A~^-1 = one V-cycle) the two

@@ -1,5 +1,5 @@
 """The reductions and multi-vector updates of the Krylov path (csrc/linalg.hip: v_mdot / v_maxpy, their single-precision-basis twins, the
-element-wise vector kernels, v_minmax) and the device-scalar CG recurrences (cgd_* / cg1_* under solver.hip::cg_device), each HOST LAUNCHER
+element-wise vector kernels, v_minmax) and the device-scalar CG recurrences (cgd_* / cg1_* under krylov.hip::cg_device), each HOST LAUNCHER
 called once on host data through the test aids ifem_test_vec_kernel / ifem_test_cg_device and compared with numpy in np.longdouble on the
 same arrays.  Whole solves hide what these kernels can get wrong (a coefficient from the wrong column, a dropped tail, a norm taken one
 pass early only cost iterations); here every dispatch arm is reached on purpose:
