@@ -81,6 +81,18 @@ int ifem_test_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int k, int64_t ld, vo
  * counts as 1.  Single rank, a created context only. */
 int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x);
 
+/* ONE matrix-free product t = A_uu x with the epilogue of its node gather (apply_mf.hip::k_mf_gather, kernels.hpp::MfFuseT) on host vectors of
+ * dim * n_unodes doubles, for the operator state of the last ifem_ins_assemble / ifem_imex_assemble.  Single rank.
+ *   prec 0: double cell arithmetic, double vectors; 1: single-precision cell arithmetic and float vectors (the level vectors of the A_uu V-cycle;
+ *   the host vectors are rounded to float and returned widened); 2: single-precision cell arithmetic, double vectors
+ *   mode 0: d = t (the plain form; xs, r unused)     mode 1: xs += x, r -= t (d unused, may be NULL)
+ *   mode 2: mode 1, then d = a x + b B r, formed in place in the device copy of x as the smoother does     mode 3: mode 1, then d = b B r
+ *   first != 0: xs = x is stored and the incoming xs not read
+ * block_cap > 0 caps the gather's blocks for this call, so that a small mesh gives one block several chunks of nodes; geo (may be NULL) receives
+ * {chunks, blocks} of the gather launch. */
+int ifem_test_uu_fused_product(ifem_ctx *ctx, int prec, int mode, int first, double a, double b, const double *x, double *xs, double *r, double *d,
+                               int block_cap, int64_t geo[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,7 +140,8 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_get_constraints", "ifem_fsi_fluid_at_points", "ifem_comm_stats_get", "ifem_comm_stats_level", "ifem_true_residual", "ifem_tpp_ilu_probe", "ifem_tpp_override", "ifem_scns_pc_probe", "ifem_test_restart_fits",
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
-           "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device"]
+           "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
+           "ifem_test_uu_fused_product"]
 
 # ops of ifem_test_vec_kernel (IFEM_TVK_*)
 (TVK_MDOT, TVK_MDOT_SELF, TVK_MAXPY, TVK_MAXPY_NORM, TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32, TVK_AXPY,
@@ -235,6 +236,8 @@ def load():
     L.ifem_test_uu_patch_info.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_test_vec_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_cg_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.ifem_test_uu_fused_product.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -559,6 +562,19 @@ class Context:
         self.vec_set(VEC_TMP, x)
         self._chk(self.L.ifem_test_uu_patch_vmult(self.h, VEC_UPDATE, VEC_TMP))
         return self.vec_get(VEC_UPDATE)
+
+    def uu_fused_product(self, prec, mode, x, xs=None, r=None, first=0, a=0.0, b=0.0, block_cap=0):
+        """one matrix-free product with the node gather's epilogue on host vectors of dim * n_unodes entries -- ifem_test_uu_fused_product.
+        Returns (xs, r, d, (chunks, blocks)); mode 0: d = A_uu x and xs, r are None; mode 1: d is None"""
+        n = self.dim * self.n_unodes_owned
+        x = np.ascontiguousarray(x[:n], float)
+        xs = None if mode == 0 else np.array(xs[:n], float)
+        r = None if mode == 0 else np.array(r[:n], float)
+        d = None if mode == 1 else np.zeros(n)
+        geo = np.zeros(2, np.int64)
+        self._chk(self.L.ifem_test_uu_fused_product(self.h, prec, mode, first, a, b, _ptr(x), None if xs is None else _ptr(xs),
+                                                    None if r is None else _ptr(r), None if d is None else _ptr(d), block_cap, _ptr(geo)))
+        return xs, r, d, (int(geo[0]), int(geo[1]))
 
     def test_vec_kernel(self, op, n, k, ld, V=None, coef=None, w=None, out=None):
         """one host launcher of the Krylov vector kernels on host arrays (C-contiguous; V float32 for the _F32 ops, everything else float64);

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/ifem_hip_testing.h"
 #include "ctx.hpp"
@@ -857,6 +858,66 @@ int ifem_test_uu_patch_info(ifem_ctx *ctx, int64_t out[4]) {
   out[1] = tables ? ctx->patch.n_patches : 0;
   out[2] = tables ? (ctx->patch.form == 1 ? ctx->patch.n_patches : ctx->patch.n_types) : 0; // stored inverses
   out[3] = tables ? ctx->patch.inv_bytes : 0;
+  IFEM_API_END
+}
+
+extern "C++" {
+// one product on host vectors with device vectors of type V (see ifem_test_uu_fused_product)
+template <typename V>
+static void fused_product_on(ifem_ctx *ctx, int prec, int mode, int first, double a, double b, const double *x, double *xs, double *r, double *d) {
+  const size_t n = size_t(ctx->dim) * ctx->nUo, nv = size_t(ctx->dim) * ctx->nUl + 8;
+  hipStream_t s = ctx->stream;
+  ifem::DBuf<V> dx, dxs, dr, dd;
+  ifem::DBuf<double> dy;
+  std::vector<V> h(nv, V(0));
+  auto up = [&](ifem::DBuf<V> &buf, const double *src, size_t len) {
+    buf.alloc(len);
+    for (size_t i = 0; i < n; ++i) h[i] = V(src[i]);
+    IFEM_HIP_CHECK(hipMemcpyAsync(buf.p, h.data(), len * sizeof(V), hipMemcpyHostToDevice, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  };
+  auto down = [&](const V *src, double *dst) {
+    IFEM_HIP_CHECK(hipMemcpyAsync(h.data(), src, n * sizeof(V), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) dst[i] = double(h[i]);
+  };
+  up(dx, x, nv);
+  if (mode == 0) {
+    dy.alloc(n);
+    if constexpr (std::is_same<V, float>::value) ifem::apply_uu_mf_f32in(ctx, dx.p, dy.p);
+    else ifem::apply_uu_mf(ctx, dx.p, dy.p, prec == 2);
+    IFEM_HIP_CHECK(hipMemcpyAsync(d, dy.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+    return;
+  }
+  up(dxs, xs, n);
+  up(dr, r, n);
+  if (mode == 3) { dd.alloc(n); IFEM_HIP_CHECK(hipMemsetAsync(dd.p, 0, n * sizeof(V), s)); }
+  ifem::MfFuseT<V> f;
+  f.mode = mode; f.a = a; f.b = b; f.first = first;
+  f.xs = dxs.p; f.r = dr.p; f.d = mode == 2 ? dx.p : dd.p; // mode 2 updates the direction in place, as the smoother does
+  if constexpr (std::is_same<V, float>::value) ifem::apply_uu_mf_f32v(ctx, dx.p, &f);
+  else ifem::apply_uu_mf(ctx, dx.p, nullptr, prec == 2, &f);
+  down(dxs.p, xs);
+  down(dr.p, r);
+  if (mode >= 2) down(f.d, d);
+}
+} // extern "C++"
+
+int ifem_test_uu_fused_product(ifem_ctx *ctx, int prec, int mode, int first, double a, double b, const double *x, double *xs, double *r, double *d,
+                               int block_cap, int64_t geo[2]) {
+  IFEM_API_BEGIN
+  if (!ctx->assembled || !ctx->mf_valid) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_fused_product called before ifem_ins_assemble");
+  if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_uu_fused_product: single-rank contexts");
+  if (prec < 0 || prec > 2 || mode < 0 || mode > 3 || block_cap < 0 || !x || (mode != 1 && !d) || (mode && (!xs || !r)))
+    throw Error(IFEM_E_BADPARAM, "ifem_test_uu_fused_product: prec 0..2, mode 0..3, block_cap >= 0, and the vectors the mode uses");
+  ctx->mf_gather_block_cap = unsigned(block_cap);
+  try {
+    if (prec == 1) fused_product_on<float>(ctx, prec, mode, first ? 1 : 0, a, b, x, xs, r, d);
+    else fused_product_on<double>(ctx, prec, mode, first ? 1 : 0, a, b, x, xs, r, d);
+  } catch (...) { ctx->mf_gather_block_cap = 0; throw; }
+  ctx->mf_gather_block_cap = 0;
+  if (geo) { geo[0] = ctx->mf_gather_geo[0]; geo[1] = ctx->mf_gather_geo[1]; }
   IFEM_API_END
 }
 

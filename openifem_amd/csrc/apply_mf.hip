@@ -445,76 +445,161 @@ __global__ __launch_bounds__(64 * WPB) void k_apply_uu_mf2(MfArgsT<R, XT> A) {
 // is stored without reading xs (the first step of a sweep from zero: no memset of xs before it).
 // LIFT (uu_lift_mf; x = the constraint values, y = the right-hand side): free rows y_i -= sum, constrained rows y_r = d_r x_r with
 // the same d_r as above.
+// The kernel: lanes walk the incidence entries FLAT, nodes sum from LDS.  A block is persistent (one resident round of blocks:
+// apply_uu_mf_t) and takes every gridDim.x-th chunk of NT consecutive nodes, so that the nodes in flight on the device at any moment are
+// neighbours and share the lines of the per-cell results.  The entries of a chunk are contiguous in `inc` (CSR), so its tile of up to
+// TILE = NT * EPT entries is read with coalesced 4-byte loads, one DIM-value load of the cell result per LIVE entry (no slot is loaded
+// that the sum does not use), and goes to LDS; the chunk's row pointers go to LDS as their low 32 bits (differences are exact below 2^32
+// entries per chunk; inc_ptr stays 64-bit).  The vectors of the epilogue are requested between the entries and the cell results, so
+// they arrive while the chain row pointer -> entry -> cell result runs.  Then lane t sums the entries of node t from LDS IN THE ORDER OF ITS INCIDENCE LIST, in
+// double, and runs the epilogue -- the order (and for R = float every bit of the result) is that of the one-node-per-thread loop this
+// replaces.  A chunk with more than TILE entries (any valence: a node's list may span tiles) takes further tiles; EPT = 6 fits the
+// chunks of a lexicographically numbered Q2 box (a grid line alternates 8- and 4-cell nodes: 1536 entries).
+// Measured and not kept (profiles/r11_mf_gather.txt): a software pipeline over the chunks of a block (cell results one chunk, entries two
+// chunks ahead) at EPT = 8 and 6 -- no faster than this form at equal EPT, 30 VGPRs more; one contiguous chunk range per block.
+template <typename R>
+struct MfGatherGeo {
+  static constexpr int NT = 256;                      // threads = nodes of a chunk
+  static constexpr int EPT = sizeof(R) == 4 ? 6 : 3;  // entries per lane and tile
+  static constexpr int TILE = NT * EPT;
+};
+inline unsigned mf_gather_chunks(int64_t n_nodes) { return unsigned((n_nodes + MfGatherGeo<float>::NT - 1) / MfGatherGeo<float>::NT); }
+
 template <int DIM, typename R, bool FUSE, typename V, bool LIFT = false>
-__global__ void k_mf_gather(int64_t n, int nn, const int64_t *__restrict__ inc_ptr, const int32_t *__restrict__ inc,
+__global__ __launch_bounds__(MfGatherGeo<R>::NT) void k_mf_gather(int64_t n, int nn, const int64_t *__restrict__ inc_ptr, const int32_t *__restrict__ inc,
                             const R *__restrict__ ycell, const uint8_t *__restrict__ is_c,
                             const double *__restrict__ bjac, const float *__restrict__ bjf, const V *x, double *y, MfFuseT<V> fuse) {
-  // one thread per node: the incidence list is walked once for the DIM components (24 contiguous bytes per entry)
-  const int64_t nd = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (nd * DIM >= n) return;
-  double s[DIM];
+  constexpr int NT = MfGatherGeo<R>::NT, EPT = MfGatherGeo<R>::EPT, TILE = MfGatherGeo<R>::TILE;
+  __shared__ R vals[TILE * DIM];
+  __shared__ uint32_t rpl[NT + 1];
+  const int t = threadIdx.x;
+  const int64_t n_nodes = n / DIM, n_chunks = (n_nodes + NT - 1) / NT;
+  // entries ts .. ts + TILE of the list [k0, k1): lane t takes ts + j NT + t; -1 marks a slot past the end
+  auto load_entries = [&](int64_t k0, int64_t k1, int64_t ts, int32_t (&e)[EPT]) {
+    const int64_t m = k1 - k0 - ts;
 #pragma unroll
-  for (int c = 0; c < DIM; ++c) s[c] = 0;
-  const int64_t k0 = inc_ptr[nd], k1 = inc_ptr[nd + 1];
-  uint8_t fl[DIM]; // constraint flags: requested now, looked at after the sums
+    for (int j = 0; j < EPT; ++j) e[j] = j * NT + t < m ? inc[k0 + ts + j * NT + t] : int32_t(-1);
+  };
+  auto load_vals = [&](const int32_t (&e)[EPT], R (&v)[EPT][DIM]) {
 #pragma unroll
-  for (int c = 0; c < DIM; ++c) fl[c] = is_c ? is_c[nd * DIM + c] : uint8_t(0);
-  // up to 8 incident cells per trip (a vertex node of a hexahedral mesh has 8): all incidence entries are loaded before
-  // the dependent loads of the cell results; slots past the end re-read the first entry with weight 0
-  for (int64_t k = k0; k < k1; k += 8) {
-    int32_t e[8];
+    for (int j = 0; j < EPT; ++j)
+      if (e[j] >= 0) {
+        const R *src = ycell + int64_t(e[j] >> 5) * (DIM * nn) + (e[j] & 31) * DIM;
 #pragma unroll
-    for (int u = 0; u < 8; ++u) e[u] = inc[k + u < k1 ? k + u : k0];
-    R v[8][DIM];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const R *src = ycell + int64_t(e[u] >> 5) * (DIM * nn) + (e[u] & 31) * DIM;
-#pragma unroll
-      for (int c = 0; c < DIM; ++c) v[u][c] = src[c];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (k + u < k1) {
-#pragma unroll
-        for (int c = 0; c < DIM; ++c) s[c] += v[u][c];
+        for (int c = 0; c < DIM; ++c) v[j][c] = src[c];
       }
-  }
-  if constexpr (!FUSE) {
+  };
+  auto stage_vals = [&](const int32_t (&e)[EPT], const R (&v)[EPT][DIM]) {
 #pragma unroll
-    for (int c = 0; c < DIM; ++c) {
-      const int64_t i = nd * DIM + c;
-      if constexpr (LIFT) y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : y[i] - s[c];
-      else y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : s[c];
+    for (int j = 0; j < EPT; ++j)
+      if (e[j] >= 0) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) vals[(j * NT + t) * DIM + c] = v[j][c];
+      }
+  };
+  // entries [lo, hi) of this lane's node that lie in the staged tile [ts, ts + TILE), in list order
+  auto sum_tile = [&](uint32_t lo, uint32_t hi, uint32_t ts, double (&s)[DIM]) {
+    const uint32_t a = lo > ts ? lo : ts, b = hi < ts + TILE ? hi : ts + TILE;
+    for (uint32_t k = a; k < b; ++k) {
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) s[c] += double(vals[(k - ts) * DIM + c]);
     }
-  } else {
-    double xv[DIM], rv[DIM], bj[DIM * DIM];
-    if (fuse.mode >= 2) {
+  };
+
+  for (int64_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+    const int64_t nd = ch * NT + t;
+    const bool act = nd < n_nodes;
+    const int64_t nds = act ? nd : 0; // (inactive lanes read node 0 and store nothing)
+    // ---- the chunk's row pointers and its first tile of entries
+    const int64_t last = (ch + 1) * NT, k0 = inc_ptr[ch * NT], k1 = inc_ptr[last < n_nodes ? last : n_nodes];
+    const uint32_t rp_reg = uint32_t(inc_ptr[nd < n_nodes ? nd : n_nodes]);
+    int32_t ent[EPT];
+    R v[EPT][DIM];
+    load_entries(k0, k1, 0, ent);
+    // ---- this chunk's vectors: requested behind the entries, looked at after the sums
+    uint8_t fl[DIM];
 #pragma unroll
-      for (int e = 0; e < DIM * DIM; ++e) bj[e] = double(bjf[nd * DIM * DIM + e]);
-    } else { // mode 1 applies no node block: only the diagonal entry of a constrained row is needed
-#pragma unroll
-      for (int c = 0; c < DIM; ++c) bj[c * DIM + c] = fl[c] ? double(bjf[nd * DIM * DIM + c * DIM + c]) : 1.0;
-    }
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) {
-      const int64_t i = nd * DIM + c;
-      xv[c] = double(x[i]);
-      const double t = fl[c] ? xv[c] / bj[c * DIM + c] : s[c];
-      rv[c] = double(fuse.r[i]) - t;
-      const double x0 = fuse.first ? 0.0 : double(fuse.xs[i]); // first: xs is not read (it holds nothing yet)
-      fuse.xs[i] = V(x0 + xv[c]);
-      fuse.r[i] = V(rv[c]);
-    }
-    if (fuse.mode >= 2) {
-      const double a = fuse.mode == 2 ? fuse.a : 0.0;
+    for (int c = 0; c < DIM; ++c) fl[c] = is_c ? is_c[nds * DIM + c] : uint8_t(0);
+    [[maybe_unused]] V xin[DIM], rin[DIM], xsin[DIM];
+    [[maybe_unused]] float bjin[DIM * DIM];
+    [[maybe_unused]] double yin[DIM];
+    if constexpr (FUSE) {
 #pragma unroll
       for (int c = 0; c < DIM; ++c) {
-        double z = 0;
+        xin[c] = x[nds * DIM + c];
+        rin[c] = fuse.r[nds * DIM + c];
+        xsin[c] = fuse.first ? V(0) : fuse.xs[nds * DIM + c]; // first: xs is not read (it holds nothing yet)
+      }
+      if (fuse.mode >= 2) {
 #pragma unroll
-        for (int j = 0; j < DIM; ++j) z += bj[c * DIM + j] * rv[j];
-        fuse.d[nd * DIM + c] = V(a * xv[c] + fuse.b * z);
+        for (int e = 0; e < DIM * DIM; ++e) bjin[e] = bjf[nds * DIM * DIM + e];
+      }
+    } else if constexpr (LIFT) {
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) yin[c] = y[nds * DIM + c];
+    }
+    // ---- the cell results of the tile, staged with the row pointers
+    load_vals(ent, v);
+    stage_vals(ent, v);
+    rpl[t] = rp_reg;
+    if (t == 0) rpl[NT] = uint32_t(k1);
+    __syncthreads();
+    // ---- node sums
+    double s[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) s[c] = 0;
+    const uint32_t lo = rpl[t] - uint32_t(k0), hi = rpl[t + 1] - uint32_t(k0);
+    sum_tile(lo, hi, 0, s);
+    for (int64_t ts = TILE; ts < k1 - k0; ts += TILE) { // (block-uniform) further tiles of a chunk with more than TILE entries
+      __syncthreads();
+      int32_t e2[EPT];
+      R v2[EPT][DIM];
+      load_entries(k0, k1, ts, e2);
+      load_vals(e2, v2);
+      stage_vals(e2, v2);
+      __syncthreads();
+      sum_tile(lo, hi, uint32_t(ts), s);
+    }
+    // ---- epilogue
+    if (act) {
+      if constexpr (!FUSE) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+          const int64_t i = nd * DIM + c;
+          if constexpr (LIFT) y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : yin[c] - s[c];
+          else y[i] = fl[c] ? x[i] / bjac[nd * DIM * DIM + c * DIM + c] : s[c];
+        }
+      } else {
+        double xv[DIM], rv[DIM], bj[DIM * DIM];
+        if (fuse.mode >= 2) {
+#pragma unroll
+          for (int e = 0; e < DIM * DIM; ++e) bj[e] = double(bjin[e]);
+        } else { // mode 1 applies no node block: only the diagonal entry of a constrained row is needed
+#pragma unroll
+          for (int c = 0; c < DIM; ++c) bj[c * DIM + c] = fl[c] ? double(bjf[nd * DIM * DIM + c * DIM + c]) : 1.0;
+        }
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+          const int64_t i = nd * DIM + c;
+          xv[c] = double(xin[c]);
+          const double tt = fl[c] ? xv[c] / bj[c * DIM + c] : s[c];
+          rv[c] = double(rin[c]) - tt;
+          fuse.xs[i] = V(double(xsin[c]) + xv[c]);
+          fuse.r[i] = V(rv[c]);
+        }
+        if (fuse.mode >= 2) {
+          const double a = fuse.mode == 2 ? fuse.a : 0.0;
+#pragma unroll
+          for (int c = 0; c < DIM; ++c) {
+            double z = 0;
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) z += bj[c * DIM + j] * rv[j];
+            fuse.d[nd * DIM + c] = V(a * xv[c] + fuse.b * z);
+          }
+        }
       }
     }
+    __syncthreads(); // the next chunk overwrites vals and rpl
   }
 }
 
@@ -627,14 +712,21 @@ static void apply_uu_mf_t(ifem_ctx *ctx, const XT *xu, double *yu, const MfFuseT
   // node gather: the per-cell results and the incidence entries once, the node's row pointer; fused form: the inverse node block
   // (single precision) and the smoother's vectors (mode 1: xs, r read + written, x read; modes 2 / 3: d written too)
   // (fuse->first: xs is not read; mode 1 reads no node block)
+  // (the row pointers are read once per node; the chunk bounds, one more 8-byte read per 256 nodes, are not counted)
   const double per_node = ctx->dim * double(sizeof(XT)) * (fuse ? (fuse->mode >= 2 ? 6.0 : 5.0) - (fuse->first ? 1.0 : 0.0) : 2.0) +
                           (fuse && fuse->mode >= 2 ? 4.0 * ctx->dim * ctx->dim : 0.0) + 8.0 + ctx->dim;
   KScope ksg(ctx, IFEM_KC_MF_GATHER, double(ctx->n_cells) * ctx->nu * (ctx->dim * sizeof(R) + 4.0) + double(ctx->nUo) * per_node);
+  // persistent blocks: one resident round of the device, at most one block per chunk
+  const unsigned g_chunks = std::max(1u, mf_gather_chunks(n / ctx->dim));
+  const unsigned g_cap = ctx->mf_gather_block_cap ? std::min(ctx->mf_gather_block_cap, g_chunks) : g_chunks;
 #define IFEM_MFG(D, F)                                                                                                 \
-  hipLaunchKernelGGL((k_mf_gather<D, R, F, XT, LIFT>), dim3(unsigned((n / D + 255) / 256)), dim3(256), 0, s, n, ctx->nu, ctx->uinc.rowptr.p, \
-                     ctx->uinc.col.p, a.ycell, a.is_c, ctx->bjac.p, fuse ? bjac_f32_ptr(ctx) : nullptr, xu, yu, f0)
-  if (ctx->dim == 3) { if (fuse) IFEM_MFG(3, true); else IFEM_MFG(3, false); }
-  else { if (fuse) IFEM_MFG(2, true); else IFEM_MFG(2, false); }
+  { static const unsigned resident = grid_for_kernel(reinterpret_cast<const void *>(&k_mf_gather<D, R, F, XT, LIFT>)) / 4u; \
+    const unsigned g = std::min(resident, g_cap);                                                                       \
+    ctx->mf_gather_geo[0] = g_chunks; ctx->mf_gather_geo[1] = g;                                                        \
+    hipLaunchKernelGGL((k_mf_gather<D, R, F, XT, LIFT>), dim3(g), dim3(MfGatherGeo<R>::NT), 0, s, n, ctx->nu, ctx->uinc.rowptr.p, \
+                       ctx->uinc.col.p, a.ycell, a.is_c, ctx->bjac.p, fuse ? bjac_f32_ptr(ctx) : nullptr, xu, yu, f0); }
+  if (ctx->dim == 3) { if (fuse) IFEM_MFG(3, true) else IFEM_MFG(3, false) }
+  else { if (fuse) IFEM_MFG(2, true) else IFEM_MFG(2, false) }
 #undef IFEM_MFG
   if (time_it) {
     IFEM_HIP_CHECK(hipEventSynchronize(ctx->ev1));

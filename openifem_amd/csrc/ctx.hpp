@@ -390,6 +390,9 @@ struct ifem_ctx {
   ifem::DBuf<double> App, app_diag, stress, fsi_stress, sigma_pml, body_force, xinv, eddy_viscosity;
   bool has_app = false, stress_valid = false;
   ifem::PlanarCsr uinc;  // velocity node -> (cell << 5 | local index) incidence lists (gather stage of the matrix-free apply)
+  // launch geometry of the last node gather {chunks, blocks} (apply_mf.hip::k_mf_gather), and a cap on its blocks (0: none) so that a small
+  // mesh can give one block several chunks -- both for ifem_test_uu_fused_product only
+  unsigned mf_gather_geo[2] = {0, 0}, mf_gather_block_cap = 0;
   // several ranks: the matrix-free apply keeps its own copy of the cell tables with the cells whose nodes are all owned
   // first (they are processed while the halo is in flight); the incidence lists then refer to this numbering
   ifem::DBuf<int32_t> mf_cell_unodes;
