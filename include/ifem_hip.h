@@ -270,8 +270,8 @@ enum {
 const char *ifem_last_error(void);
 /* sizeof of the structs above as this library was compiled, for a binding to check its mirror against:
  * 0 ifem_mesh_desc, 1 ifem_partition, 2 ifem_ins_params, 3 ifem_solver_opts, 4 ifem_solve_stats, 5 ifem_scns_params,
- * 6 ifem_timing, 7 ifem_tuning, 8 ifem_mg_transfer, 9 ifem_fsi_solid, 10 ifem_fsi_stats, 11 ifem_comm_stats, 12 ifem_kprof_entry;
- * -1 for anything else */
+ * 6 ifem_timing, 7 ifem_tuning, 8 ifem_mg_transfer, 9 ifem_fsi_solid, 10 ifem_fsi_stats, 11 ifem_comm_stats, 12 ifem_kprof_entry,
+ * 13 ifem_sa_params; -1 for anything else */
 int64_t ifem_abi_sizeof(int which);
 int ifem_device_count(void);
 void ifem_default_solver_opts(ifem_solver_opts *o);
@@ -443,7 +443,8 @@ typedef struct {
 int ifem_set_scns_fields(ifem_ctx *ctx, const double *sigma_pml, const double *body_force, const double *fsi_stress);
 /* nodal eddy viscosity of an attached turbulence model ([n_unodes_local] on the scalar Q_kv space, or NULL to detach):
  * SCnsIM::assemble adds max(nu_t(q), 0) to the viscosity at every quadrature point (mpi_scnsim.cpp:198-216).  The
- * turbulence model itself (Spalart-Allmaras, source/mpi_spalart_allmaras.cpp) is outside the path. */
+ * Spalart-Allmaras model below (ifem_sa_*) writes the same buffer on the device: after ifem_sa_newton_step or
+ * ifem_sa_update_eddy_viscosity no upload is needed. */
 int ifem_set_eddy_viscosity(ifem_ctx *ctx, const double *nodal);
 /* FluidSolver::update_stress (mpi_fluid_solver.cpp:716-811) from IFEM_VEC_PRESENT into the context's nodal stress
  * (read by the next ifem_scns_assemble); host_out (may be NULL) receives [dim][dim][n_unodes_local] */
@@ -456,6 +457,52 @@ int ifem_scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, i
 /* Newton loop of SUPGFluidSolver::run_one_step (:331-425, floor 1e-14) followed by update_stress */
 int ifem_scns_newton_step(ifem_ctx *ctx, const ifem_scns_params *p, const ifem_solver_opts *o, int apply_nonzero,
                           double tolerance, int max_iterations, double *log);
+
+/* ---- Fluid::MPI::SpalartAllmaras (source/mpi_spalart_allmaras.cpp, on mpi_turbulence_model.cpp): the one-equation
+ * turbulence model of SUPGFluidSolver::run() (mpi_supg_solver.cpp:290-293, 456-469) on the device.  The unknown nu~ lives
+ * on the scalar Q_kv space, i.e. on the velocity NODES of the context ([n_unodes_local] vectors, node numbering of
+ * cell_unodes); its matrix uses the node pattern of A_uu.  The fluid velocity is read from IFEM_VEC_PRESENT, the
+ * artificial-fluid indicator from ifem_set_cell_fields / ifem_fsi_update_indicator.
+ * Geometry: support points and Jacobians come from the d-linear (MappingQ1) map of `vcoords`, as everywhere in this
+ * library; the reference evaluates the support points with MappingQGeneric(degree), which differs on curved cells only.
+ * ONE deliberate deviation: mpi_spalart_allmaras.cpp:757-770 discards the result of std::min and returns an uninitialised
+ * r whenever |S~| > 1e-8.  Implemented is the evident intent, r = min(nu~_present / (S~ kappa^2 d^2), 10) there and r = 10
+ * otherwise.
+ * Partitioned contexts work as for SCnsIM (owner-computes rows, halo refresh of nu~ and of the Krylov vectors, per-rank ILU(0) of the
+ * owned x owned block); every rank passes ALL wall points and the constraint lines of its owned and ghost nodes.
+ * Scope: contexts without hanging-node lines (with them: IFEM_E_BADPARAM); no FSI wall function
+ * (update_moving_wall_distance, update_boundary_condition, get_shear_velocity), no refinement transfer, no checkpoint
+ * payload. */
+typedef struct {
+  double viscosity, rho, dt; /* parameters.viscosity (laminar mu), fluid_rho, time step */
+} ifem_sa_params;
+enum { IFEM_SA_PRESENT = 0, IFEM_SA_EVAL = 1, IFEM_SA_UPDATE = 2, IFEM_SA_RHS = 3, IFEM_SA_N_VECS = 4 };
+/* SpalartAllmaras::setup_cell_property (:409-539): pts [n][dim] = the vertices of the wall faces (S-A boundary type 0);
+ * computes d(node) = min_i |x_node - pts_i| for every local node by brute force.  n = 0: d = DBL_MAX everywhere. */
+int ifem_sa_set_wall_points(ifem_ctx *ctx, int64_t n, const double *pts);
+int ifem_sa_get_wall_distance(ifem_ctx *ctx, double *host_out); /* [n_unodes_local] */
+/* SpalartAllmaras::make_constraints (:348-406): Dirichlet lines nu~[node[i]] = inhom[i] of constraint object `which`
+ * (0 = zero_constraints: inhom ignored, 1 = nonzero_constraints; inhom NULL = 0).  Replaces the object. */
+int ifem_sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom);
+/* present_solution / evaluation_point / newton_update / system_rhs of the model, [n_unodes_local] */
+int ifem_sa_vec_set(ifem_ctx *ctx, int vec, const double *host);
+int ifem_sa_vec_get(ifem_ctx *ctx, int vec, double *host);
+/* SpalartAllmaras::assemble (:620-862) at IFEM_SA_EVAL / IFEM_SA_PRESENT */
+int ifem_sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero);
+/* SpalartAllmaras::solve (:864-889): FGMRES(30) to 1e-8 ||rhs||, at most 2 n_dofs iterations, preconditioned by the ILU(0)
+ * of the matrix (Euclid level 0; exact substitution; Jacobi if the factorisation breaks down); then distribute().  n_dofs counts the
+ * scalar space: the global number of velocity NODES */
+int ifem_sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res);
+/* SpalartAllmaras::run_one_step (:283-345) including update_eddy_viscosity.  log (may be NULL) receives
+ * [ABS_RES, REL_RES, GMRES_ITR, GMRES_RES] per iteration.  Returns the number of Newton iterations. */
+int ifem_sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations,
+                        double *log);
+/* SpalartAllmaras::update_eddy_viscosity (:892-914): mu_t = chi^3 / (chi^3 + c_v1^3) nu~ rho from IFEM_SA_PRESENT, written
+ * into the buffer of ifem_set_eddy_viscosity; host_out [n_unodes_local] may be NULL */
+int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
+/* test hook: the assembled matrix as CSR over the nodes (two-call protocol of ifem_export_csr: rowptr [n_unodes_owned + 1]
+ * first with col = val = NULL) */
+int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val);
 
 /* ---- fluid-side inputs of MPI::FSI produced on the device (source/mpi_fsi.cpp) --------------------
  * What the FSI driver computes on the fluid mesh before every fluid step (mpi_fsi.cpp:1189-1208), from the solid as every

@@ -67,6 +67,14 @@ class ScnsParams(C.Structure):
 FORM_SCNSIM, FORM_SUPG_INSIM = 0, 1
 
 
+class SaParams(C.Structure):
+    """ifem_sa_params"""
+    _fields_ = [("viscosity", C.c_double), ("rho", C.c_double), ("dt", C.c_double)]
+
+
+SA_PRESENT, SA_EVAL, SA_UPDATE, SA_RHS = range(4)  # IFEM_SA_*
+
+
 class SolverOpts(C.Structure):
     _fields_ = [("fgmres_restart", C.c_int32), ("fgmres_maxit", C.c_int32), ("fgmres_rel", C.c_double),
                 ("fgmres_abs", C.c_double), ("mp_rel", C.c_double), ("mp_abs", C.c_double),
@@ -141,7 +149,9 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
-           "ifem_test_uu_fused_product"]
+           "ifem_test_uu_fused_product",
+           "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
+           "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
 
 # ops of ifem_test_vec_kernel (IFEM_TVK_*)
 (TVK_MDOT, TVK_MDOT_SELF, TVK_MAXPY, TVK_MAXPY_NORM, TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32, TVK_AXPY,
@@ -250,6 +260,16 @@ def load():
     L.ifem_fsi_get_stress.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_fsi_fluid_at_points.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_get_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.ifem_sa_set_wall_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.ifem_sa_get_wall_distance.argtypes = [C.c_void_p, C.c_void_p]
+    L.ifem_sa_set_constraints.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ifem_sa_vec_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.ifem_sa_vec_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.ifem_sa_assemble.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_int]
+    L.ifem_sa_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    L.ifem_sa_newton_step.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_int, C.c_double, C.c_int, C.c_void_p]
+    L.ifem_sa_update_eddy_viscosity.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_void_p]
+    L.ifem_sa_export_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_abi_sizeof.argtypes = [C.c_int]
     L.ifem_abi_sizeof.restype = C.c_int64
     _lib = L
@@ -278,7 +298,7 @@ class CommStats(C.Structure):  # ifem_comm_stats
 
 
 ABI_STRUCTS = [MeshDesc, Partition, InsParams, SolverOpts, SolveStats, ScnsParams, Timing, Tuning, MgTransfer, FsiSolid, FsiStats,
-               CommStats, KprofEntry]
+               CommStats, KprofEntry, SaParams]
 
 
 def export_rows(L, ctx, row0, nrows, which=0):
@@ -709,6 +729,60 @@ class Context:
         rc = self._chk(self.L.ifem_scns_newton_step(self.h, C.byref(params), C.byref(self.opts), int(apply_nonzero), tol,
                                                     maxit, _ptr(log)))
         return rc, log[:rc]
+
+    # ---- Fluid::MPI::SpalartAllmaras on the velocity nodes (mpi_spalart_allmaras.cpp); vectors are [n_unodes_local]
+    def sa_set_wall_points(self, pts):
+        """setup_cell_property: the vertices of the wall faces [n, dim] (empty: d = DBL_MAX)"""
+        pts = np.ascontiguousarray(pts, float).reshape(-1, self.dim)
+        self._chk(self.L.ifem_sa_set_wall_points(self.h, len(pts), _ptr(pts)))
+
+    def sa_wall_distance(self):
+        out = np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_get_wall_distance(self.h, _ptr(out)))
+        return out
+
+    def sa_set_constraints(self, which, nodes, vals=None):
+        nodes = np.ascontiguousarray(nodes, np.int32)
+        vals = None if vals is None else np.ascontiguousarray(vals, float)
+        self._chk(self.L.ifem_sa_set_constraints(self.h, which, len(nodes), _ptr(nodes), _ptr(vals)))
+
+    def sa_vec_set(self, vec, x):
+        x = np.ascontiguousarray(x, float)
+        assert x.size == self.n_u // self.dim
+        self._chk(self.L.ifem_sa_vec_set(self.h, vec, _ptr(x)))
+
+    def sa_vec_get(self, vec):
+        x = np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_vec_get(self.h, vec, _ptr(x)))
+        return x
+
+    def sa_assemble(self, params, use_nonzero):
+        self._chk(self.L.ifem_sa_assemble(self.h, C.byref(params), int(use_nonzero)))
+
+    def sa_solve(self, use_nonzero):
+        """(FGMRES iterations, last residual)"""
+        it, res = C.c_uint32(0), C.c_double(0)
+        self._chk(self.L.ifem_sa_solve(self.h, int(use_nonzero), C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def sa_newton_step(self, params, apply_nonzero, tol=1e-6, maxit=8):
+        log = np.zeros((maxit + 1, 4))
+        rc = self._chk(self.L.ifem_sa_newton_step(self.h, C.byref(params), int(apply_nonzero), tol, maxit, _ptr(log)))
+        return rc, log[:rc]
+
+    def sa_update_eddy_viscosity(self, params):
+        out = np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_update_eddy_viscosity(self.h, C.byref(params), _ptr(out)))
+        return out
+
+    def sa_export_csr(self):
+        import scipy.sparse as sp
+        n = self.n_unodes_owned
+        rp = np.zeros(n + 1, np.int64)
+        self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), None, None))
+        col, val = np.zeros(rp[-1], np.int32), np.zeros(rp[-1])
+        self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), _ptr(col), _ptr(val)))
+        return sp.csr_matrix((val, col, rp), shape=(n, self.n_u // self.dim))
 
     def rhs_norm(self):
         v = C.c_double()

@@ -93,6 +93,7 @@ int64_t ifem_abi_sizeof(int which) {
   case 10: return sizeof(ifem_fsi_stats);
   case 11: return sizeof(ifem_comm_stats);
   case 12: return sizeof(ifem_kprof_entry);
+  case 13: return sizeof(ifem_sa_params);
   default: return -1;
   }
 }
@@ -741,6 +742,110 @@ int ifem_scns_newton_step(ifem_ctx *ctx, const ifem_scns_params *p, const ifem_s
   catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
   catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
   return outer;
+}
+
+// ---- Fluid::MPI::SpalartAllmaras (sa.hip).  A context only exists where a device does: without one the caller has none to pass.
+static void sa_need_ctx(const ifem_ctx *ctx) {
+  if (ctx) return;
+  if (ifem_device_count() <= 0) throw Error(IFEM_E_NODEVICE, "no HIP device: libifem_hip has no CPU fallback");
+  throw Error(IFEM_E_BADPARAM, "ifem_sa_*: no context");
+}
+static inline bool sa_vec_ok(int v) { return v >= 0 && v < IFEM_SA_N_VECS; }
+
+int ifem_sa_set_wall_points(ifem_ctx *ctx, int64_t n, const double *pts) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_set_wall_points(ctx, n, pts);
+  IFEM_API_END
+}
+
+int ifem_sa_get_wall_distance(ifem_ctx *ctx, double *host_out) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_check(ctx);
+  if (!host_out) throw Error(IFEM_E_BADPARAM, "ifem_sa_get_wall_distance: no output array");
+  sa_ensure(ctx);
+  IFEM_HIP_CHECK(hipMemcpyAsync(host_out, ctx->sa.wall_d.p, ctx->sa.wall_d.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_set_constraints(ctx, which, n, node, inhom);
+  IFEM_API_END
+}
+
+int ifem_sa_vec_set(ifem_ctx *ctx, int vec, const double *host) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_check(ctx);
+  if (!sa_vec_ok(vec) || !host) throw Error(IFEM_E_BADPARAM, "ifem_sa_vec_set: bad vector id or no data");
+  sa_ensure(ctx);
+  IFEM_HIP_CHECK(hipMemcpyAsync(ctx->sa.vec[vec].p, host, ctx->sa.vec[vec].n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_sa_vec_get(ifem_ctx *ctx, int vec, double *host) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_check(ctx);
+  if (!sa_vec_ok(vec) || !host) throw Error(IFEM_E_BADPARAM, "ifem_sa_vec_get: bad vector id or no output array");
+  sa_ensure(ctx);
+  IFEM_HIP_CHECK(hipMemcpyAsync(host, ctx->sa.vec[vec].p, ctx->sa.vec[vec].n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_assemble(ctx, p, use_nonzero);
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_solve(ctx, use_nonzero, iters, res);
+  IFEM_API_END
+}
+
+int ifem_sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log) {
+  int outer = 0;
+  try {
+    sa_need_ctx(ctx);
+    outer = sa_newton_step(ctx, p, apply_nonzero, tolerance, max_iterations, log);
+  }
+  catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
+  catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
+  return outer;
+}
+
+int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_update_eddy_viscosity(ctx, p, host_out);
+  IFEM_API_END
+}
+
+int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val) {
+  IFEM_API_BEGIN
+  sa_need_ctx(ctx);
+  sa_check(ctx);
+  if (!rowptr) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr: no rowptr array");
+  hipStream_t s = ctx->stream;
+  const auto rp = ctx->Auu.rowptr.download(s);
+  for (int64_t i = 0; i <= ctx->nUo; ++i) rowptr[i] = rp[i] - rp[0];
+  if (!col || !val) return IFEM_OK;
+  if (!ctx->sa.assembled) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr called before ifem_sa_assemble");
+  const auto c = ctx->Auu.col.download(s);
+  const auto v = ctx->sa.val.download(s);
+  for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
+  IFEM_API_END
 }
 
 int ifem_system_vmult(ifem_ctx *ctx, int dst, int src) {

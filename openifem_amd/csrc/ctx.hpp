@@ -131,6 +131,7 @@ struct PlanarCsr {
   // then the rows that read a ghost column; built on first use (setup.hip::build_row_split)
   DBuf<int32_t> split_rows;
   int64_t n_interior = -1, n_boundary = 0;
+  int64_t order_version = 0; // bumped when the blocks of the rows are re-ordered in place (setup.hip::reorder_uu_rows): positions taken before are stale
 };
 
 // FE tables for one (dim, kv): reference-cell shape values/gradients at the volume quadrature points.
@@ -367,6 +368,26 @@ struct GeoCache {
 
 } // namespace ifem
 
+namespace ifem {
+// Spalart-Allmaras turbulence model (sa.hip): the scalar Q_kv space is the velocity NODES, its matrix lives on the node pattern of A_uu
+// (Auu.rowptr / col, one value per block, scattered through posUU).  Allocated by the first ifem_sa_* call.
+struct SaState {
+  DBuf<double> vec[IFEM_SA_N_VECS]; // nu~: present, evaluation point, Newton update, right-hand side, each [nUl]
+  DBuf<double> val;                 // [Auu.nnzb] system matrix
+  DBuf<uint8_t> is_c[2];            // constraint objects over the nodes (0 = zero, 1 = nonzero): flag ...
+  DBuf<double> cval[2];             // ... and inhomogeneity, [nUl]
+  bool has_c[2] = {false, false};
+  DBuf<double> node_points;         // support points of the local nodes [nUl][dim] (d-linear map), built by the first ifem_sa_set_wall_points
+  DBuf<double> wall_d;              // nodal distance to the nearest wall point [nUl] (DBL_MAX without wall points)
+  BIlu ilu;                         // ILU(0) of the matrix (dim = 1)
+  DBuf<double> dinv;                // diagonal of the matrix: the Jacobi fallback of a factorisation that broke down
+  DBuf<double> V, Z, w;             // FGMRES bases (grown with the iteration count) and work vector
+  DBuf<double> xext, halo_buf;      // several ranks: ghost-extended operator input [nUl]; staging of the ghost refresh [nUl][dim]
+  bool assembled = false, ilu_ok = false;
+  int64_t val_order = -1, ilu_order = -1; // PlanarCsr::order_version of A_uu the values were scattered / the ILU(0) was analysed for
+};
+} // namespace ifem
+
 struct ifem_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -426,6 +447,7 @@ struct ifem_ctx {
   ifem::DBuf<int32_t> sm_rows;
   ifem::Hanging hang; // hanging-node lines (hanging.hip)
   ifem::FsiState fsi; // solid + scratch of the device-side FSI inputs (fsi.hip)
+  ifem::SaState sa;   // Spalart-Allmaras turbulence model on the velocity nodes (sa.hip)
   // multigrid (ifem_mg_attach): the next coarser level (not owned) and the pressure transfers to it; per-level state of
   // the S_m V-cycle: 1/diag(S_m), largest eigenvalue of D^-1 S_m, scratch vectors [nPl]
   ifem_ctx *mg_coarse = nullptr;

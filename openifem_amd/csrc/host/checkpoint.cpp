@@ -51,6 +51,8 @@ void get(std::ifstream &i, T *p, size_t n) {
 
 template <int dim>
 void FluidSolver<dim>::save_checkpoint(const int output_index) {
+  // the reference serialises the model's present_solution beside the fluid's (:624-632); this payload has no slot for it
+  if (turbulence_model) throw std::runtime_error("save_checkpoint: not supported with a turbulence model attached (its solution would be lost)");
   const int nranks = proc_grid[0] * proc_grid[1] * proc_grid[2];
   const fs::path dir(output_dir.empty() ? std::string("./") : output_dir);
   if (part_rank == 0) { // keep only the latest earlier checkpoint (:584-614)

@@ -469,6 +469,46 @@ int ifemx_nested_transfer_check(int dim, int level, int kv, double *out) {
 
 #define DISPATCH(h, expr2, expr3) (static_cast<Handle *>(h)->dim == 2 ? (expr2) : (expr3))
 
+// FluidSolver::attach_turbulence_model(name): "Spalart-Allmaras"; before setup / run
+int ifemx_attach_turbulence_model(void *hv, const char *name) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] { if (h->dim == 2) h->s2->attach_turbulence_model(name ? name : ""); else h->s3->attach_turbulence_model(name ? name : ""); });
+}
+extern "C++" {
+namespace {
+template <int dim>
+void turbulence_out(Fluid::MPI::FluidSolver<dim> &s, double *nu, double *eddy, int32_t *node, double *value, int64_t *n_lines, double *wall, int64_t *n_wall) {
+  auto *m = s.get_turbulence_model();
+  if (!m) throw std::invalid_argument("no turbulence model attached");
+  if (nu) { const auto x = m->get_present_solution(); std::memcpy(nu, x.data(), x.size() * sizeof(double)); }
+  if (eddy) { const auto x = m->get_eddy_viscosity(); std::memcpy(eddy, x.data(), x.size() * sizeof(double)); }
+  auto *sa = dynamic_cast<Fluid::MPI::SpalartAllmaras<dim> *>(m);
+  if (n_lines) *n_lines = sa ? (int64_t)sa->constraint_nodes().size() : 0;
+  if (n_wall) *n_wall = sa ? (int64_t)(sa->wall_points().size() / dim) : 0;
+  if (sa && node) std::memcpy(node, sa->constraint_nodes().data(), sa->constraint_nodes().size() * sizeof(int32_t));
+  if (sa && value) std::memcpy(value, sa->constraint_values().data(), sa->constraint_values().size() * sizeof(double));
+  if (sa && wall) std::memcpy(wall, sa->wall_points().data(), sa->wall_points().size() * sizeof(double));
+}
+} // namespace
+} // extern "C++"
+// present solution nu~ and eddy viscosity mu_t of the attached model, each [n_unodes] (either may be NULL)
+int ifemx_turbulence_solution(void *hv, double *nu, double *eddy) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    if (h->dim == 2) turbulence_out<2>(*h->s2, nu, eddy, nullptr, nullptr, nullptr, nullptr, nullptr);
+    else turbulence_out<3>(*h->s3, nu, eddy, nullptr, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+// test hook (the facade's counterpart of ifemx_constraints): what the model handed to the device -- the lines of nonzero_constraints (node, inhomogeneity) and the wall points [n_wall][dim];
+// call with NULL arrays for the counts
+int ifemx_turbulence_setup(void *hv, int32_t *node, double *value, int64_t *n_lines, double *wall, int64_t *n_wall) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    if (h->dim == 2) turbulence_out<2>(*h->s2, nullptr, nullptr, node, value, n_lines, wall, n_wall);
+    else turbulence_out<3>(*h->s3, nullptr, nullptr, node, value, n_lines, wall, n_wall);
+  });
+}
+
 int ifemx_run(void *hv) {
   auto *h = static_cast<Handle *>(hv);
   return guard([&] { if (h->dim == 2) h->s2->run(); else h->s3->run(); });

@@ -252,6 +252,11 @@ void FluidSolver<dim>::set_body_force(const std::function<double(const Point &, 
 }
 
 template <int dim>
+void FluidSolver<dim>::attach_turbulence_model(const std::string &model_name) {
+  turbulence_model.reset(TurbulenceModel<dim>::create(*this, model_name));
+}
+
+template <int dim>
 void FluidSolver<dim>::set_sigma_pml_field(const std::function<double(const Point &, const unsigned int)> &pml) {
   sigma_pml_field.reset(new std::function<double(const Point &, const unsigned int)>(pml));
 }
@@ -323,6 +328,7 @@ void FluidSolver<dim>::make_constraints() {
     mg_coarse->field_time = field_time;
     mg_coarse->make_constraints();
   }
+  if (turbulence_model) turbulence_model->make_constraints(); // (mpi_fluid_solver.cpp:276-279)
 }
 
 template <int dim>

@@ -17,6 +17,7 @@
 #include "grid.hpp"
 #include "multigrid.hpp"
 #include "parameters.hpp"
+#include "turbulence.hpp"
 
 namespace ifem_host {
 namespace Utils {
@@ -60,7 +61,7 @@ namespace MPI {
 template <int dim>
 void write_vtu_piece(const std::string &filename, const DoFTables<dim> &dofs, const std::vector<double> &solution,
                      const std::vector<double> &fsi_acc, const std::vector<double> &stress, const std::vector<int32_t> &indicator,
-                     int subdomain, std::vector<std::string> *names_out);
+                     int subdomain, std::vector<std::string> *names_out, const std::vector<double> *eddy_viscosity = nullptr);
 
 struct SolverFailure : std::runtime_error {
   int code;
@@ -80,6 +81,10 @@ public:
   // SCnsIM inputs evaluated at the quadrature points (mpi_fluid_solver.cpp:82-103, mpi_scnsim.cpp:188-197)
   void set_body_force(const std::function<double(const Point &, const unsigned int)> &);
   void set_sigma_pml_field(const std::function<double(const Point &, const unsigned int)> &);
+  // FluidSolver::attach_turbulence_model (mpi_fluid_solver.cpp:53-63): "Spalart-Allmaras"; anything else throws (ExcNotImplemented).
+  // The model follows make_constraints / initialize_system / run() of the SUPG solvers and adds eddy_viscosity to output_results
+  void attach_turbulence_model(const std::string &model_name);
+  TurbulenceModel<dim> *get_turbulence_model() const { return turbulence_model.get(); }
   // projected nodal viscous stress [dim][dim][n_unodes] of the present solution (mpi_fluid_solver.cpp:716-811)
   std::vector<double> update_stress();
   // FluidSolver::output_results (mpi_fluid_solver.cpp:491-579): fluid_<index>.<rank>.vtu (+ .pvtu and fluid.pvd on rank 0)
@@ -133,6 +138,8 @@ public:
   unsigned int last_newton_iterations = 0, last_fgmres_iterations = 0;
 
 protected:
+  friend class SpalartAllmaras<dim>;
+  std::unique_ptr<TurbulenceModel<dim>> turbulence_model;
   void check(int rc, const char *what) const;
   // the same formulation on another triangulation (a coarser multigrid level); nullptr: this family keeps no levels
   virtual std::unique_ptr<FluidSolver<dim>> make_level_solver(Triangulation<dim> &) const { return nullptr; }

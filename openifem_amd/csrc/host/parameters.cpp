@@ -100,6 +100,21 @@ AllParameters AllParameters::from_string(const std::string &text) {
   if (p.n_fluid_neumann_bcs && nids.size() != p.n_fluid_neumann_bcs) throw std::invalid_argument("Inconsistent boundary ids!");
   if (p.n_fluid_neumann_bcs && nvals.size() != p.n_fluid_neumann_bcs) throw std::invalid_argument("Inconsistent boundary values!");
   for (unsigned i = 0; i < p.n_fluid_neumann_bcs; ++i) p.fluid_neumann_bcs[(unsigned)nids[i]] = nvals[i];
+  const std::string SA = "Spalart Allmaras model";
+  p.n_spalart_allmaras_model_bcs = geti(SA, "Number of S-A model BCs", 0);
+  const auto sids = parse_list<int>(gets(SA, "S-A model boundary id", ""));
+  const auto stypes = parse_list<int>(gets(SA, "S-A model boundary types", ""));
+  if (p.n_spalart_allmaras_model_bcs && sids.size() != p.n_spalart_allmaras_model_bcs) throw std::invalid_argument("Inconsistent boundary ids!");
+  if (p.n_spalart_allmaras_model_bcs && stypes.size() != p.n_spalart_allmaras_model_bcs) throw std::invalid_argument("Inconsistent boundary values!");
+  for (unsigned i = 0; i < p.n_spalart_allmaras_model_bcs; ++i) {
+    if (stypes[i] < 0 || stypes[i] > 1) throw std::invalid_argument("S-A model boundary types must be 0 (wall) or 1 (inflow)"); // Patterns::Integer(0, 1)
+    p.spalart_allmaras_model_bcs[(unsigned)sids[i]] = (unsigned)stypes[i];
+  }
+  p.spalart_allmaras_initial_condition_coefficient = getd(SA, "Initial condition coefficient", 0.0);
+  p.spalart_allmaras_wall_function_distance = getd(SA, "Wall function effective distance", 0.0);
+  p.spalart_allmaras_image_distance = getd(SA, "Wall function image distance", 0.0);
+  if (p.spalart_allmaras_initial_condition_coefficient < 0 || p.spalart_allmaras_wall_function_distance < 0 || p.spalart_allmaras_image_distance < 0)
+    throw std::invalid_argument("Spalart Allmaras model: coefficient and distances must not be negative"); // Patterns::Double(0.0)
   if (p.fluid_velocity_degree < 1 || p.fluid_velocity_degree > 2 || p.fluid_pressure_degree != 1)
     throw std::invalid_argument("supported elements: Q2/Q1 and Q1/Q1");
   return p;

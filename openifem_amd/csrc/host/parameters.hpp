@@ -32,6 +32,11 @@ struct AllParameters {
   // subsection Fluid Neumann BCs (:243-288): id -> pressure
   unsigned n_fluid_neumann_bcs = 0;
   std::map<unsigned, double> fluid_neumann_bcs;
+  // subsection Spalart Allmaras model (:290-361): id -> type (0 wall, 1 inflow); absent section = these defaults
+  unsigned n_spalart_allmaras_model_bcs = 0;
+  std::map<unsigned, unsigned> spalart_allmaras_model_bcs;
+  double spalart_allmaras_initial_condition_coefficient = 0.0;
+  double spalart_allmaras_wall_function_distance = 0.0, spalart_allmaras_image_distance = 0.0;
 
   AllParameters() = default;
   explicit AllParameters(const std::string &infile);

@@ -45,6 +45,7 @@ template <int dim>
 void SUPGFluidSolver<dim>::initialize_system() {
   FluidSolver<dim>::initialize_system();
   upload_fields();
+  if (this->turbulence_model) this->turbulence_model->initialize_system(); // (mpi_supg_solver.cpp:290-293)
 }
 
 template <int dim>
@@ -104,9 +105,11 @@ void SUPGFluidSolver<dim>::run() {
     this->setup_dofs();
     this->make_constraints();
     this->initialize_system();
+    if (this->turbulence_model) this->turbulence_model->run_one_step(true); // (:456-463)
     run_one_step(true);
   }
   while (time.end() - time.current() > 1e-12) {
+    if (this->turbulence_model) this->turbulence_model->run_one_step(false); // (:466-469)
     if (!this->hard_coded_boundary_values.empty()) {
       this->field_time += time.get_delta_t();
       this->make_constraints();

@@ -61,6 +61,16 @@ void constraint_set_identity(ifem_ctx *ctx, int which, bool differs_self, bool d
 void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonzero);
 void launch_update_stress(ifem_ctx *ctx, double mu);
 
+// sa.hip -- Fluid::MPI::SpalartAllmaras (mpi_spalart_allmaras.cpp) on the velocity nodes; state in ctx->sa
+void sa_check(ifem_ctx *ctx);  // refuses what the model does not cover (hanging-node lines)
+void sa_ensure(ifem_ctx *ctx); // allocates the state on first use
+void sa_set_wall_points(ifem_ctx *ctx, int64_t n_pts, const double *pts);
+void sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom);
+void sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero);
+void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out);
+int sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log);
+void sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
+
 // linalg.hip -- all on ctx->stream.  Block vectors are [u (dim*nUl) | p (nPl)]; "owned" ranges only.
 struct VecLayout {
   int64_t n_u_owned; // dim*nUo

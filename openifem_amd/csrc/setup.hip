@@ -207,6 +207,7 @@ static void reorder_uu_rows(ifem_ctx *ctx) {
   IFEM_HIP_CHECK(hipMemcpyAsync(M.col.p, col2.p, (size_t)nnzb * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   IFEM_HIP_CHECK(hipStreamSynchronize(s));
   IFEM_HIP_CHECK(hipGetLastError());
+  ++M.order_version;
   M.n_interior = -1; // a row list built from the old order stays valid (it lists rows), but keep the invariant simple
   ctx->scat3.release(); // records of the old order
   ctx->hdr3_rows = false;

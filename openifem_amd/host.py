@@ -74,6 +74,9 @@ def _lib():
     L.ifemx_box_injection.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.ifemx_box_injection_partial.argtypes = L.ifemx_box_injection.argtypes
     L.ifemx_nested_transfer_check.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.ifemx_attach_turbulence_model.argtypes = [C.c_void_p, C.c_char_p]
+    L.ifemx_turbulence_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifemx_turbulence_setup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
     L.ifemx_channel_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_double]
     L._ifemx_bound = True
     return L
@@ -141,6 +144,26 @@ class FluidSolver:
 
     def set_initial_condition(self, fn):
         self._field(self.L.ifemx_set_initial_condition, fn)
+
+    def attach_turbulence_model(self, name):
+        """FluidSolver::attach_turbulence_model: "Spalart-Allmaras" (anything else raises); call before setup() / run()"""
+        self._chk(self.L.ifemx_attach_turbulence_model(self.h, name.encode()))
+
+    def turbulence_solution(self):
+        """(nu~, mu_t) of the attached model on the velocity nodes"""
+        n = self.sizes()[1] // self.dim
+        nu, eddy = np.zeros(n), np.zeros(n)
+        self._chk(self.L.ifemx_turbulence_solution(self.h, nu.ctypes.data_as(C.c_void_p), eddy.ctypes.data_as(C.c_void_p)))
+        return nu, eddy
+
+    def turbulence_setup(self):
+        """what the attached model handed to the device: (constrained nodes, their inhomogeneities, wall points [n, dim])"""
+        nl, nw = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.ifemx_turbulence_setup(self.h, None, None, C.byref(nl), None, C.byref(nw)))
+        node, val, wall = np.zeros(nl.value, np.int32), np.zeros(nl.value), np.zeros((nw.value, self.dim))
+        self._chk(self.L.ifemx_turbulence_setup(self.h, node.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), C.byref(nl),
+                                                wall.ctypes.data_as(C.c_void_p), C.byref(nw)))
+        return node, val, wall
 
     def update_stress(self):
         _, n_u, _ = self.sizes()
