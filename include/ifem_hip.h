@@ -482,7 +482,8 @@ enum { IFEM_SA_PRESENT = 0, IFEM_SA_EVAL = 1, IFEM_SA_UPDATE = 2, IFEM_SA_RHS = 
 int ifem_sa_set_wall_points(ifem_ctx *ctx, int64_t n, const double *pts);
 int ifem_sa_get_wall_distance(ifem_ctx *ctx, double *host_out); /* [n_unodes_local] */
 /* SpalartAllmaras::make_constraints (:348-406): Dirichlet lines nu~[node[i]] = inhom[i] of constraint object `which`
- * (0 = zero_constraints: inhom ignored, 1 = nonzero_constraints; inhom NULL = 0).  Replaces the object. */
+ * (0 = zero_constraints: inhom ignored, 1 = nonzero_constraints; inhom NULL = 0).  Replaces the object.  A node listed twice
+ * keeps its LAST line, as a dof of ifem_set_constraints does. */
 int ifem_sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom);
 /* present_solution / evaluation_point / newton_update / system_rhs of the model, [n_unodes_local] */
 int ifem_sa_vec_set(ifem_ctx *ctx, int vec, const double *host);

@@ -32,7 +32,62 @@ __global__ void k_constraint_scatter(int32_t n, const int32_t *dof, const double
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   flag[dof[i]] = 1;
-  cval[dof[i]] = val ? val[i] : 0.0;
+  cval[dof[i]] = val[i];
+}
+
+// Only the n lines cross the bus; flags and inhomogeneities over [0, N) are built on the device (FSI re-makes the constraints every
+// time step, mpi_fsi.cpp:1191: at 128^3 the dense host arrays were 480 MB per call).  See kernels.hpp.
+bool build_line_set(ifem_ctx *ctx, size_t N, int32_t n, const int32_t *idx, const double *val, std::vector<int32_t> &kept_idx,
+                    std::vector<double> &kept_val, DBuf<uint8_t> &flag, DBuf<double> &cval) {
+  kept_idx.clear(); kept_val.clear();
+  kept_idx.reserve((size_t)n); kept_val.reserve((size_t)n);
+  std::vector<uint8_t> &seen = ctx->seen_scratch; // all zero between calls
+  if (seen.size() < N) seen.assign(N, 0);
+  bool in_range = true;
+  for (int32_t i = n - 1; i >= 0; --i) {
+    const int32_t d = idx[i];
+    if (d < 0 || (size_t)d >= N) { in_range = false; break; }
+    if (seen[d]) continue;
+    seen[d] = 1;
+    kept_idx.push_back(d);
+    kept_val.push_back(val ? val[i] : 0.0);
+  }
+  for (int32_t d : kept_idx) seen[d] = 0;
+  if (!in_range) return false;
+  hipStream_t s = ctx->stream;
+  flag.alloc(N);
+  cval.alloc(N);
+  if (N) {
+    IFEM_HIP_CHECK(hipMemsetAsync(flag.p, 0, N, s));
+    IFEM_HIP_CHECK(hipMemsetAsync(cval.p, 0, N * sizeof(double), s));
+  }
+  if (!kept_idx.empty()) {
+    DBuf<int32_t> d_idx;
+    DBuf<double> d_val;
+    d_idx.upload(kept_idx.data(), kept_idx.size(), s);
+    d_val.upload(kept_val.data(), kept_val.size(), s);
+    hipLaunchKernelGGL(k_constraint_scatter, dim3((unsigned)((kept_idx.size() + 255) / 256)), dim3(256), 0, s, (int32_t)kept_idx.size(), d_idx.p, d_val.p, flag.p, cval.p);
+    IFEM_HIP_CHECK(hipGetLastError());
+    IFEM_HIP_CHECK(hipStreamSynchronize(s)); // d_idx, d_val are released on return
+  }
+  return true;
+}
+
+// the loop of run_one_step in the three solvers (its head: mpi_insim.cpp:420-427, mpi_supg_solver.cpp:354-355, mpi_spalart_allmaras.cpp:296-297).
+// See kernels.hpp.
+int newton_loop(double floor, int apply_nonzero, double tolerance, int max_iterations, double *log, const std::function<NewtonIter(int)> &iteration) {
+  int outer = 0;
+  double cur = 1.0, init = 1.0, rel = 1.0;
+  while (rel > tolerance && cur > floor) {
+    if (outer >= max_iterations) throw Error(IFEM_E_NEWTON_MAXIT, "Too many Newton iterations!");
+    const NewtonIter it = iteration(apply_nonzero && outer == 0);
+    cur = it.rhs_norm;
+    if (outer == 0) init = cur;
+    rel = cur / init;
+    if (log) { log[outer * 4 + 0] = cur; log[outer * 4 + 1] = rel; log[outer * 4 + 2] = it.log2; log[outer * 4 + 3] = it.log3; }
+    ++outer;
+  }
+  return outer;
 }
 
 // out[k] = 1 when the flag arrays of pair k differ somewhere (a never-set array differs from everything), compared on the
@@ -71,6 +126,21 @@ std::vector<T> download_range(const ifem::DBuf<T> &b, int64_t off, int64_t count
     IFEM_HIP_CHECK(hipStreamSynchronize(s));
   }
   return h;
+}
+
+// the caller's options, or the defaults
+ifem_solver_opts opts_or_default(const ifem_solver_opts *o) {
+  ifem_solver_opts d;
+  if (o) d = *o; else ifem_default_solver_opts(&d);
+  return d;
+}
+
+// entry points that return a count (>= 0) instead of IFEM_OK
+template <class Body>
+int api_count(Body &&body) {
+  try { return body(); }
+  catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
+  catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
 }
 } // namespace
 
@@ -257,28 +327,15 @@ int ifem_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *dof
   IFEM_API_BEGIN
   if (which < 0 || which > 1) throw Error(IFEM_E_BADPARAM, "which must be 0 or 1");
   if (n < 0 || (n > 0 && !dof)) throw Error(IFEM_E_BADPARAM, "bad constraint list");
-  // Only the n lines cross the bus; flags and inhomogeneities over the local dofs are built and compared on the device
-  // (FSI re-makes the constraints every time step, mpi_fsi.cpp:1191: at 128^3 the dense host arrays were 480 MB per call).
   // A dof listed twice keeps its LAST line, as the sequential host loop did.
   const size_t N = (size_t)ctx->n_local;
   std::vector<int32_t> kd;
   std::vector<double> kv;
-  kd.reserve((size_t)n);
-  kv.reserve((size_t)n);
+  DBuf<uint8_t> nf;
+  DBuf<double> nv;
   {
-    std::vector<uint8_t> &seen = ctx->seen_scratch; // all zero between calls
-    if (seen.size() != N) seen.assign(N, 0);
-    int32_t bad = 0;
-    for (int32_t i = n - 1; i >= 0; --i) {
-      const int32_t d = dof[i];
-      if (d < 0 || (size_t)d >= N) { bad = 1; break; }
-      if (d >= ctx->dim * ctx->nUl) { bad = 2; break; }
-      if (seen[d]) continue;
-      seen[d] = 1;
-      kd.push_back(d);
-      kv.push_back(inhom ? inhom[i] : 0.0);
-    }
-    for (int32_t d : kd) seen[d] = 0;
+    int bad = build_line_set(ctx, N, n, dof, inhom, kd, kv, nf, nv) ? 0 : 1;
+    for (int32_t d : kd) if (d >= ctx->dim * ctx->nUl) { bad = 2; break; } // (seen before the line that left the range: the walk runs from the back)
     // the call is collective on partitioned contexts (constraint_set_identity all-reduces): every rank must fail together,
     // or the ranks with good lists would wait in that all-reduce for the one that threw
     double worst = bad;
@@ -286,25 +343,9 @@ int ifem_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *dof
     if (worst == 1.0) throw Error(IFEM_E_BADPARAM, bad == 1 ? "constraint dof out of range" : "constraint dof out of range on another rank");
     if (worst == 2.0) throw Error(IFEM_E_BADPARAM, "pressure Dirichlet constraints are not supported");
   }
-  hipStream_t s = ctx->stream;
-  DBuf<int32_t> d_dof;
-  DBuf<double> d_val;
-  DBuf<uint8_t> nf;
-  DBuf<double> nv;
-  nf.alloc(N);
-  nv.alloc(N);
-  if (N) {
-    IFEM_HIP_CHECK(hipMemsetAsync(nf.p, 0, N, s));
-    IFEM_HIP_CHECK(hipMemsetAsync(nv.p, 0, N * sizeof(double), s));
-  }
-  if (!kd.empty()) {
-    d_dof.upload(kd.data(), kd.size(), s);
-    d_val.upload(kv.data(), kv.size(), s);
-    hipLaunchKernelGGL(k_constraint_scatter, dim3((unsigned)((kd.size() + 255) / 256)), dim3(256), 0, s, (int32_t)kd.size(), d_dof.p, d_val.p, nf.p, nv.p);
-  }
   const DBuf<uint8_t> *pa[2] = {&nf, &nf}, *pb[2] = {&ctx->is_c[which], &ctx->is_c[1 - which]};
   double differs[2];
-  flags_differ(ctx, 2, pa, pb, differs); // synchronises: the host lists may go away
+  flags_differ(ctx, 2, pa, pb, differs);
   ctx->is_c[which].swap(nf);
   ctx->cval[which].swap(nv);
   ctx->has_c[which] = !kd.empty();
@@ -589,20 +630,19 @@ int ifem_imex_assemble(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero,
   IFEM_API_END
 }
 
-static int imex_solve_impl(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
-  ifem_solver_opts oo;
-  if (o) oo = *o; else { ifem_default_solver_opts(&oo); oo.inner_rel = 1e-4; }
+static void imex_solve_impl(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
+  ifem_solver_opts oo = opts_or_default(o);
+  if (!o) oo.inner_rel = 1e-4;
   const double bn = norm2_owned(ctx, IFEM_VEC_RHS);
   oo.fgmres_rel = 0.0;
   oo.fgmres_abs = std::min(1e-9, 1e-8 * bn); // mpi_insimex.cpp:369-370
-  return ins_solve(ctx, p, &oo, use_nonzero, stats);
+  ins_solve(ctx, p, &oo, use_nonzero, stats);
 }
 
 int ifem_imex_solve(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
   IFEM_API_BEGIN
   if (!p) throw Error(IFEM_E_BADPARAM, "null params");
-  const int rc = imex_solve_impl(ctx, p, o, use_nonzero, stats);
-  if (rc != 0) { g_err = "FGMRES did not converge (SolverControl::NoConvergence)"; return rc; }
+  imex_solve_impl(ctx, p, o, use_nonzero, stats);
   IFEM_API_END
 }
 
@@ -612,8 +652,7 @@ int ifem_imex_step(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_op
   if (!p || p->dt <= 0) throw Error(IFEM_E_BADPARAM, "bad ifem_ins_params");
   v_zero(ctx, ctx->n_local, ctx->vec[IFEM_VEC_UPDATE].p); // solution_time_increment = 0
   launch_ins_assemble_ex(ctx, p, apply_nonzero, 1, assemble_system ? AsmMode::Full : AsmMode::Rhs);
-  const int rc = imex_solve_impl(ctx, p, o, apply_nonzero, stats);
-  if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
+  imex_solve_impl(ctx, p, o, apply_nonzero, stats);
   copy_owned(ctx, IFEM_VEC_PRESENT, IFEM_VEC_UPDATE, 1.0, 1.0); // present_solution += solution_time_increment
   launch_update_stress(ctx, p->viscosity);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -622,47 +661,38 @@ int ifem_imex_step(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_op
 
 int ifem_solve(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
   IFEM_API_BEGIN
-  ifem_solver_opts def;
-  if (!o) { ifem_default_solver_opts(&def); o = &def; }
-  const int rc = ins_solve(ctx, p, o, use_nonzero, stats);
-  if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
+  const ifem_solver_opts oo = opts_or_default(o);
+  ins_solve(ctx, p, &oo, use_nonzero, stats);
   IFEM_API_END
 }
 
 int ifem_rhs_norm(ifem_ctx *ctx, double *l2) { return ifem_vec_norm2(ctx, IFEM_VEC_RHS, l2); }
 
+// solution_increment = present - evaluation; present = evaluation (:465-473)
+static void fluid_newton_accept(ifem_ctx *ctx) {
+  copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_PRESENT, 1.0, 0.0);
+  copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_EVAL, -1.0, 1.0);
+  copy_owned(ctx, IFEM_VEC_PRESENT, IFEM_VEC_EVAL, 1.0, 0.0);
+}
+
 int ifem_ins_newton_step(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int apply_nonzero,
                          double tolerance, int max_iterations, double *log) {
-  int outer = 0;
-  try {
-    ifem_solver_opts def;
-    if (!o) { ifem_default_solver_opts(&def); o = &def; }
-    double cur = 1.0, init = 1.0, rel = 1.0;
+  return api_count([&] {
+    const ifem_solver_opts oo = opts_or_default(o);
     copy_owned(ctx, IFEM_VEC_EVAL, IFEM_VEC_PRESENT, 1.0, 0.0); // evaluation_point = present_solution (:420)
-    while (rel > tolerance && cur > 1e-11) {
-      if (outer >= max_iterations) throw Error(IFEM_E_NEWTON_MAXIT, "Too many Newton iterations!");
-      const int nz = apply_nonzero && outer == 0;
+    const int outer = newton_loop(1e-11, apply_nonzero, tolerance, max_iterations, log, [&](int nz) {
+      ifem_solve_stats st{};
       v_zero(ctx, ctx->n_local, ctx->vec[IFEM_VEC_UPDATE].p); // newton_update = 0 (:427)
       launch_ins_assemble_ex(ctx, p, nz, 0, AsmMode::Full);
-      ifem_solve_stats st{};
-      const int rc = ins_solve(ctx, p, o, nz, &st);
-      if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
-      cur = norm2_owned(ctx, IFEM_VEC_RHS);                      // system_rhs.l2_norm() (:438)
+      ins_solve(ctx, p, &oo, nz, &st);
+      const double cur = norm2_owned(ctx, IFEM_VEC_RHS);         // system_rhs.l2_norm() (:438)
       copy_owned(ctx, IFEM_VEC_EVAL, IFEM_VEC_UPDATE, 1.0, 1.0); // evaluation_point += newton_update (:444-448)
-      if (outer == 0) init = cur;
-      rel = cur / init;
-      if (log) { log[outer * 4 + 0] = cur; log[outer * 4 + 1] = rel; log[outer * 4 + 2] = st.fgmres_iters; log[outer * 4 + 3] = st.fgmres_res; }
-      ++outer;
-    }
-    // solution_increment = present - evaluation; present = evaluation (:465-473)
-    copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_PRESENT, 1.0, 0.0);
-    copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_EVAL, -1.0, 1.0);
-    copy_owned(ctx, IFEM_VEC_PRESENT, IFEM_VEC_EVAL, 1.0, 0.0);
+      return NewtonIter{cur, double(st.fgmres_iters), st.fgmres_res};
+    });
+    fluid_newton_accept(ctx);
     IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  }
-  catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
-  catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
-  return outer;
+    return outer;
+  });
 }
 
 int ifem_set_scns_fields(ifem_ctx *ctx, const double *sigma_pml, const double *body_force, const double *fsi_stress) {
@@ -703,45 +733,30 @@ int ifem_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonzero
 
 int ifem_scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
   IFEM_API_BEGIN
-  ifem_solver_opts def;
-  if (!o) { ifem_default_solver_opts(&def); o = &def; }
-  const int rc = scns_solve(ctx, o, use_nonzero, stats);
-  if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
+  const ifem_solver_opts oo = opts_or_default(o);
+  scns_solve(ctx, &oo, use_nonzero, stats);
   IFEM_API_END
 }
 
 int ifem_scns_newton_step(ifem_ctx *ctx, const ifem_scns_params *p, const ifem_solver_opts *o, int apply_nonzero,
                           double tolerance, int max_iterations, double *log) {
-  int outer = 0;
-  try {
-    ifem_solver_opts def;
-    if (!o) { ifem_default_solver_opts(&def); o = &def; }
-    double cur = 1.0, init = 1.0, rel = 1.0;
+  return api_count([&] {
+    const ifem_solver_opts oo = opts_or_default(o);
     copy_owned(ctx, IFEM_VEC_EVAL, IFEM_VEC_PRESENT, 1.0, 0.0);
-    while (rel > tolerance && cur > 1e-14) { // mpi_supg_solver.cpp:354-355
-      if (outer >= max_iterations) throw Error(IFEM_E_NEWTON_MAXIT, "Too many Newton iterations!");
-      const int nz = apply_nonzero && outer == 0;
+    const int outer = newton_loop(1e-14, apply_nonzero, tolerance, max_iterations, log, [&](int nz) { // mpi_supg_solver.cpp:354-355
+      ifem_solve_stats st{};
       v_zero(ctx, ctx->n_local, ctx->vec[IFEM_VEC_UPDATE].p);
       launch_scns_assemble(ctx, p, nz);
-      ifem_solve_stats st{};
-      const int rc = scns_solve(ctx, o, nz, &st);
-      if (rc != 0) throw Error(rc, "FGMRES did not converge (SolverControl::NoConvergence)");
-      cur = norm2_owned(ctx, IFEM_VEC_RHS);
+      scns_solve(ctx, &oo, nz, &st);
+      const double cur = norm2_owned(ctx, IFEM_VEC_RHS);
       copy_owned(ctx, IFEM_VEC_EVAL, IFEM_VEC_UPDATE, 1.0, 1.0);
-      if (outer == 0) init = cur;
-      rel = cur / init;
-      if (log) { log[outer * 4 + 0] = cur; log[outer * 4 + 1] = rel; log[outer * 4 + 2] = st.fgmres_iters; log[outer * 4 + 3] = st.inner_iters; }
-      ++outer;
-    }
-    copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_PRESENT, 1.0, 0.0);
-    copy_owned(ctx, IFEM_VEC_INCREMENT, IFEM_VEC_EVAL, -1.0, 1.0);
-    copy_owned(ctx, IFEM_VEC_PRESENT, IFEM_VEC_EVAL, 1.0, 0.0);
+      return NewtonIter{cur, double(st.fgmres_iters), double(st.inner_iters)};
+    });
+    fluid_newton_accept(ctx);
     launch_update_stress(ctx, p->viscosity); // update_stress() (:396), feeds the next assemble
     IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  }
-  catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
-  catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
-  return outer;
+    return outer;
+  });
 }
 
 // ---- Fluid::MPI::SpalartAllmaras (sa.hip).  A context only exists where a device does: without one the caller has none to pass.
@@ -815,14 +830,10 @@ int ifem_sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res) 
 }
 
 int ifem_sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log) {
-  int outer = 0;
-  try {
+  return api_count([&] {
     sa_need_ctx(ctx);
-    outer = sa_newton_step(ctx, p, apply_nonzero, tolerance, max_iterations, log);
-  }
-  catch (const ifem::Error &e) { g_err = e.what(); return e.code; }
-  catch (const std::exception &e) { g_err = e.what(); return IFEM_E_HIP; }
-  return outer;
+    return sa_newton_step(ctx, p, apply_nonzero, tolerance, max_iterations, log);
+  });
 }
 
 int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out) {
@@ -1091,9 +1102,8 @@ int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double 
 int ifem_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int dst, int src) {
   IFEM_API_BEGIN
   if (!vec_ok(dst) || !vec_ok(src) || is_ext(dst) || is_ext(src)) throw Error(IFEM_E_BADPARAM, "use non-ghosted vectors");
-  ifem_solver_opts def;
-  if (!o) { ifem_default_solver_opts(&def); o = &def; }
-  ins_precond_vmult(ctx, p, o, ctx->vec[src].p, ctx->vec[dst].p);
+  const ifem_solver_opts oo = opts_or_default(o);
+  ins_precond_vmult(ctx, p, &oo, ctx->vec[src].p, ctx->vec[dst].p);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
 }
@@ -1158,67 +1168,10 @@ int ifem_tpp_override(ifem_ctx *ctx, const double *val) {
   IFEM_API_END
 }
 
-int ifem_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val) {
-  IFEM_API_BEGIN
-  hipStream_t s = ctx->stream;
-  const int dim = ctx->dim;
-  const int64_t nuo = dim * ctx->nUo, npo = ctx->nPo, n = nuo + npo, poff = dim * ctx->nUl;
-  auto rpA = ctx->Auu.rowptr.download(s), rpT = ctx->Bt.rowptr.download(s), rpB = ctx->B.rowptr.download(s),
-       rpM = ctx->Mp.rowptr.download(s);
-  std::vector<double> vApp;
-  if (ctx->has_app) vApp = ctx->App.download(s);
-  // pattern: [A_uu | B^T ; B | M_p-pattern]  (explicit zeros kept so that both `which` share one pattern)
-  rowptr[0] = 0;
-  for (int64_t A = 0; A < ctx->nUo; ++A)
-    for (int c = 0; c < dim; ++c) rowptr[A * dim + c + 1] = (rpA[A + 1] - rpA[A]) * dim + (rpT[A + 1] - rpT[A]);
-  for (int64_t i = 0; i < npo; ++i) rowptr[nuo + i + 1] = (rpB[i + 1] - rpB[i]) * dim + (rpM[i + 1] - rpM[i]);
-  for (int64_t i = 0; i < n; ++i) rowptr[i + 1] += rowptr[i];
-  if (!col || !val) return IFEM_OK;
-  auto cA = ctx->Auu.col.download(s), cT = ctx->Bt.col.download(s), cB = ctx->B.col.download(s), cM = ctx->Mp.col.download(s);
-  std::vector<double> vA;
-  if (which == 0) vA = stored_uu(ctx).download(s);
-  auto vT = ctx->Bt.val.download(s), vB = ctx->B.val.download(s), vM = ctx->Mp.val.download(s);
-  auto dM = ctx->diagMu.download(s);
-  for (int64_t A = 0; A < ctx->nUo; ++A) {
-    const int64_t rs = rpA[A], len = rpA[A + 1] - rs, ts = rpT[A], tlen = rpT[A + 1] - ts;
-    for (int c = 0; c < dim; ++c) {
-      int64_t o = rowptr[A * dim + c];
-      for (int64_t k = 0; k < len; ++k)
-        for (int d = 0; d < dim; ++d) {
-          col[o] = cA[rs + k] * dim + d;
-          if (which == 0) val[o] = vA[uu_base(rs, len, k, dim * dim) + (c * dim + d) * uu_estride(len)];
-          else val[o] = (cA[rs + k] == A && c == d) ? dM[A * dim + c] : 0.0;
-          ++o;
-        }
-      for (int64_t k = 0; k < tlen; ++k) {
-        col[o] = int32_t(poff + cT[ts + k]);
-        val[o] = (which == 0) ? vT[ts * dim + c * tlen + k] : 0.0;
-        ++o;
-      }
-    }
-  }
-  for (int64_t i = 0; i < npo; ++i) {
-    const int64_t rs = rpB[i], len = rpB[i + 1] - rs, ms = rpM[i], mlen = rpM[i + 1] - ms;
-    int64_t o = rowptr[nuo + i];
-    for (int64_t k = 0; k < len; ++k)
-      for (int d = 0; d < dim; ++d) {
-        col[o] = cB[rs + k] * dim + d;
-        val[o] = (which == 0) ? vB[rs * dim + d * len + k] : 0.0;
-        ++o;
-      }
-    for (int64_t k = 0; k < mlen; ++k) {
-      col[o] = int32_t(poff + cM[ms + k]);
-      val[o] = (which == 0) ? (ctx->has_app ? vApp[ms + k] : 0.0) : vM[ms + k];
-      ++o;
-    }
-  }
-  IFEM_API_END
-}
-
-// rows [row0, row0 + nrows) of the CSR ifem_export_csr describes, downloading only the slices of the device arrays those rows own
-// (the whole A_uu of the 128^3 channel is 78 GB: ifem_export_csr cannot be called there)
-int ifem_export_rows(ifem_ctx *ctx, int which, int64_t row0, int64_t nrows, int64_t *rowptr, int32_t *col, double *val) {
-  IFEM_API_BEGIN
+// rows [row0, row0 + nrows) of the local system as CSR, pattern [A_uu | B^T ; B | M_p-pattern] (explicit zeros kept so that both `which`
+// share one pattern), downloading only the slices of the device arrays those rows own (the whole A_uu of the 128^3 channel is 78 GB:
+// ifem_export_csr cannot be called there)
+static void export_rows(ifem_ctx *ctx, int which, int64_t row0, int64_t nrows, int64_t *rowptr, int32_t *col, double *val) {
   hipStream_t s = ctx->stream;
   const int dim = ctx->dim, bs = dim * dim;
   const int64_t nuo = dim * ctx->nUo, npo = ctx->nPo, n = nuo + npo, poff = dim * ctx->nUl;
@@ -1295,6 +1248,18 @@ int ifem_export_rows(ifem_ctx *ctx, int which, int64_t row0, int64_t nrows, int6
       }
     }
   }
+}
+
+int ifem_export_rows(ifem_ctx *ctx, int which, int64_t row0, int64_t nrows, int64_t *rowptr, int32_t *col, double *val) {
+  IFEM_API_BEGIN
+  export_rows(ctx, which, row0, nrows, rowptr, col, val);
+  IFEM_API_END
+}
+
+// the whole local system: the slab [0, n)
+int ifem_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val) {
+  IFEM_API_BEGIN
+  export_rows(ctx, which, 0, int64_t(ctx->dim) * ctx->nUo + ctx->nPo, rowptr, col, val);
   IFEM_API_END
 }
 

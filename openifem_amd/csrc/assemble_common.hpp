@@ -1,6 +1,6 @@
-// assemble_common.hpp -- argument block and small helpers shared by the InsIM assembly kernels (assemble.hip: first
-// version with the physical-gradient table in LDS; assemble2.hip: quadrature-point-outer version with register
-// accumulators).
+// assemble_common.hpp -- argument block and small helpers shared by the InsIM assembly driver (assemble.hip) and its cell
+// kernels (assemble3.hip: 3D Q2/Q1 on the FP64 matrix cores; assemble2.hip: every other (dim, kv), quadrature-point-outer with
+// register accumulators); Geo and the small inverses also serve assemble_scns.hip and sa.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>

@@ -401,6 +401,34 @@ void halo_exchange(ifem_ctx *ctx, double *xu_ext) {
   exchange(ctx, xu_ext, 0);
 }
 
+// nodal planes f[nf][n] <-> the interleaved [node][dim] layout the velocity halo plan moves (components nf.. are zero padding); only owned
+// entries are sent and only ghost entries [n_owned, n) are written back
+__global__ void k_nodal_pack(int64_t n_owned, int64_t n, int dim, int nf, const double *__restrict__ f, double *__restrict__ buf) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n_owned) return;
+  for (int c = 0; c < dim; ++c) buf[i * dim + c] = c < nf ? f[int64_t(c) * n + i] : 0.0;
+}
+__global__ void k_nodal_unpack(int64_t n_owned, int64_t n, int dim, int nf, const double *__restrict__ buf, double *__restrict__ f) {
+  const int64_t i = n_owned + int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (int c = 0; c < nf; ++c) f[int64_t(c) * n + i] = buf[i * dim + c];
+}
+
+void halo_refresh_nodal(ifem_ctx *ctx, int nplanes, double *f) {
+  Halo &h = ctx->halo;
+  if (h.nranks == 1) return;
+  const int dim = ctx->dim;
+  const int64_t n = ctx->nUl, no = ctx->nUo;
+  if (h.nodal_buf.n != (size_t)n * dim) h.nodal_buf.alloc((size_t)n * dim);
+  for (int c0 = 0; c0 < nplanes; c0 += dim) {
+    const int nf = std::min(dim, nplanes - c0);
+    double *fc = f + int64_t(c0) * n;
+    if (no > 0) hipLaunchKernelGGL(k_nodal_pack, dim3(unsigned((no + 255) / 256)), dim3(256), 0, ctx->stream, no, n, dim, nf, fc, h.nodal_buf.p);
+    exchange(ctx, h.nodal_buf.p, 0);
+    if (n > no) hipLaunchKernelGGL(k_nodal_unpack, dim3(unsigned((n - no + 255) / 256)), dim3(256), 0, ctx->stream, no, n, dim, nf, h.nodal_buf.p, fc);
+  }
+}
+
 void halo_exchange_s(ifem_ctx *ctx, double *xs_ext) {
   if (ctx->halo.nranks == 1) return;
   if (!ctx->halo.has_s) throw Error(IFEM_E_BADPARAM, "no 2-deep pressure halo plan in this context");

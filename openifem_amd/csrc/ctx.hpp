@@ -163,6 +163,7 @@ struct Halo {
   int64_t n_s_cols = 0; // nPo + far nodes
   bool has_s = false;
   DBuf<double> sendbuf;
+  DBuf<double> nodal_buf; // staging of halo_refresh_nodal [nUl][dim], allocated by its first call
   void *comm = nullptr;  // ncclComm_t
   // overlapped exchanges (halo_start / halo_wait): a second communicator (ncclCommSplit of `comm`) whose send/recv groups
   // run on `hstream` (high priority) while the context stream works on the rows / cells that need no ghost value
@@ -382,7 +383,7 @@ struct SaState {
   BIlu ilu;                         // ILU(0) of the matrix (dim = 1)
   DBuf<double> dinv;                // diagonal of the matrix: the Jacobi fallback of a factorisation that broke down
   DBuf<double> V, Z, w;             // FGMRES bases (grown with the iteration count) and work vector
-  DBuf<double> xext, halo_buf;      // several ranks: ghost-extended operator input [nUl]; staging of the ghost refresh [nUl][dim]
+  DBuf<double> xext;                // several ranks: ghost-extended operator input [nUl]
   bool assembled = false, ilu_ok = false;
   int64_t val_order = -1, ilu_order = -1; // PlanarCsr::order_version of A_uu the values were scattered / the ILU(0) was analysed for
 };
@@ -437,7 +438,7 @@ struct ifem_ctx {
   // re-making identical constraints (time-dependent boundary values) keeps it
   // (decided by comparing the flag arrays on the device, api.hip::flags_differ)
   int64_t flag_id[2] = {0, 0}, flag_counter = 0;
-  std::vector<uint8_t> seen_scratch; // ifem_set_constraints: duplicate detection over the local dofs, all zero between calls
+  std::vector<uint8_t> seen_scratch; // api.hip::build_line_set: duplicate detection over the local dofs / nodes, all zero between calls
   // scalar velocity operator S^ = mu K + rho C(u) + rho/dt M on the A_uu block pattern (IFEM_AINV_SCALAR_*)
   ifem::DBuf<double> Shat, shat_dinv;
   ifem::F32Copy Shat_f32;

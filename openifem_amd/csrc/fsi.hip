@@ -504,18 +504,6 @@ __global__ void k_fsi_mark(int32_t n, const int32_t *dof, uint8_t *taken) {
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) taken[dof[i]] = 1;
 }
-// scalar nodal fields <-> the velocity-layout buffer the halo exchange moves ([node][dim]); unpack writes ghosts only
-__global__ void k_fsi_pack(int64_t n, int dim, int nf, const double *f, double *buf) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  for (int c = 0; c < dim; ++c) buf[i * dim + c] = c < nf ? f[(size_t)c * n + i] : 0.0;
-}
-__global__ void k_fsi_unpack(int64_t n, int64_t n_owned, int dim, int nf, const double *buf, double *f) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + n_owned;
-  if (i >= n) return;
-  for (int c = 0; c < nf; ++c) f[(size_t)c * n + i] = buf[i * dim + c];
-}
-
 // Dirichlet lines of ghost dofs are the owner's: flags / inhomogeneities travel as doubles in the velocity layout
 __global__ void k_fsi_lines_pack(int64_t n, int what, const uint8_t *is_c1, const double *cval1, double *buf) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -973,18 +961,7 @@ void fsi_find_fluid_bc(ifem_ctx *ctx, double dt, int use_dirichlet_bc, const int
   }
   if (ctx->halo.nranks > 1) { // ghosts take the owner's values (fsi_acceleration and fsi_stress are ghosted vectors)
     if (!use_dirichlet_bc) halo_exchange(ctx, ctx->vec[IFEM_VEC_FSI_ACC].p);
-    if (F.has_stress) {
-      DBuf<double> buf;
-      buf.alloc((size_t)dim * nUl);
-      for (int c0 = 0; c0 < ncomp; c0 += dim) {
-        const int nf_ = std::min(dim, ncomp - c0);
-        hipLaunchKernelGGL(k_fsi_pack, grid_for(nUl), dim3(kBlock), 0, st, nUl, dim, nf_, ctx->fsi_stress.p + (size_t)c0 * nUl, buf.p);
-        halo_exchange(ctx, buf.p);
-        if (nUl > ctx->nUo)
-          hipLaunchKernelGGL(k_fsi_unpack, grid_for(nUl - ctx->nUo), dim3(kBlock), 0, st, nUl, ctx->nUo, dim, nf_, buf.p, ctx->fsi_stress.p + (size_t)c0 * nUl);
-      }
-      IFEM_HIP_CHECK(hipStreamSynchronize(st));
-    }
+    if (F.has_stress) halo_refresh_nodal(ctx, ncomp, ctx->fsi_stress.p);
   }
   IFEM_HIP_CHECK(hipStreamSynchronize(st));
   if (nf != 0.0) throw Error(IFEM_E_BADPARAM, "Cannot find point in solid (mpi_fsi.cpp:526-533): " + std::to_string((int64_t)nf) + " support point(s)");

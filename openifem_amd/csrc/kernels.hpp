@@ -1,5 +1,7 @@
 // kernels.hpp -- host-callable launchers implemented in the .hip translation units.
 #pragma once
+#include <functional>
+#include <vector>
 #include "ctx.hpp"
 
 namespace ifem {
@@ -56,6 +58,17 @@ void fsi_fluid_at_points(ifem_ctx *ctx, int32_t n, const double *points, double 
 // its flags changed
 void flags_differ(ifem_ctx *ctx, int npairs, const DBuf<uint8_t> *const *a, const DBuf<uint8_t> *const *b, double *out);
 void constraint_set_identity(ifem_ctx *ctx, int which, bool differs_self, bool differs_other);
+// api.hip: Dirichlet lines (index, value; val == nullptr: all zero) -> flag / value arrays over [0, N) in fresh buffers, zero where no line
+// stands.  An index listed twice keeps its LAST line.  kept_*: the lines that stand, last first.  false: an index outside [0, N) -- the
+// walk (from the back) stopped there, kept_* hold what it had passed and nothing was built
+bool build_line_set(ifem_ctx *ctx, size_t N, int32_t n, const int32_t *idx, const double *val, std::vector<int32_t> &kept_idx,
+                    std::vector<double> &kept_val, DBuf<uint8_t> &flag, DBuf<double> &cval);
+// api.hip: the Newton loop of run_one_step.  `iteration(nz)` zeroes the update, assembles and solves with the constraint object nz,
+// adds the update to the evaluation point and returns ||rhs|| with the two log columns of its system; the loop runs while
+// ||rhs|| / ||rhs_0|| > tolerance and ||rhs|| > floor, throws IFEM_E_NEWTON_MAXIT at max_iterations, writes log[4 * outer + 0..3] =
+// {||rhs||, relative, log2, log3} and returns the number of iterations.  nz = apply_nonzero in the first iteration, 0 afterwards
+struct NewtonIter { double rhs_norm, log2, log3; };
+int newton_loop(double floor, int apply_nonzero, double tolerance, int max_iterations, double *log, const std::function<NewtonIter(int)> &iteration);
 
 // assemble_scns.hip
 void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonzero);
@@ -167,8 +180,10 @@ void cg1_update(ifem_ctx *ctx, int64_t n, const double *diag, double *u, const d
 void v_minmax(ifem_ctx *ctx, int64_t n, const double *x, double *mn, double *mx);
 // test aid (ifem_test_cg_device): solver.hip::cg_device on A = diag(a), host arrays in and out, exactly `iters` iterations
 void test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x);
-// x[dof] = value for constrained dofs (AffineConstraints::distribute, Dirichlet lines)
+// x[dof] = value for constrained dofs (AffineConstraints::distribute, Dirichlet lines) of the fluid set `which`; the launch itself on any
+// flag / value arrays: x is compact [u (n_u_owned) | p (n_owned - n_u_owned)], the arrays hold the p part at p_off_ext
 void apply_constraints(ifem_ctx *ctx, int which, double *x);
+void distribute_lines(ifem_ctx *ctx, int64_t n_u_owned, int64_t n_owned, int64_t p_off_ext, const uint8_t *is_c, const double *cval, double *x);
 void spmv_planar_scalar(ifem_ctx *ctx, const PlanarCsr &M, const double *val, const double *xp, double *yp);
 // explicit pressure Schur complement of the SUPG block preconditioner (tpp.hip)
 void tpp_numeric(ifem_ctx *ctx);
@@ -238,6 +253,8 @@ void local_world_destroy(void *w);
 // ghost refresh of a ghost-extended velocity buffer [dim*nUl] / pressure buffer [nPl] (RCCL send/recv over xGMI)
 void halo_exchange(ifem_ctx *ctx, double *xu_ext);
 void halo_exchange_p(ifem_ctx *ctx, double *xp_ext);
+// ghost entries of nodal plane fields f[nplanes][nUl] := the owners' values, through the velocity halo plan (dim planes per exchange)
+void halo_refresh_nodal(ifem_ctx *ctx, int nplanes, double *f);
 // transpose: ghost entries are sent back to their owners and added there (C^T of hanging lines across ranks)
 void halo_reverse_add(ifem_ctx *ctx, double *xu_ext);
 // single-precision velocity vectors (level vectors of the A_uu V-cycle): same plans, half the bytes
@@ -257,10 +274,12 @@ void comm_init(ifem_ctx *ctx, const ifem_partition *part);
 void comm_destroy(ifem_ctx *ctx);
 
 // solver.hip
-int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
+// (a Krylov solve that misses its tolerance throws IFEM_E_KRYLOV_NOCONV through throw_noconv: SolverControl::NoConvergence)
+[[noreturn]] void throw_noconv(const char *solver, int it, double res, double tol);
+void ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, const double *src, double *dst);
 void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst);
-int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
+void scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 // y = A_uu z on a compact owned SINGLE-PRECISION column (ghosts refreshed on a float copy), single-precision cell arithmetic, fp64 result
 void uu_apply_f32col(ifem_ctx *ctx, const float *z, double *y);
 

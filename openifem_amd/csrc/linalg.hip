@@ -1554,12 +1554,15 @@ __global__ void k_apply_constraints(int64_t n_u_owned, int64_t n_owned, int64_t 
   }
 }
 
+void distribute_lines(ifem_ctx *ctx, int64_t n_u_owned, int64_t n_owned, int64_t p_off_ext, const uint8_t *is_c, const double *cval, double *x) {
+  if (n_owned) hipLaunchKernelGGL(k_apply_constraints, dim3(vgrid(n_owned)), dim3(256), 0, ctx->stream, n_u_owned, n_owned, p_off_ext, is_c, cval, x);
+}
+
 void apply_constraints(ifem_ctx *ctx, int which, double *x) {
   if (!ctx->has_c[which]) return;
   const int64_t nuo = ctx->dim * ctx->nUo, n = nuo + ctx->nPo;
   KScope ks(ctx, IFEM_KC_OTHER, double(n));
-  hipLaunchKernelGGL(k_apply_constraints, dim3(vgrid(n)), dim3(256), 0, ctx->stream, nuo, n, ctx->dim * ctx->nUl,
-                     ctx->is_c[which].p, ctx->cval[which].p, x);
+  distribute_lines(ctx, nuo, n, ctx->dim * ctx->nUl, ctx->is_c[which].p, ctx->cval[which].p, x);
 }
 
 } // namespace ifem

@@ -304,28 +304,6 @@ __global__ __launch_bounds__(256) void k_sa_spmv(int64_t n_rows, const int64_t *
   if (lig == 0 && row < n_rows) y[row] = acc;
 }
 
-__global__ void k_sa_diag(int64_t n_rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val, double *__restrict__ d) {
-  const int64_t row = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (row >= n_rows) return;
-  double out = 1.0;
-  for (int64_t k = rp[row]; k < rp[row + 1]; ++k)
-    if (col[k] == row) { out = val[k]; break; }
-  d[row] = out;
-}
-
-__global__ void k_sa_constraint_scatter(int32_t n, const int32_t *__restrict__ node, const double *__restrict__ val, uint8_t *__restrict__ flag, double *__restrict__ cval) {
-  const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  flag[node[i]] = 1;
-  cval[node[i]] = val ? val[i] : 0.0;
-}
-
-// AffineConstraints::distribute on Dirichlet lines
-__global__ void k_sa_distribute(int64_t n, const uint8_t *__restrict__ flag, const double *__restrict__ cval, double *__restrict__ x) {
-  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < n && flag[i]) x[i] = cval[i];
-}
-
 // mu_t = f_v1 nu~ rho (:904-911)
 __global__ void k_sa_eddy(int64_t n, const double *__restrict__ nu, double laminar_nu, double rho, double *__restrict__ out) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -337,28 +315,11 @@ __global__ void k_sa_eddy(int64_t n, const double *__restrict__ nu, double lamin
 
 inline unsigned grid_for(int64_t n) { return unsigned((n + 255) / 256); }
 
-// nodal scalar <-> component 0 of an interleaved [node][dim] buffer: lets the velocity halo plan refresh the ghost entries
-__global__ void k_sa_halo_pack(int64_t n, int dim, double *__restrict__ x, double *__restrict__ buf, int64_t first, int dir) {
-  const int64_t i = first + int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (dir == 0) buf[i * dim] = x[i];
-  else x[i] = buf[i * dim];
-}
-
 // ghost entries of a nodal scalar [nUl] := the owners' values (collective; nothing to do on one rank)
 void refresh_ghosts(ifem_ctx *ctx, double *x) {
   if (ctx->halo.nranks == 1) return;
-  SaState &sa = ctx->sa;
-  const int64_t n = ctx->nUl, no = ctx->nUo;
-  const int dim = ctx->dim;
-  if (sa.halo_buf.n != (size_t)n * dim) {
-    sa.halo_buf.alloc((size_t)n * dim);
-    IFEM_HIP_CHECK(hipMemsetAsync(sa.halo_buf.p, 0, sa.halo_buf.n * sizeof(double), ctx->stream));
-  }
   KScope ks(ctx, IFEM_KC_OTHER);
-  if (no > 0) hipLaunchKernelGGL(k_sa_halo_pack, dim3(grid_for(no)), dim3(256), 0, ctx->stream, no, dim, x, sa.halo_buf.p, int64_t(0), 0);
-  halo_exchange(ctx, sa.halo_buf.p);
-  if (n > no) hipLaunchKernelGGL(k_sa_halo_pack, dim3(grid_for(n - no)), dim3(256), 0, ctx->stream, n, dim, x, sa.halo_buf.p, no, 1);
+  halo_refresh_nodal(ctx, 1, x);
 }
 
 void check_params(const ifem_sa_params *p) {
@@ -417,25 +378,20 @@ void sa_set_wall_points(ifem_ctx *ctx, int64_t n_pts, const double *pts) {
   IFEM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// a node listed twice keeps its LAST line, as for ifem_set_constraints
 void sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom) {
   sa_check(ctx);
   if (which < 0 || which > 1 || n < 0 || (n > 0 && !node)) throw Error(IFEM_E_BADPARAM, "ifem_sa_set_constraints: which / n / node");
-  for (int32_t i = 0; i < n; ++i)
-    if (node[i] < 0 || node[i] >= ctx->nUl) throw Error(IFEM_E_BADPARAM, "ifem_sa_set_constraints: node outside [0, n_unodes_local)");
+  std::vector<int32_t> kept;
+  std::vector<double> kept_val;
+  DBuf<uint8_t> flag;
+  DBuf<double> cval;
+  if (!build_line_set(ctx, (size_t)ctx->nUl, n, node, which == 1 ? inhom : nullptr, kept, kept_val, flag, cval))
+    throw Error(IFEM_E_BADPARAM, "ifem_sa_set_constraints: node outside [0, n_unodes_local)");
   sa_ensure(ctx);
   SaState &sa = ctx->sa;
-  hipStream_t s = ctx->stream;
-  IFEM_HIP_CHECK(hipMemsetAsync(sa.is_c[which].p, 0, sa.is_c[which].n, s));
-  IFEM_HIP_CHECK(hipMemsetAsync(sa.cval[which].p, 0, sa.cval[which].n * sizeof(double), s));
-  if (n > 0) {
-    DBuf<int32_t> dn;
-    DBuf<double> dv;
-    dn.upload(node, (size_t)n, s);
-    if (which == 1 && inhom) dv.upload(inhom, (size_t)n, s);
-    hipLaunchKernelGGL(k_sa_constraint_scatter, dim3(grid_for(n)), dim3(256), 0, s, n, dn.p, dv.p, sa.is_c[which].p, sa.cval[which].p);
-    IFEM_HIP_CHECK(hipGetLastError());
-    IFEM_HIP_CHECK(hipStreamSynchronize(s)); // dn, dv are released on return
-  }
+  sa.is_c[which].swap(flag);
+  sa.cval[which].swap(cval);
   sa.has_c[which] = n > 0;
 }
 
@@ -502,7 +458,7 @@ void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out) 
     if (!sa.ilu_ok) { // as scns_solve: a factorisation that broke down is not applied
       if (sa.dinv.n != (size_t)n) sa.dinv.alloc((size_t)n);
       KScope ks(ctx, IFEM_KC_OTHER);
-      hipLaunchKernelGGL(k_sa_diag, dim3(grid_for(n)), dim3(256), 0, s, n, ctx->Auu.rowptr.p, ctx->Auu.col.p, sa.val.p, sa.dinv.p);
+      scalar_diag(ctx, ctx->Auu, sa.val.p, sa.dinv.p);
     }
   }
   const bool ranks = ctx->halo.nranks > 1;
@@ -539,17 +495,13 @@ void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out) 
   const int w = use_nonzero ? 1 : 0;
   if (sa.has_c[w]) {
     KScope ks(ctx, IFEM_KC_OTHER);
-    hipLaunchKernelGGL(k_sa_distribute, dim3(grid_for(ctx->nUl)), dim3(256), 0, s, ctx->nUl, sa.is_c[w].p, sa.cval[w].p, upd);
+    distribute_lines(ctx, ctx->nUl, ctx->nUl, 0, sa.is_c[w].p, sa.cval[w].p, upd);
   }
   IFEM_HIP_CHECK(hipGetLastError());
   IFEM_HIP_CHECK(hipStreamSynchronize(s));
   if (iters) *iters = (uint32_t)it;
   if (res_out) *res_out = res;
-  if (!(res <= tol)) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "Spalart-Allmaras FGMRES did not converge (SolverControl::NoConvergence): residual %.6e after %d iterations, tolerance %.6e", res, it, tol);
-    throw Error(IFEM_E_KRYLOV_NOCONV, msg);
-  }
+  if (!(res <= tol)) throw_noconv("Spalart-Allmaras FGMRES", it, res, tol);
 }
 
 void sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out) {
@@ -575,26 +527,17 @@ int sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, do
   sa_ensure(ctx);
   SaState &sa = ctx->sa;
   const int64_t n = ctx->nUl, no = ctx->nUo;
-  int outer = 0;
-  double cur = 1.0, init = 1.0, rel = 1.0;
   v_copy(ctx, n, sa.vec[IFEM_SA_PRESENT].p, sa.vec[IFEM_SA_EVAL].p);
-  while (rel > tolerance && cur > 1e-14) { // :296-297
-    if (outer >= max_iterations) throw Error(IFEM_E_NEWTON_MAXIT, "Too many Newton iterations!");
-    const int nz = apply_nonzero && outer == 0;
+  const int outer = newton_loop(1e-14, apply_nonzero, tolerance, max_iterations, log, [&](int nz) { // :296-297
     v_zero(ctx, n, sa.vec[IFEM_SA_UPDATE].p);
     sa_assemble(ctx, p, nz);
     uint32_t its = 0;
-    double res = 0;
+    double res = 0, rr;
     sa_solve(ctx, nz, &its, &res);
-    double rr;
     v_mdot(ctx, no, 1, sa.vec[IFEM_SA_RHS].p, no, sa.vec[IFEM_SA_RHS].p, &rr, /*all_ranks=*/true);
-    cur = std::sqrt(rr);
     v_axpy(ctx, n, 1.0, sa.vec[IFEM_SA_UPDATE].p, sa.vec[IFEM_SA_EVAL].p);
-    if (outer == 0) init = cur;
-    rel = cur / init;
-    if (log) { log[outer * 4 + 0] = cur; log[outer * 4 + 1] = rel; log[outer * 4 + 2] = its; log[outer * 4 + 3] = res; }
-    ++outer;
-  }
+    return NewtonIter{std::sqrt(rr), double(its), res};
+  });
   v_copy(ctx, n, sa.vec[IFEM_SA_EVAL].p, sa.vec[IFEM_SA_PRESENT].p);
   sa_update_eddy_viscosity(ctx, p, nullptr);
   return outer;

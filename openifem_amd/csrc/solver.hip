@@ -1158,7 +1158,7 @@ void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst) {
 //   T_pp     : A_pp - A_pv P_vv^-1 A_vp, solved by GMRES(200) to 1e-3 ||.|| with the ILU(0) of the explicit T_pp
 //                                                   (reference: ILU(0) of B2pp = A_pp - A_pv rowsum|A_vv|^-1 A_vp)
 // what deal.II's SolverControl::NoConvergence carries: the last step and the last residual
-static void throw_noconv(const char *solver, int it, double res, double tol) {
+void throw_noconv(const char *solver, int it, double res, double tol) {
   char msg[256];
   snprintf(msg, sizeof msg, "%s did not converge (SolverControl::NoConvergence): residual %.6e after %d iteration%s, tolerance %.6e%s", solver, res, it,
            it == 1 ? "" : "s", tol, std::isfinite(res) ? "" : " -- the system holds non-finite values (check the state vectors)");
@@ -1211,7 +1211,7 @@ void scns_pc_probe(ifem_ctx *ctx, int which, const double *x, double *y) {
   }
 }
 
-int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
+void scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats) {
   if (!ctx->assembled || !ctx->has_app) throw Error(IFEM_E_BADPARAM, "ifem_scns_solve called before ifem_scns_assemble");
   SolveState S{ctx, nullptr, o};
   carve_workspace(S);
@@ -1352,11 +1352,10 @@ int scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_s
     fprintf(stderr, "[ifem] scns solve: fgmres %d its res %.3e (tol %.3e) | inner Tpp its %u | %.1f ms\n", it, res, tol,
             S.st.inner_iters, S.st.t_total_ms);
   if (!(res <= tol)) throw_noconv("FGMRES", it, res, tol);
-  return 0;
 }
 
-int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, int use_nonzero,
-              ifem_solve_stats *stats) {
+void ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, int use_nonzero,
+               ifem_solve_stats *stats) {
   if (!ctx->assembled) throw Error(IFEM_E_BADPARAM, "ifem_solve called before ifem_ins_assemble");
   SolveState S{ctx, P, o};
   carve_workspace(S);
@@ -1408,7 +1407,6 @@ int ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o
     fprintf(stderr, "\n");
   }
   if (!(res <= tol)) throw_noconv("FGMRES", it, res, tol);
-  return 0;
 }
 
 } // namespace ifem

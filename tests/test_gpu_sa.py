@@ -98,6 +98,47 @@ def test_assembly_parity(name, use_nonzero):
     assert eb < 1e-11, eb
 
 
+def test_a_node_listed_twice_keeps_its_last_line():
+    """ifem_sa_set_constraints follows ifem_set_constraints: of two lines for one node the LAST stands, whichever thread scatters it.  The
+    first node of the "2q1" list is appended a second time with another value; matrix, right-hand side and the distributed update are those
+    of the deduplicated constraint, and with the two entries of that node exchanged the other value stands."""
+    capi = _capi()
+    m, inp = sa_ref.parity_inputs("2q1")
+    d = sa_ref.wall_distance(m, inp["wall"])
+    P = sa_ref.PARITY_PARAMS
+    first = int(inp["nodes"][0])
+    nodes = np.append(inp["nodes"], first).astype(np.int32)
+    vals = np.append(inp["inhom"], inp["inhom"][0] + 0.5)
+    exchanged = vals.copy()
+    exchanged[[0, -1]] = vals[[-1, 0]]
+    ctx = _ctx(m)
+    ctx.vec_set(capi.VEC_PRESENT, inp["fluid"])
+    ctx.set_indicator(inp["indicator"])
+    ctx.sa_set_wall_points(inp["wall"])
+    ctx.sa_vec_set(capi.SA_PRESENT, inp["present"])
+    ctx.sa_vec_set(capi.SA_EVAL, inp["eval"])
+    for v in (vals, exchanged):
+        assert v[0] != v[-1]
+        cval = inp["cval"].copy()
+        cval[first] = v[-1]
+        A, b, _ = sa_ref.assemble(m, inp["fluid"], inp["eval"], inp["present"], d, indicator=inp["indicator"], is_c=inp["is_c"], cval=cval, **P)
+        ctx.sa_set_constraints(0, nodes, None)
+        ctx.sa_set_constraints(1, nodes, v)
+        ctx.sa_assemble(_sa_params(P["mu"], P["rho"], P["dt"]), True)
+        Ag = ctx.sa_export_csr()
+        bg = ctx.sa_vec_get(capi.SA_RHS)
+        ctx.sa_solve(True)
+        x = ctx.sa_vec_get(capi.SA_UPDATE)
+        eA = abs(Ag - A).max() / abs(A).max()
+        eb = np.abs(bg - b).max() / np.abs(b).max()
+        print(f"S-A duplicated line, last value {v[-1]:.4f}: matrix {eA:.2e}, rhs {eb:.2e}, update at the node {x[first]:.4f}")
+        assert eA < 1e-11, eA
+        assert eb < 1e-11, eb
+        assert x[first] == v[-1]
+        assert (x[inp["nodes"][1:]] == inp["inhom"][1:]).all()
+    ctx.close()
+
+
 # ---- 3. solve
 @pytest.mark.parametrize("name", ["2q2", "3q1"])
 @pytest.mark.parametrize("use_nonzero", [False, True])
