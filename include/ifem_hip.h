@@ -149,6 +149,11 @@ typedef struct {
   double  inner_first_pshare; /* 0 (default): 10 fgmres_rel.  The largest pressure share ||r_p|| / ||r|| of the first Krylov vector
                                  for which inner_rel_first is used -- a heuristic: the block-triangular preconditioner leaves
                                  O(0.1) of the pressure part of a residual behind per outer iteration */
+  int32_t mp_solver;          /* 0 (default): tensor-product direct solve where the level qualifies, CG elsewhere; 1: always CG, as the reference.
+                                 A level qualifies when it is a uniform axis-aligned box on one rank without hanging-node lines whose Q1
+                                 pressure nodes fill the whole lattice (at most 65536 per line), and the line solves reproduce the assembled
+                                 M_p on a probe vector to 1e-12; M_p^-1 is then three sweeps of tridiagonal line solves (the solution to
+                                 rounding, so mp_rel / mp_abs are met trivially) and ifem_solve_stats::cg_mp_iters stays 0 */
 } ifem_solver_opts;
 
 /* Tuning / measurement knobs of one context (defaults = the measured best; nothing here changes results beyond fp64

@@ -93,6 +93,12 @@ int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double 
 int ifem_test_uu_fused_product(ifem_ctx *ctx, int prec, int mode, int first, double a, double b, const double *x, double *xs, double *r, double *d,
                                int block_cap, int64_t geo[2]);
 
+/* The M_p solve of the block preconditioner (solver.hip::solve_mp) on host vectors of n_pnodes (owned) doubles: x = what it produces for b under
+ * the options o (NULL: the defaults), by the tensor-product line solves where the level qualifies and ifem_solver_opts::mp_solver = 0, by CG to
+ * max(mp_abs, mp_rel ||b||) elsewhere.  info = {1 direct / 0 CG, CG iterations}.  After an assembly that integrated M_p (a multigrid level: after
+ * the first solve of its chain).  The direct path is single-rank; on several ranks the call is collective like the solve itself. */
+int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]);
+
 #ifdef __cplusplus
 }
 #endif

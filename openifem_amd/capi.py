@@ -83,7 +83,7 @@ class SolverOpts(C.Structure):
                 ("explicit_schur", C.c_int32), ("verbose", C.c_int32), ("device_cg", C.c_int32), ("outer_matrix_free", C.c_int32),
                 ("sm_mg", C.c_int32), ("mg_smooth", C.c_int32), ("mg_cheb_ratio", C.c_double),
                 ("mg_smooth_u", C.c_int32), ("mg_smooth_u_post", C.c_int32), ("mg_cheb_ratio_u", C.c_double),
-                ("inner_rel_first", C.c_double), ("inner_first_pshare", C.c_double)]
+                ("inner_rel_first", C.c_double), ("inner_first_pshare", C.c_double), ("mp_solver", C.c_int32)]
 
 
 class SolveStats(C.Structure):
@@ -149,7 +149,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
-           "ifem_test_uu_fused_product",
+           "ifem_test_uu_fused_product", "ifem_test_mp_solve",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
 
@@ -248,6 +248,7 @@ def load():
     L.ifem_test_cg_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_test_uu_fused_product.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_void_p]
+    L.ifem_test_mp_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -612,6 +613,14 @@ class Context:
         x = np.zeros(len(a))
         self._chk(self.L.ifem_test_cg_device(self.h, len(a), _ptr(a), _ptr(jac), _ptr(b), iters, _ptr(x)))
         return x
+
+    def mp_solve(self, b, opts=None):
+        """(x, direct?, CG iterations): the M_p solve of the block preconditioner for the host vector b (owned pressure nodes) under
+        `opts` (default: self.opts) -- ifem_test_mp_solve"""
+        b = np.ascontiguousarray(b, float)
+        x, info = np.zeros(len(b)), np.zeros(2, np.int32)
+        self._chk(self.L.ifem_test_mp_solve(self.h, C.byref(self.opts if opts is None else opts), _ptr(b), _ptr(x), _ptr(info)))
+        return x, bool(info[0]), int(info[1])
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

@@ -186,6 +186,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
   o->mg_smooth_u = 2; o->mg_smooth_u_post = 0; o->mg_cheb_ratio_u = 4.0;
   o->inner_rel_first = 0.0;
   o->inner_first_pshare = 0.0;
+  o->mp_solver = 0;
 }
 
 void ifem_default_tuning(ifem_tuning *t) {
@@ -1096,6 +1097,21 @@ int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double 
   if (n <= 0 || iters < 0 || !a || !b || !x) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: n > 0, iters >= 0, a, b and x");
   if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: single-rank contexts");
   test_cg_device(ctx, n, a, jac, b, iters, x);
+  IFEM_API_END
+}
+
+int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]) {
+  IFEM_API_BEGIN
+  if (!b || !x || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_mp_solve: b, x and info");
+  if (!ctx->mp_direct.mass_ready) throw Error(IFEM_E_BADPARAM, "ifem_test_mp_solve called before an assembly that integrated M_p");
+  const ifem_solver_opts oo = opts_or_default(o);
+  const size_t n = size_t(ctx->nPo);
+  DBuf<double> db, dx;
+  db.upload(b, n, ctx->stream);
+  dx.alloc(n);
+  mp_solve_probe(ctx, &oo, db.p, dx.p, info);
+  if (n) IFEM_HIP_CHECK(hipMemcpyAsync(x, dx.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
 }
 

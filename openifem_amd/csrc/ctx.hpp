@@ -389,6 +389,20 @@ struct SaState {
 };
 } // namespace ifem
 
+namespace ifem {
+// Tensor-product direct solve of M_p on a uniform box level (mp_direct.hip): the pressure nodes form the full lattice n[0] x n[1] (x n[2]), so
+// M_p = M_x (x) M_y (x) M_z and M_p^-1 is one sweep of tridiagonal line solves per axis.  Built lazily by the first solve_mp that could take it.
+struct MpDirect {
+  int state = 0;   // 0: not looked at yet, 1: the tables below are built, -1: this context keeps CG (not a full lattice, beyond a cap, or a failed check)
+  int checked = 0; // 0: the present M_p values have not been probed yet, 1: they passed (ctx.hpp::geometry_written resets it when M_p is re-integrated)
+  bool mass_ready = false; // an assembly has left M_p values behind
+  int n[3] = {1, 1, 1};    // lattice nodes per axis (cells + 1)
+  DBuf<int32_t> node_of_lattice; // pressure node at lattice point i_x + n[0] (i_y + n[1] i_z)
+  DBuf<double> rpiv[3], mult[3]; // Thomas factors of the 1D mass matrices: reciprocal pivots, off-diagonal x reciprocal pivot, n[d] entries each
+  DBuf<double> w;                // the lattice-ordered work vector of the sweeps
+};
+} // namespace ifem
+
 struct ifem_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -433,6 +447,7 @@ struct ifem_ctx {
   ifem::DBuf<double> xs_ext; // [halo.n_s_cols] input of the distributed S_m SpMV: owned entries + 2-deep far nodes
   ifem::F32Copy Sm_f32; // single-precision copy of the S_m values for its SpMV (approximate-preconditioner kinds)
   ifem::F32Copy Mp_f32; // the same for M_p (CG(M_p) of the preconditioner)
+  ifem::MpDirect mp_direct; // M_p^-1 by line solves where the level is a full uniform lattice (mp_direct.hip; ifem_solver_opts::mp_solver)
   // identity of the constrained-dof SET of each AffineConstraints object (which dofs, not their values): B, B^T, M_p,
   // diag(M_u) and S_m depend on nothing else, so zero_ / nonzero_constraints with the same lines share one cache entry and
   // re-making identical constraints (time-dependent boundary values) keeps it
@@ -628,7 +643,8 @@ inline void bjac_written(ifem_ctx *c) { c->bjac_f32.stale(); }
 // (ifem_tuning::geo_cache = 1; the reference rebuilds it every solve(), same values).
 inline void geometry_written(ifem_ctx *c, int64_t key, bool mass) {
   c->B_f32.stale(); c->Bt_f32.stale();
-  if (mass) c->Mp_f32.stale();
+  if (mass) { c->Mp_f32.stale(); c->mp_direct.checked = 0; } // (the direct solve probes the new values before it trusts them again)
+  c->mp_direct.mass_ready = true;
   if (key != c->sm_key || c->tune.geo_cache != 1) { c->sm_valid = false; c->sm_key = key; }
 }
 // S_m formed for the present blocks (explicit values, or the diagonal of its operator form)

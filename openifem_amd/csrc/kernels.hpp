@@ -137,6 +137,15 @@ void sm_diag_from_blocks(ifem_ctx *ctx, const double *dinv_mu_ext, double *d); /
 void scalar_diag(ifem_ctx *ctx, const PlanarCsr &M, const double *val, double *d);
 // y_p = M_p x_p
 void spmv_mp(ifem_ctx *ctx, const double *xp, double *yp, int part = 0, bool use_f32 = false);
+// mp_direct.hip: x = M_p^-1 b by tensor-product line solves on a uniform box level.  mp_direct_ready: the context qualifies, its tables are
+// built and the present M_p values have passed the probe against the assembled matrix (decides, builds and probes on demand; false: CG).
+// mp_direct_apply: the three sweeps on device vectors in the caller's node order (b and x may be the same vector)
+bool mp_direct_ready(ifem_ctx *ctx, int verbose);
+void mp_direct_apply(ifem_ctx *ctx, const double *b, double *x);
+// its host-side setup, plain C++: lattice map of the pressure nodes (false: not the full lattice of a uniform box) and the Thomas factors
+// of h tridiag(1/6, 2/3, 1/6) with end diagonals 1/3
+bool mpd_lattice_map(int dim, int64_t nc, int64_t n_nodes, const double *vc, const int32_t *cp, const double *h, int n[3], std::vector<int32_t> &node_of_lattice);
+void mpd_thomas_factors(int n, double h, std::vector<double> &rpiv, std::vector<double> &mult);
 // explicit S_m: numeric product B diag(1/diag M_u) B^T into ctx->Sm (pattern must exist), and y_p = S_m x_p
 void schur_numeric(ifem_ctx *ctx);
 void spmv_sm(ifem_ctx *ctx, const double *xp, double *yp, bool use_f32, int part = 0);
@@ -279,6 +288,8 @@ void comm_destroy(ifem_ctx *ctx);
 void ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *o, const double *src, double *dst);
 void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst);
+// test aid (ifem_test_mp_solve): solve_mp under `o` on device vectors of nPo entries; info = {1 direct / 0 CG, CG iterations}
+void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]);
 void scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 // y = A_uu z on a compact owned SINGLE-PRECISION column (ghosts refreshed on a float copy), single-precision cell arithmetic, fp64 result
 void uu_apply_f32col(ifem_ctx *ctx, const float *z, double *y);

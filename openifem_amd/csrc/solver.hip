@@ -914,9 +914,16 @@ static bool approx_kind(const ifem_solver_opts *o) {
 static int p_maxit(const ifem_ctx *c) { return (int)std::min<int64_t>(std::max<int64_t>(c->n_global_p, 1), 1 << 30); }
 
 // CG for Mp (:69-84): x = M_p^-1 b to max(mp_abs, mp_rel ||b||)
-static void solve_mp(SolveState &S, const double *b, double *x) {
+// ... or, on a uniform box level whose pressure nodes fill the lattice (mp_direct.hip; ifem_solver_opts::mp_solver = 0), three sweeps of
+// tridiagonal line solves: the solution to rounding, which meets mp_rel / mp_abs trivially; cg_mp_iters stays as it is.  Returns whether
+// the direct path ran
+static bool solve_mp(SolveState &S, const double *b, double *x) {
   ifem_ctx *c = S.ctx;
   const ifem_solver_opts *o = S.o;
+  if (o->mp_solver == 0 && mp_direct_ready(c, o->verbose)) {
+    mp_direct_apply(c, b, x);
+    return true;
+  }
   // the approximate-preconditioner kinds stream M_p in single precision like S_m (the solve is to 1e-6, the rounding of the
   // values 6e-8).  (p.q fused into this SpMV was measured: a block reduction in each of its 67 k small blocks costs more
   // than the separate pass over the two vectors.)
@@ -938,6 +945,7 @@ static void solve_mp(SolveState &S, const double *b, double *x) {
     S.st.cg_mp_iters += pcg_jacobi(c, S.npo, mp, S.tp[5], b, x, tol, p_maxit(c), S.tp[1], c->nPl, S.tp[3], S.tp[4], mdot_over(c, S.npo)); // r = tp[1], z = tp[2]
   else
     S.st.cg_mp_iters += cg(c, S.npo, mp, b, x, tol, p_maxit(c), S.tp[1], S.tp[2], S.tp[3], [&](const double *u, const double *v) { return dot_all(S, S.npo, u, v); });
+  return false;
 }
 
 // CG for Sm (:86-112): x = S_m^-1 b to max(sm_abs, sm_rel ||b||)
@@ -1131,6 +1139,14 @@ void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solve
   ctx->pc_used = 0;
   precond_vmult(S, src, dst);
   ctx->pc_used = 0;
+}
+
+void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]) {
+  SolveState S{ctx, nullptr, o};
+  carve_workspace(S);
+  S.p_src_norm = std::sqrt(dot_all(S, S.npo, b, b));
+  info[0] = solve_mp(S, b, x) ? 1 : 0;
+  info[1] = int32_t(S.st.cg_mp_iters);
 }
 
 // right-hand side of the condensed system after an assembly that treated the hanging dofs as ordinary ones:
