@@ -99,6 +99,18 @@ int ifem_test_uu_fused_product(ifem_ctx *ctx, int prec, int mode, int first, dou
  * the first solve of its chain).  The direct path is single-rank; on several ranks the call is collective like the solve itself. */
 int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]);
 
+/* y = S_m x, the pressure Schur block S_m = B diag(M_u)^-1 B^T of the block preconditioner, on host vectors of n_pnodes (owned) doubles.  After
+ * an assembly (a multigrid level: after the first solve of its chain); forms S_m and its stencil tables when they are not there yet, as a solve
+ * would.  Path 0 needs one rank and the explicit S_m; on several ranks path 1 is collective like the solve itself (every rank calls it with its
+ * owned entries) and is the distributed product, which never takes the stencil path.
+ *   path 0: the fp64 CSR product of the assembled matrix     path 1: what the solves of the default options use (solver.hip::sm_apply): the
+ *   lattice stencil product (sm_stencil.hip) where the level is a full uniform lattice and its tables passed their probe, the CSR product elsewhere
+ *   path 2: switch the stencil product of this context off from now on     path 3: on again (the default).  Both only switch (x, y unused, may be
+ *   NULL) and make a captured V-cycle of the context be captured anew; path 3 also builds and probes the tables of an S_m that was re-formed
+ *   while the path was off.
+ * info = {1 the stencil product is in use / 0, its classes, its irregular rows (produced by the CSR kernel), bytes of its table}. */
+int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,7 +149,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
-           "ifem_test_uu_fused_product", "ifem_test_mp_solve",
+           "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
 
@@ -249,6 +249,7 @@ def load():
     L.ifem_test_uu_fused_product.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_test_mp_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_test_sm_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -621,6 +622,19 @@ class Context:
         x, info = np.zeros(len(b)), np.zeros(2, np.int32)
         self._chk(self.L.ifem_test_mp_solve(self.h, C.byref(self.opts if opts is None else opts), _ptr(b), _ptr(x), _ptr(info)))
         return x, bool(info[0]), int(info[1])
+
+    def sm_apply(self, path, x=None):
+        """(y, info): y = S_m x for the host vector x (owned pressure nodes); path 0 the fp64 CSR product of the assembled matrix, 1 the
+        product the solves use.  path 2 / 3 switch the stencil product of this context off / on (x unused, y is None).
+        info = [stencil used, classes, irregular rows, table bytes] -- ifem_test_sm_apply"""
+        info = np.zeros(4, np.int64)
+        if path >= 2:
+            self._chk(self.L.ifem_test_sm_apply(self.h, path, None, None, _ptr(info)))
+            return None, info
+        x = np.ascontiguousarray(x, float)
+        y = np.zeros(len(x))
+        self._chk(self.L.ifem_test_sm_apply(self.h, path, _ptr(x), _ptr(y), _ptr(info)))
+        return y, info
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

@@ -1115,6 +1115,23 @@ int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b
   IFEM_API_END
 }
 
+int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]) {
+  IFEM_API_BEGIN
+  if (path < 0 || path > 3 || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply: path 0..3 and info");
+  if (path >= 2) { sm_apply_probe(ctx, path, nullptr, nullptr, info); return IFEM_OK; }
+  if (!x || !y) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply: x and y");
+  if (!ctx->geo.valid) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply called before an assembly that left B, B^T and diag(M_u) behind");
+  if (ctx->halo.nranks > 1 && path == 0) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply: path 0 is single-rank (several ranks: path 1, collective)");
+  const size_t n = size_t(ctx->nPo);
+  DBuf<double> dx, dy;
+  dx.upload(x, n, ctx->stream);
+  dy.alloc(n);
+  sm_apply_probe(ctx, path, dx.p, dy.p, info);
+  if (n) IFEM_HIP_CHECK(hipMemcpyAsync(y, dy.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
 int ifem_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *p, const ifem_solver_opts *o, int dst, int src) {
   IFEM_API_BEGIN
   if (!vec_ok(dst) || !vec_ok(src) || is_ext(dst) || is_ext(src)) throw Error(IFEM_E_BADPARAM, "use non-ghosted vectors");

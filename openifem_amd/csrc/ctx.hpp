@@ -390,16 +390,43 @@ struct SaState {
 } // namespace ifem
 
 namespace ifem {
-// Tensor-product direct solve of M_p on a uniform box level (mp_direct.hip): the pressure nodes form the full lattice n[0] x n[1] (x n[2]), so
+// The pressure nodes of a uniform box level as the full lattice n[0] x n[1] (x n[2]) (setup.hip::p_lattice_ensure, host side lattice.cpp): one
+// table for its readers, the direct M_p solve (mp_direct.hip) and the S_m stencil product (sm_stencil.hip).  Decided once per context: one rank,
+// no hanging-node line, ifem_ctx::mf_uniform, Q1 pressure in 2D / 3D, the map node -> lattice point a bijection onto the whole box.
+struct PLattice {
+  int state = 0;        // 0: not looked at yet, 1: the maps below are built, -1: this context is no full lattice
+  int n[3] = {1, 1, 1}; // lattice nodes per axis (cells + 1)
+  DBuf<int32_t> node_of_lattice; // pressure node at lattice point i_x + n[0] (i_y + n[1] i_z)
+  DBuf<int32_t> lattice_of_node; // its inverse
+};
+
+// Tensor-product direct solve of M_p on a uniform box level (mp_direct.hip): the pressure nodes form the full lattice (PLattice), so
 // M_p = M_x (x) M_y (x) M_z and M_p^-1 is one sweep of tridiagonal line solves per axis.  Built lazily by the first solve_mp that could take it.
 struct MpDirect {
   int state = 0;   // 0: not looked at yet, 1: the tables below are built, -1: this context keeps CG (not a full lattice, beyond a cap, or a failed check)
   int checked = 0; // 0: the present M_p values have not been probed yet, 1: they passed (ctx.hpp::geometry_written resets it when M_p is re-integrated)
   bool mass_ready = false; // an assembly has left M_p values behind
-  int n[3] = {1, 1, 1};    // lattice nodes per axis (cells + 1)
-  DBuf<int32_t> node_of_lattice; // pressure node at lattice point i_x + n[0] (i_y + n[1] i_z)
   DBuf<double> rpiv[3], mult[3]; // Thomas factors of the 1D mass matrices: reciprocal pivots, off-diagonal x reciprocal pivot, n[d] entries each
   DBuf<double> w;                // the lattice-ordered work vector of the sweeps
+};
+
+// y = S_m x from stencil tables over the pressure lattice (sm_stencil.hip): on a uniform box every row with the same position signature (per
+// axis the distance to either face, capped at 2) has the same 5^dim stencil.  The tables are re-made and probed against the assembled S_m whenever
+// S_m is re-formed (`version`), at set-up time; rows that differ from their class (`rows`) keep the CSR product.
+struct SmStencil {
+  bool off = false;     // test aid (ifem_test_sm_apply): the context keeps the CSR product
+  int64_t version = -1; // ifem_ctx::sm_version the tables (or the decision against them) belong to
+  bool ready = false;   // ... and they passed the probe: sm_apply takes the stencil path
+  bool failed = false;  // a probe failed: the context keeps the CSR product from then on
+  bool said = false;    // the verbose line of a level that keeps the CSR product has been printed
+  int classes = 0, ncls[3] = {1, 1, 1};
+  int64_t n_irregular = 0;
+  DBuf<uint8_t> axcls;   // [n[0] + n[1] + n[2]] per-axis class of every lattice coordinate
+  DBuf<int32_t> first;   // [ncls[0] + ncls[1] + ncls[2]] first coordinate of every axis class
+  DBuf<double> table;    // [classes][5^dim] stencil of every class in offset order, [classes] max |entry| behind it
+  DBuf<uint16_t> cls;    // [lattice] class of the row at that point, 0xFFFF: irregular
+  DBuf<int32_t> rows;    // [n_irregular] the irregular rows (pressure nodes); capacity lattice / 8 + 1
+  DBuf<int32_t> counter; // [1] device count of the irregular rows
 };
 } // namespace ifem
 
@@ -447,7 +474,9 @@ struct ifem_ctx {
   ifem::DBuf<double> xs_ext; // [halo.n_s_cols] input of the distributed S_m SpMV: owned entries + 2-deep far nodes
   ifem::F32Copy Sm_f32; // single-precision copy of the S_m values for its SpMV (approximate-preconditioner kinds)
   ifem::F32Copy Mp_f32; // the same for M_p (CG(M_p) of the preconditioner)
+  ifem::PLattice p_lattice; // the pressure nodes as a full lattice, where they are one (shared by the two readers below)
   ifem::MpDirect mp_direct; // M_p^-1 by line solves where the level is a full uniform lattice (mp_direct.hip; ifem_solver_opts::mp_solver)
+  ifem::SmStencil sm_stencil; // S_m x from lattice stencil tables where the level is one (sm_stencil.hip)
   // identity of the constrained-dof SET of each AffineConstraints object (which dofs, not their values): B, B^T, M_p,
   // diag(M_u) and S_m depend on nothing else, so zero_ / nonzero_constraints with the same lines share one cache entry and
   // re-making identical constraints (time-dependent boundary values) keeps it

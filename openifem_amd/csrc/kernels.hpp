@@ -3,6 +3,7 @@
 #include <functional>
 #include <vector>
 #include "ctx.hpp"
+#include "lattice.hpp"
 
 namespace ifem {
 
@@ -142,13 +143,20 @@ void spmv_mp(ifem_ctx *ctx, const double *xp, double *yp, int part = 0, bool use
 // mp_direct_apply: the three sweeps on device vectors in the caller's node order (b and x may be the same vector)
 bool mp_direct_ready(ifem_ctx *ctx, int verbose);
 void mp_direct_apply(ifem_ctx *ctx, const double *b, double *x);
-// its host-side setup, plain C++: lattice map of the pressure nodes (false: not the full lattice of a uniform box) and the Thomas factors
-// of h tridiag(1/6, 2/3, 1/6) with end diagonals 1/3
-bool mpd_lattice_map(int dim, int64_t nc, int64_t n_nodes, const double *vc, const int32_t *cp, const double *h, int n[3], std::vector<int32_t> &node_of_lattice);
+// its host-side setup, plain C++: the Thomas factors of h tridiag(1/6, 2/3, 1/6) with end diagonals 1/3
 void mpd_thomas_factors(int n, double h, std::vector<double> &rpiv, std::vector<double> &mult);
+// setup.hip: the pressure nodes of this context as a full lattice (ctx.hpp::PLattice; host side lattice.hpp), decided and built on first use
+bool p_lattice_ensure(ifem_ctx *ctx);
 // explicit S_m: numeric product B diag(1/diag M_u) B^T into ctx->Sm (pattern must exist), and y_p = S_m x_p
 void schur_numeric(ifem_ctx *ctx);
 void spmv_sm(ifem_ctx *ctx, const double *xp, double *yp, bool use_f32, int part = 0);
+void spmv_sm_rows(ifem_ctx *ctx, const double *xp, double *yp, int64_t n_list, const int32_t *rows); // the listed rows only, fp64 values
+// sm_stencil.hip: y = S_m x from stencil tables over the pressure lattice of a uniform box level.  sm_stencil_setup: set-up time only (allocates,
+// synchronises): (re)builds and probes the tables when S_m was re-formed since it last looked.  sm_stencil_ready: sm_apply may take
+// sm_stencil_apply (no allocation, capture-safe).
+void sm_stencil_setup(ifem_ctx *ctx, int verbose);
+inline bool sm_stencil_ready(const ifem_ctx *ctx) { return ctx->sm_stencil.ready && !ctx->sm_stencil.off && ctx->sm_stencil.version == ctx->sm_version; }
+void sm_stencil_apply(ifem_ctx *ctx, const double *x, double *y);
 // y_u = d .* x_u (diagonal scaling with 1/diag(M_u))
 void vec_mul(ifem_ctx *ctx, int64_t n, const double *d, const double *x, double *y);
 void vec_div(ifem_ctx *ctx, int64_t n, const double *d, const double *x, double *y); // y = x ./ d (d == 0 -> 1)
@@ -290,6 +298,7 @@ void ins_precond_vmult(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solve
 void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst);
 // test aid (ifem_test_mp_solve): solve_mp under `o` on device vectors of nPo entries; info = {1 direct / 0 CG, CG iterations}
 void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]);
+void sm_apply_probe(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]); // ifem_test_sm_apply on device vectors
 void scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 // y = A_uu z on a compact owned SINGLE-PRECISION column (ghosts refreshed on a float copy), single-precision cell arithmetic, fp64 result
 void uu_apply_f32col(ifem_ctx *ctx, const float *z, double *y);

@@ -799,6 +799,13 @@ void spmv_sm(ifem_ctx *ctx, const double *xp, double *yp, bool use_f32, int part
                        ctx->Sm.rowptr.p, ctx->Sm.col.p, ctx->Sm.val.p, xp, yp, rp_.rows);
 }
 
+// the listed rows of y = S_m x with the fp64 values (the irregular rows of sm_stencil.hip; inside that product's KScope)
+void spmv_sm_rows(ifem_ctx *ctx, const double *xp, double *yp, int64_t n_list, const int32_t *rows) {
+  if (n_list <= 0) return;
+  hipLaunchKernelGGL((k_spmv_planar<1, 1, 32>), dim3(blocks_for_rows(n_list, 32)), dim3(256), 0, ctx->stream, n_list,
+                     ctx->Sm.rowptr.p, ctx->Sm.col.p, ctx->Sm.val.p, xp, yp, rows);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // vector kernels: grid-stride, 16-byte accesses where alignment allows
 static inline unsigned vgrid(int64_t n) {

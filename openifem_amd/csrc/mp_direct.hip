@@ -10,10 +10,10 @@
 // e, x = direct(e), max |M_p x - e| <= 1e-12 max |e| with the fp64 SpMV) after the first assembly and again whenever M_p is re-integrated
 // (ctx.hpp::geometry_written); a context that fails keeps CG from then on.
 //
-// Eligibility (mp_direct_build, once per context): one rank, no hanging-node line, ifem_ctx::mf_uniform as detected at creation, Q1 pressure in
+// Eligibility (mp_direct_build, once per context; the lattice map is the context's, setup.hip::p_lattice_ensure / lattice.cpp): one rank, no hanging-node line, ifem_ctx::mf_uniform as detected at creation, Q1 pressure in
 // 2D / 3D, every cell vertex on a lattice point i_d = round((x_d - x_min,d) / h_d) within 8 eps max|x| (the allowance of
 // setup.hip::detect_uniform_cells), the map node -> lattice point a bijection onto the full box (holes, L-shapes, duplicates: CG), and
-// CAP: at most kMpdMaxLine = 65536 nodes per line (the factor tables and the 32-bit position along a line) and fewer than 2^31 nodes.
+// CAP: at most kLatticeMaxLine = 65536 nodes per line (the factor tables and the 32-bit position along a line) and fewer than 2^31 nodes.
 //
 // Kernels.  The work vector w is lattice-ordered, x fastest.  The node order is folded into the sweeps: the first sweep reads b[node_of_lattice[.]],
 // the last one stores x[node_of_lattice[.]]; there is no permutation pass.
@@ -37,64 +37,10 @@
 
 namespace ifem {
 
-constexpr int kMpdMaxLine = 65536;
 constexpr int kMpdTL = 64, kMpdTC = 32, kMpdPitch = kMpdTC + 1; // tile of k_mpd_contig: lines, columns, LDS row pitch
 constexpr int kMpdU = 16;                                       // entries per batch of k_mpd_strided
 
-// ---- host side: lattice map and Thomas factors (plain C++, no device call)
-
-// node_of_lattice from the cell tables (vc [nc][2^dim][dim], cp [nc][2^dim]); false: the nodes are not the full lattice of a uniform box
-bool mpd_lattice_map(int dim, int64_t nc, int64_t n_nodes, const double *vc, const int32_t *cp, const double *h, int n[3], std::vector<int32_t> &node_of_lattice) {
-  const int nv = 1 << dim;
-  if (nc <= 0 || n_nodes <= 0 || n_nodes >= (int64_t(1) << 31)) return false;
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, M = 0;
-  for (int64_t k = 0; k < nc * nv; ++k)
-    for (int d = 0; d < dim; ++d) {
-      const double x = vc[k * dim + d];
-      if (!std::isfinite(x)) return false;
-      if (k == 0 || x < lo[d]) lo[d] = x;
-      if (k == 0 || x > hi[d]) hi[d] = x;
-      M = std::max(M, std::fabs(x));
-    }
-  const double tol = 8.0 * 2.220446049250313e-16 * M;
-  // the lattice step is extent / count (how a box mesh forms its coordinates: lo + i * step); it must be the detected cell edge
-  double step[3] = {1, 1, 1};
-  int64_t total = 1;
-  n[0] = n[1] = n[2] = 1;
-  for (int d = 0; d < dim; ++d) {
-    if (!(h[d] > 0)) return false;
-    const double cells = std::round((hi[d] - lo[d]) / h[d]);
-    if (!(cells >= 1) || cells + 1 > kMpdMaxLine) return false;
-    n[d] = int(cells) + 1;
-    step[d] = (hi[d] - lo[d]) / cells;
-    if (!(std::fabs(step[d] - h[d]) <= tol)) return false;
-    total *= n[d];
-    if (total > n_nodes) return false; // more lattice points than nodes: a hole
-  }
-  if (total != n_nodes) return false;
-  node_of_lattice.assign(size_t(total), -1);
-  std::vector<int32_t> lattice_of_node(size_t(n_nodes), -1);
-  for (int64_t k = 0; k < nc * nv; ++k) {
-    const int32_t node = cp[k];
-    if (node < 0 || node >= n_nodes) return false;
-    int64_t lin = 0, mul = 1;
-    for (int d = 0; d < dim; ++d) {
-      const double x = vc[k * dim + d];
-      const double fi = std::round((x - lo[d]) / step[d]);
-      if (!(fi >= 0 && fi <= n[d] - 1)) return false;
-      if (!(std::fabs(x - (lo[d] + fi * step[d])) <= tol)) return false;
-      lin += int64_t(fi) * mul;
-      mul *= n[d];
-    }
-    if (lattice_of_node[node] >= 0 && lattice_of_node[node] != lin) return false; // one node at two points
-    lattice_of_node[node] = int32_t(lin);
-    if (node_of_lattice[lin] >= 0 && node_of_lattice[lin] != node) return false; // two nodes at one point
-    node_of_lattice[lin] = node;
-  }
-  for (int64_t l = 0; l < total; ++l)
-    if (node_of_lattice[l] < 0) return false; // a lattice point no cell touches (with total == n_nodes: some node is in no cell either)
-  return true;
-}
+// ---- host side: Thomas factors (plain C++, no device call; the lattice map is setup.hip::p_lattice_ensure)
 
 // Thomas factors of M = h tridiag(1/6, 2/3, 1/6) with end diagonals 1/3, n >= 2 rows, no pivoting (SPD, strictly diagonally dominant):
 // forward d'_i = rpiv_i d_i - mult_i d'_{i-1}, backward x_i = d'_i - mult_i x_{i+1}; mult_i = (h / 6) rpiv_i serves both (the matrix is symmetric
@@ -237,23 +183,16 @@ static void mp_direct_build(ifem_ctx *ctx) {
   MpDirect &D = ctx->mp_direct;
   D.state = -1;
   const int dim = ctx->dim;
-  if (ctx->halo.nranks > 1 || ctx->hang.active || ctx->hang.n > 0 || !ctx->mf_uniform) return;
-  if ((dim != 2 && dim != 3) || ctx->np != (1 << dim) || ctx->nPo != ctx->nPl || ctx->Mp.n_rows != ctx->nPo || ctx->n_cells <= 0) return;
+  if (!p_lattice_ensure(ctx) || ctx->Mp.n_rows != ctx->nPo) return;
+  const PLattice &L = ctx->p_lattice;
   hipStream_t s = ctx->stream;
-  const std::vector<double> vc = ctx->vcoords.download(s);
-  const std::vector<int32_t> cp = ctx->cell_pnodes.download(s);
-  if (vc.size() != size_t(ctx->n_cells) * ctx->np * dim || cp.size() != size_t(ctx->n_cells) * ctx->np) return;
-  std::vector<int32_t> nol;
-  if (!mpd_lattice_map(dim, ctx->n_cells, ctx->nPo, vc.data(), cp.data(), ctx->mf_h, D.n, nol)) return;
   std::vector<double> rp, mu;
   for (int d = 0; d < dim; ++d) {
-    mpd_thomas_factors(D.n[d], ctx->mf_h[d], rp, mu);
+    mpd_thomas_factors(L.n[d], ctx->mf_h[d], rp, mu);
     D.rpiv[d].upload(rp.data(), rp.size(), s);
     D.mult[d].upload(mu.data(), mu.size(), s);
     IFEM_HIP_CHECK(hipStreamSynchronize(s)); // (rp / mu are reused)
   }
-  D.node_of_lattice.upload(nol.data(), nol.size(), s);
-  IFEM_HIP_CHECK(hipStreamSynchronize(s));
   D.w.alloc(size_t(ctx->nPo), "the work vector of the direct M_p solve");
   D.state = 1;
 }
@@ -262,10 +201,11 @@ void mp_direct_apply(ifem_ctx *ctx, const double *b, double *x) {
   MpDirect &D = ctx->mp_direct;
   if (D.state != 1) throw Error(IFEM_E_BADPARAM, "mp_direct_apply: the context has no line-solve tables");
   const int dim = ctx->dim;
-  const int64_t nx = D.n[0], ny = D.n[1], nz = dim == 3 ? D.n[2] : 1, N = nx * ny * nz;
+  const PLattice &L = ctx->p_lattice;
+  const int64_t nx = L.n[0], ny = L.n[1], nz = dim == 3 ? L.n[2] : 1, N = nx * ny * nz;
   hipStream_t s = ctx->stream;
   KScope ks(ctx, IFEM_KC_SPMV_MP, double(N) * (36.0 + 32.0 * (dim - 2) + 36.0));
-  const int32_t *nol = D.node_of_lattice.p;
+  const int32_t *nol = L.node_of_lattice.p;
   double *w = D.w.p;
   { // x: the contiguous axis, gathers b
     const int64_t lines = ny * nz;
@@ -329,11 +269,11 @@ bool mp_direct_ready(ifem_ctx *ctx, int verbose) {
   double err = 0;
   if (mp_direct_probe(ctx, &err)) {
     D.checked = 1;
-    if (verbose) fprintf(stderr, "[ifem] M_p: line solves on the %d x %d x %d lattice, probe max |M_p x - e| / max |e| = %.2e\n", D.n[0], D.n[1], D.n[2], err);
+    if (verbose) fprintf(stderr, "[ifem] M_p: line solves on the %d x %d x %d lattice, probe max |M_p x - e| / max |e| = %.2e\n", ctx->p_lattice.n[0], ctx->p_lattice.n[1], ctx->p_lattice.n[2], err);
     return true;
   }
   D.state = -1; // off for this context
-  D.node_of_lattice.release(); D.w.release();
+  D.w.release(); // (the lattice map is shared: it stays)
   for (int d = 0; d < 3; ++d) { D.rpiv[d].release(); D.mult[d].release(); }
   if (verbose) fprintf(stderr, "[ifem] M_p: the line solves miss the assembled matrix (probe %.2e > 1e-12): CG from now on\n", err);
   return false;

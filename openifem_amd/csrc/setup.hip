@@ -553,6 +553,27 @@ void detect_uniform_cells(ifem_ctx *ctx) {
   for (int d = 0; d < ctx->dim; ++d) ctx->mf_h[d] = h[d];
 }
 
+// the pressure nodes as a full lattice (ctx.hpp::PLattice): decided and built on first use, once per context
+bool p_lattice_ensure(ifem_ctx *ctx) {
+  PLattice &L = ctx->p_lattice;
+  if (L.state != 0) return L.state > 0;
+  L.state = -1;
+  const int dim = ctx->dim;
+  if (ctx->halo.nranks > 1 || ctx->hang.active || ctx->hang.n > 0 || !ctx->mf_uniform) return false;
+  if ((dim != 2 && dim != 3) || ctx->np != (1 << dim) || ctx->nPo != ctx->nPl || ctx->n_cells <= 0) return false;
+  hipStream_t s = ctx->stream;
+  const std::vector<double> vc = ctx->vcoords.download(s);
+  const std::vector<int32_t> cp = ctx->cell_pnodes.download(s);
+  if (vc.size() != size_t(ctx->n_cells) * ctx->np * dim || cp.size() != size_t(ctx->n_cells) * ctx->np) return false;
+  std::vector<int32_t> nol, lon;
+  if (!lattice_map(dim, ctx->n_cells, ctx->nPo, vc.data(), cp.data(), ctx->mf_h, L.n, nol, lon)) return false;
+  L.node_of_lattice.upload(nol.data(), nol.size(), s);
+  L.lattice_of_node.upload(lon.data(), lon.size(), s);
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  L.state = 1;
+  return true;
+}
+
 // ---- cell tables of the matrix-free apply on several ranks: interior cells (all nodes owned) first, then the cells that
 // touch a ghost node; order kept inside both groups (the Morton locality survives)
 __global__ void k_cell_flag(int64_t n_cells, int nu, const int32_t *__restrict__ cell_unodes, int32_t n_owned, int64_t *__restrict__ flag) {

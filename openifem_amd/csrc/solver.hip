@@ -142,6 +142,7 @@ static void sm_ensure(SolveState &S) {
   if (c->halo.nranks == 1) {
     if (c->Sm.n_rows == 0) build_schur_pattern(c);
     schur_numeric(c);
+    sm_stencil_setup(c, S.o->verbose); // (re)builds and probes the lattice stencil tables when S_m was re-formed: set-up time, never inside sm_apply
     return;
   }
   // same matrix, distributed: pattern from the pressure lattice, values by probing
@@ -170,7 +171,12 @@ static void sm_apply(SolveState &S, const double *x, double *y, bool lowp) {
   }
   // the approximate-preconditioner kinds (1, 3) also stream S_m in single precision: it only ever acts inside CG to
   // 1e-3 ||v|| and the rounding (6e-8 relative) is far below the eigenvalue ratio of this Laplacian-like operator
-  if (sm_is_explicit(S)) { spmv_sm(c, x, y, lowp); return; }
+  // ... unless the level applies S_m from its lattice stencil tables (sm_stencil.hip: fp64 tables of a few KB, `lowp` has nothing to save there)
+  if (sm_is_explicit(S)) {
+    if (sm_stencil_ready(c)) sm_stencil_apply(c, x, y);
+    else spmv_sm(c, x, y, lowp);
+    return;
+  }
   sm_matrix_free(S, x, y, lowp);
 }
 
@@ -259,6 +265,10 @@ static void sm_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   key_ptr(key, lc->mg_Rp.col.p); key_ptr(key, lc->mg_Pp.col.p);
   key.push_back(uint64_t(lc->nPo)); key.push_back(uint64_t(lc->sm_version)); key.push_back(uint64_t(lc->tune.sm_lanes)); key.push_back(uint64_t(lc->Sm_f32.valid));
   key_f64(key, lc->sm_lmax);
+  // which product the level launches, and the tables of the stencil one
+  const SmStencil &T = lc->sm_stencil;
+  key.push_back(uint64_t(sm_stencil_ready(lc))); key.push_back(uint64_t(T.n_irregular));
+  key_ptr(key, T.table.p); key_ptr(key, T.cls.p); key_ptr(key, T.rows.p); key_ptr(key, lc->p_lattice.node_of_lattice.p);
 }
 static void uu_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   (void)bjac_f32_ptr(lc); // lazy state (the single-precision copy of the inverse node blocks) stays outside the graph
@@ -1147,6 +1157,29 @@ void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, d
   S.p_src_norm = std::sqrt(dot_all(S, S.npo, b, b));
   info[0] = solve_mp(S, b, x) ? 1 : 0;
   info[1] = int32_t(S.st.cg_mp_iters);
+}
+
+// ifem_test_sm_apply: y = S_m x on device vectors of owned pressure nodes.  path 0: the fp64 CSR product of the assembled matrix (one rank); 1: sm_apply
+// as the solves of the default options call it (several ranks: collective, the distributed explicit product or the two SpMVs); 2 / 3: switch the
+// stencil path of this context off / on again (x, y unused; 3 also makes the tables of the present S_m when that is formed already)
+void sm_apply_probe(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]) {
+  SmStencil &T = ctx->sm_stencil;
+  if (path == 2 || path == 3) {
+    T.off = path == 2;
+    ctx->graph_epoch++; // captured cycles are keyed on the product they launch
+    if (path == 3 && ctx->halo.nranks == 1 && ctx->sm_valid && ctx->Sm.n_rows > 0) sm_stencil_setup(ctx, 0); // S_m re-formed while the path was off
+  } else {
+    SolveState S = default_state(ctx);
+    if (path == 0 && !sm_is_explicit(S)) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply: this context keeps no explicit S_m");
+    sm_ensure(S);
+    if (path == 0) spmv_sm(ctx, x, y, false);
+    else sm_apply(S, x, y, approx_kind(S.o));
+  }
+  const bool on = sm_stencil_ready(ctx);
+  info[0] = on ? 1 : 0;
+  info[1] = on ? T.classes : 0;
+  info[2] = on ? T.n_irregular : 0;
+  info[3] = on ? int64_t(T.table.n * sizeof(double)) : 0;
 }
 
 // right-hand side of the condensed system after an assembly that treated the hanging dofs as ordinary ones:
