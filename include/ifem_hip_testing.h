@@ -111,6 +111,18 @@ int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b
  * info = {1 the stencil product is in use / 0, its classes, its irregular rows (produced by the CSR kernel), bytes of its table}. */
 int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]);
 
+/* The products with the off-diagonal blocks on host vectors.  which 0: y = B x (x: dim * n_unodes_local doubles, node-interleaved, ghost entries
+ * filled by the caller; y: n_pnodes_owned), 1: y = B^T x (x: n_pnodes_local; y: dim * n_unodes_owned), 2: y += B^T x (y in and out).  After an
+ * assembly that left the blocks behind.  No exchange is made: on several ranks every rank multiplies what it is given.
+ *   path 0: the fp64 CSR product of the assembled block     path 1: what the solves launch (linalg.hip::spmv_b / spmv_bt / the B^T arm of
+ *   spmv_uu): the lattice stencil product (bb_stencil.hip) where the context is a full uniform Q2/Q1 lattice on one rank and the block's tables
+ *   passed their probe, the CSR product elsewhere; makes the tables of blocks an assembly wrote since the last look, as a solve's set-up does
+ *   path 2: switch the stencil products of this context off from now on     path 3: on again (the default).  Both only switch (x, y unused, may
+ *   be NULL); path 3 also builds and probes the tables when the blocks were written while the path was off.
+ * info = {0: the product of `which` is the CSR one / otherwise the number of table builds this context has made so far (an assembly that keeps
+ * the blocks adds none), classes of the block, its irregular rows (produced by the CSR kernel), bytes of its table}. */
+int ifem_test_b_apply(ifem_ctx *ctx, int which, int path, const double *x, double *y, int64_t info[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,7 +149,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
-           "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply",
+           "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
 
@@ -250,6 +250,7 @@ def load():
                                              C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_test_mp_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_sm_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_test_b_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -635,6 +636,22 @@ class Context:
         y = np.zeros(len(x))
         self._chk(self.L.ifem_test_sm_apply(self.h, path, _ptr(x), _ptr(y), _ptr(info)))
         return y, info
+
+    def b_apply(self, which, path, x=None, y=None):
+        """(y, info): which 0: y = B x (x: dim * n_unodes_local, node-interleaved), 1: y = B^T x (x: n_pnodes_local), 2: y + B^T x for the given
+        y; path 0 the fp64 CSR product of the assembled block, 1 the product the solves launch.  path 2 / 3 switch the stencil products of this
+        context off / on (x unused, y is None).  info = [0 CSR / table builds so far, classes, irregular rows, table bytes] -- ifem_test_b_apply"""
+        info = np.zeros(4, np.int64)
+        if path >= 2:
+            self._chk(self.L.ifem_test_b_apply(self.h, which, path, None, None, _ptr(info)))
+            return None, info
+        x = np.ascontiguousarray(x, float)
+        nuo = self.dim * self.n_unodes_owned
+        n_out = self.n_owned - nuo if which == 0 else nuo
+        out = np.zeros(n_out) if which != 2 else np.array(y, float).reshape(-1).copy()
+        assert len(out) == n_out and len(x) == (self.n_u if which == 0 else self.n_local - self.n_u)
+        self._chk(self.L.ifem_test_b_apply(self.h, which, path, _ptr(x), _ptr(out), _ptr(info)))
+        return out, info
 
     def set_constraints(self, which, dofs, vals=None):
         dofs = np.ascontiguousarray(dofs, np.int32)

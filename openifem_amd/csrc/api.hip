@@ -209,6 +209,7 @@ int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
   if (t->uu_patch_levels != 0 && t->uu_patch_levels != 1) throw Error(IFEM_E_BADPARAM, "uu_patch_levels must be 0 (uniform box levels only) or 1 (per-patch inverses on all other eligible levels)");
   ctx->tune = *t;
   ++ctx->graph_epoch;
+  ++ctx->bb_version; // the lattice tables of B / B^T are re-made and probed by the next solve's set-up (CSR until then)
   if (ctx->tune.asm3_cpb <= 0) ctx->tune.asm3_cpb = 2; // a zero-initialised struct: the defaults of the fields added after round 4
   if (ctx->tune.scns_pc == 0) { ctx->tune.scns_pc = 2; if (!ctx->tune.pvv_sweeps) ctx->tune.pvv_sweeps = 4; if (!ctx->tune.b2pp_sweeps) ctx->tune.b2pp_sweeps = 6; ctx->tune.scns_inner_left = 1; ctx->tune.stored_uu = 1; }
   IFEM_API_END
@@ -1128,6 +1129,23 @@ int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int6
   dy.alloc(n);
   sm_apply_probe(ctx, path, dx.p, dy.p, info);
   if (n) IFEM_HIP_CHECK(hipMemcpyAsync(y, dy.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_test_b_apply(ifem_ctx *ctx, int which, int path, const double *x, double *y, int64_t info[4]) {
+  IFEM_API_BEGIN
+  if (which < 0 || which > 2 || path < 0 || path > 3 || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_b_apply: which 0..2, path 0..3 and info");
+  if (path >= 2) { b_apply_probe(ctx, which, path, nullptr, nullptr, info); return IFEM_OK; }
+  if (!x || !y) throw Error(IFEM_E_BADPARAM, "ifem_test_b_apply: x and y");
+  if (!ctx->assembled && !ctx->geo.valid) throw Error(IFEM_E_BADPARAM, "ifem_test_b_apply called before an assembly that left B and B^T behind");
+  const size_t nu = size_t(ctx->dim) * size_t(ctx->nUl), np = size_t(ctx->nPl), nuo = size_t(ctx->dim) * size_t(ctx->nUo), npo = size_t(ctx->nPo);
+  const size_t n_in = which == 0 ? nu : np, n_out = which == 0 ? npo : nuo;
+  DBuf<double> dx, dy;
+  dx.upload(x, n_in, ctx->stream);
+  if (which == 2) dy.upload(y, n_out, ctx->stream); else dy.alloc(n_out);
+  b_apply_probe(ctx, which, path, dx.p, dy.p, info);
+  if (n_out) IFEM_HIP_CHECK(hipMemcpyAsync(y, dy.p, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
 }

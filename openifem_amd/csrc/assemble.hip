@@ -228,7 +228,7 @@ static void assemble_epilogue(ifem_ctx *ctx, const AsmPlan &pl, int cset) {
     dinv_setup(ctx);
     ctx->asm_constraint_set = cset;
     // (M_p's single-precision copy goes stale only when M_p was re-integrated: with the unconstrained copies, or by the cell kernel)
-    geometry_written(ctx, ctx->flag_id[cset], pl.unconstrained_first || pl.geo == GeoFrom::Cell);
+    geometry_written(ctx, ctx->flag_id[cset], pl.unconstrained_first || pl.geo == GeoFrom::Cell, pl.geo != GeoFrom::Kept);
   }
   if (pl.mode == AsmMode::Full) {
     if (pl.stores_uu) bjac_setup(ctx);

@@ -428,6 +428,40 @@ struct SmStencil {
   DBuf<int32_t> rows;    // [n_irregular] the irregular rows (pressure nodes); capacity lattice / 8 + 1
   DBuf<int32_t> counter; // [1] device count of the irregular rows
 };
+
+// The velocity nodes of the same level as the full lattice n[d] = deg cells_d + 1 (setup.hip::u_lattice_ensure, host side
+// lattice.cpp::lattice_map_u): pressure point j sits at velocity point deg j.  Same eligibility and `state` protocol as PLattice.
+struct ULattice {
+  int state = 0;
+  int n[3] = {1, 1, 1};
+  int deg = 0;
+  DBuf<int32_t> node_of_lattice; // velocity node at lattice point i_x + n[0] (i_y + n[1] i_z)
+  DBuf<int32_t> lattice_of_node; // its inverse
+};
+
+// y = B x and y = B^T x from stencil tables over the two lattices (bb_stencil.hip).  A B row at pressure point j couples the velocity points
+// within +-deg of deg j (times dim components); a B^T row at velocity point i the at most 3^dim pressure points j with |i - deg j| <= deg.
+// Each block has its own tables, read off its own assembled values (with ifem_tuning::geo_cache = 2 both are masked copies: neither is assumed
+// to be the transpose of the other), re-made and probed whenever an assembly wrote the blocks (ifem_ctx::bb_version), at solve set-up.
+struct BbStencil {
+  struct Block {
+    bool ready = false;  // the tables belong to `version` and passed the probe
+    bool failed = false; // a probe failed: this block keeps the CSR product for the life of the context
+    bool said = false;   // the verbose line of a block that keeps the CSR product has been printed
+    int classes = 0, ncls[3] = {1, 1, 1};
+    int64_t n_irregular = 0;
+    DBuf<uint8_t> axcls;   // per-axis class of every coordinate of the row lattice
+    DBuf<int32_t> first;   // first coordinate of every axis class
+    DBuf<double> table;    // [classes][K] dense row of every class (component-major, then offset order), [classes] max |entry| behind it
+    DBuf<uint16_t> cls;    // [row lattice] class of the row at that point, 0xFFFF: irregular
+    DBuf<int32_t> rows;    // the irregular rows (nodes); capacity lattice / 8 + 1
+    DBuf<int32_t> counter; // [1] device count of the irregular rows
+  } b, bt;
+  bool off = false;     // test aid (ifem_test_b_apply): the context keeps the CSR products
+  bool scns = false;    // B / B^T hold the stabilised blocks of an SCnsIM assembly: ineligible until an INS assembly writes them again
+  int64_t version = -1; // ifem_ctx::bb_version the tables (or the decision against them) belong to
+  int64_t builds = 0;   // table builds so far (ifem_test_b_apply reports it: an assembly that kept the blocks adds none)
+};
 } // namespace ifem
 
 struct ifem_ctx {
@@ -477,6 +511,9 @@ struct ifem_ctx {
   ifem::PLattice p_lattice; // the pressure nodes as a full lattice, where they are one (shared by the two readers below)
   ifem::MpDirect mp_direct; // M_p^-1 by line solves where the level is a full uniform lattice (mp_direct.hip; ifem_solver_opts::mp_solver)
   ifem::SmStencil sm_stencil; // S_m x from lattice stencil tables where the level is one (sm_stencil.hip)
+  ifem::ULattice u_lattice;   // the velocity nodes as a full lattice, where they are one
+  ifem::BbStencil bb_stencil; // B x and B^T x from lattice stencil tables (bb_stencil.hip)
+  int64_t bb_version = 0;     // B / B^T values were written (re-integrated, masked, or stabilised by an SCnsIM assembly)
   // identity of the constrained-dof SET of each AffineConstraints object (which dofs, not their values): B, B^T, M_p,
   // diag(M_u) and S_m depend on nothing else, so zero_ / nonzero_constraints with the same lines share one cache entry and
   // re-making identical constraints (time-dependent boundary values) keeps it
@@ -667,11 +704,13 @@ inline void uu_written(ifem_ctx *c) {
 }
 // the inverse node blocks `bjac` written
 inline void bjac_written(ifem_ctx *c) { c->bjac_f32.stale(); }
-// an assembly left B, B^T, M_p, diag(M_u) holding the blocks of constrained-dof set `key` (re-integrated, masked or kept; `mass`: M_p
-// was re-integrated).  The single-precision copies of B / B^T are re-made once per assembly; S_m stays while the set stays
+// an assembly left B, B^T, M_p, diag(M_u) holding the blocks of constrained-dof set `key` (`blocks`: re-integrated or masked, i.e. their
+// values were written -- the stencil tables of bb_stencil.hip belong to the values; false: kept; `mass`: M_p was re-integrated).  The
+// single-precision copies of B / B^T are re-made once per assembly; S_m stays while the set stays
 // (ifem_tuning::geo_cache = 1; the reference rebuilds it every solve(), same values).
-inline void geometry_written(ifem_ctx *c, int64_t key, bool mass) {
+inline void geometry_written(ifem_ctx *c, int64_t key, bool mass, bool blocks) {
   c->B_f32.stale(); c->Bt_f32.stale();
+  if (blocks) { c->bb_version++; c->bb_stencil.scns = false; }
   if (mass) { c->Mp_f32.stale(); c->mp_direct.checked = 0; } // (the direct solve probes the new values before it trusts them again)
   c->mp_direct.mass_ready = true;
   if (key != c->sm_key || c->tune.geo_cache != 1) { c->sm_valid = false; c->sm_key = key; }
@@ -688,6 +727,7 @@ inline void scns_assembled(ifem_ctx *c) {
   uu_written(c);
   c->uu_is_stored = true;
   c->B_f32.stale(); c->Bt_f32.stale();
+  c->bb_version++; c->bb_stencil.scns = true; // (stabilised blocks: the products keep CSR)
   c->sm_valid = false; c->sm_key = -1;
   c->geo.valid = false;
   c->mf_valid = false;

@@ -157,6 +157,20 @@ void spmv_sm_rows(ifem_ctx *ctx, const double *xp, double *yp, int64_t n_list, c
 void sm_stencil_setup(ifem_ctx *ctx, int verbose);
 inline bool sm_stencil_ready(const ifem_ctx *ctx) { return ctx->sm_stencil.ready && !ctx->sm_stencil.off && ctx->sm_stencil.version == ctx->sm_version; }
 void sm_stencil_apply(ifem_ctx *ctx, const double *x, double *y);
+// bb_stencil.hip: y = B x and y (+)= B^T x from stencil tables over the pressure and velocity lattices of a uniform box level.  bb_stencil_setup:
+// solve set-up only (allocates, synchronises): (re)builds and probes the tables of both blocks when an assembly wrote them since it last looked
+// (ifem_ctx::bb_version).  bb_stencil_ready(which: 0 B, 1 B^T): spmv_b / spmv_bt / the B^T arm of spmv_uu take the stencil product (no
+// allocation, capture-safe).
+bool u_lattice_ensure(ifem_ctx *ctx); // setup.hip: the velocity nodes as a full lattice (ctx.hpp::ULattice), decided and built on first use
+void bb_stencil_setup(ifem_ctx *ctx, int verbose);
+inline bool bb_stencil_ready(const ifem_ctx *ctx, int which) {
+  const BbStencil &T = ctx->bb_stencil;
+  return !T.off && T.version == ctx->bb_version && (which ? T.bt.ready : T.b.ready);
+}
+void bb_stencil_apply_b(ifem_ctx *ctx, const double *xu, double *yp);
+void bb_stencil_apply_bt(ifem_ctx *ctx, const double *xp, double *yu, bool add);
+void spmv_b_rows(ifem_ctx *ctx, const double *xu, double *yp, int64_t n_list, const int32_t *rows); // the listed rows only, fp64 values
+void spmv_bt_rows(ifem_ctx *ctx, const double *xp, double *yu, int64_t n_list, const int32_t *rows, bool add);
 // y_u = d .* x_u (diagonal scaling with 1/diag(M_u))
 void vec_mul(ifem_ctx *ctx, int64_t n, const double *d, const double *x, double *y);
 void vec_div(ifem_ctx *ctx, int64_t n, const double *d, const double *x, double *y); // y = x ./ d (d == 0 -> 1)
@@ -299,6 +313,7 @@ void ins_system_vmult(ifem_ctx *ctx, const double *src, double *dst);
 // test aid (ifem_test_mp_solve): solve_mp under `o` on device vectors of nPo entries; info = {1 direct / 0 CG, CG iterations}
 void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int32_t info[2]);
 void sm_apply_probe(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]); // ifem_test_sm_apply on device vectors
+void b_apply_probe(ifem_ctx *ctx, int which, int path, const double *x, double *y, int64_t info[4]); // ifem_test_b_apply on device vectors
 void scns_solve(ifem_ctx *ctx, const ifem_solver_opts *o, int use_nonzero, ifem_solve_stats *stats);
 // y = A_uu z on a compact owned SINGLE-PRECISION column (ghosts refreshed on a float copy), single-precision cell arithmetic, fp64 result
 void uu_apply_f32col(ifem_ctx *ctx, const float *z, double *y);

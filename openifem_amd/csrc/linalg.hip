@@ -306,7 +306,8 @@ void spmv_uu(ifem_ctx *ctx, const double *xu, const double *xp, double *yu, bool
       hipLaunchKernelGGL(k_spmv_uu_pipe, dim3(nb), dim3(256), size_t(2 * rpb) * sizeof(int64_t), s, n, ctx->Auu.rowptr.p, ctx->Auu.col.p,
                          A.p, xu, yu, rows, rpb);
     }
-    if (xp && ctx->Bt.n_rows) { // + B^T x_p on the same rows
+    if (xp && ctx->Bt.n_rows && part == 0 && bb_stencil_ready(ctx, 1)) bb_stencil_apply_bt(ctx, xp, yu, /*add=*/true); // + B^T x_p from the lattice tables
+    else if (xp && ctx->Bt.n_rows) { // + B^T x_p on the same rows
       KScope ks(ctx, IFEM_KC_SPMV_BBT, planar_bytes(ctx->Bt, n, 8, ctx->nPl, 8, 48));
       hipLaunchKernelGGL((k_spmv_planar_add<3, 1, 8>), dim3(blocks_for_rows(n, 8)), dim3(256), 0, s, n, ctx->Bt.rowptr.p, ctx->Bt.col.p,
                          ctx->Bt.val.p, xp, yu, rows);
@@ -464,6 +465,7 @@ void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part, const double 
   const RowPart rp_ = row_part(ctx->B, part);
   const int64_t n = rp_.n;
   if (n == 0) return;
+  if (!val && part == 0 && bb_stencil_ready(ctx, 0)) { bb_stencil_apply_b(ctx, xu, yp); return; }
   if (!val) val = ctx->B.val.p;
   KScope ks(ctx, IFEM_KC_SPMV_BBT, planar_bytes(ctx->B, n, 8, ctx->nUl, 8 * ctx->dim, 8));
   if (ctx->dim == 3)
@@ -477,6 +479,7 @@ void spmv_b(ifem_ctx *ctx, const double *xu, double *yp, int part, const double 
 void spmv_bt(ifem_ctx *ctx, const double *xp, double *yu) {
   const int64_t n = ctx->Bt.n_rows;
   if (n == 0) return;
+  if (bb_stencil_ready(ctx, 1)) { bb_stencil_apply_bt(ctx, xp, yu, /*add=*/false); return; }
   KScope ks(ctx, IFEM_KC_SPMV_BBT, planar_bytes(ctx->Bt, n, 8, ctx->nPl, 8, 8 * ctx->dim));
   if (ctx->dim == 3)
     hipLaunchKernelGGL((k_spmv_planar<3, 1, 8>), dim3(blocks_for_rows(n, 8)), dim3(256), 0, ctx->stream, n,
@@ -484,6 +487,24 @@ void spmv_bt(ifem_ctx *ctx, const double *xp, double *yu) {
   else
     hipLaunchKernelGGL((k_spmv_planar<2, 1, 4>), dim3(blocks_for_rows(n, 4)), dim3(256), 0, ctx->stream, n,
                        ctx->Bt.rowptr.p, ctx->Bt.col.p, ctx->Bt.val.p, xp, yu);
+}
+
+// the listed rows of y = B x and y (+)= B^T x with the fp64 values (the irregular rows of bb_stencil.hip; inside those products' KScope)
+void spmv_b_rows(ifem_ctx *ctx, const double *xu, double *yp, int64_t n_list, const int32_t *rows) {
+  if (n_list <= 0) return;
+  if (ctx->dim == 3)
+    hipLaunchKernelGGL((k_spmv_planar<1, 3, 32>), dim3(blocks_for_rows(n_list, 32)), dim3(256), 0, ctx->stream, n_list, ctx->B.rowptr.p, ctx->B.col.p, ctx->B.val.p, xu, yp, rows);
+  else
+    hipLaunchKernelGGL((k_spmv_planar<1, 2, 16>), dim3(blocks_for_rows(n_list, 16)), dim3(256), 0, ctx->stream, n_list, ctx->B.rowptr.p, ctx->B.col.p, ctx->B.val.p, xu, yp, rows);
+}
+void spmv_bt_rows(ifem_ctx *ctx, const double *xp, double *yu, int64_t n_list, const int32_t *rows, bool add) {
+  if (n_list <= 0) return;
+  const PlanarCsr &M = ctx->Bt;
+  hipStream_t s = ctx->stream;
+  if (ctx->dim == 3 && add) hipLaunchKernelGGL((k_spmv_planar_add<3, 1, 8>), dim3(blocks_for_rows(n_list, 8)), dim3(256), 0, s, n_list, M.rowptr.p, M.col.p, M.val.p, xp, yu, rows);
+  else if (ctx->dim == 3) hipLaunchKernelGGL((k_spmv_planar<3, 1, 8>), dim3(blocks_for_rows(n_list, 8)), dim3(256), 0, s, n_list, M.rowptr.p, M.col.p, M.val.p, xp, yu, rows);
+  else if (add) hipLaunchKernelGGL((k_spmv_planar_add<2, 1, 4>), dim3(blocks_for_rows(n_list, 4)), dim3(256), 0, s, n_list, M.rowptr.p, M.col.p, M.val.p, xp, yu, rows);
+  else hipLaunchKernelGGL((k_spmv_planar<2, 1, 4>), dim3(blocks_for_rows(n_list, 4)), dim3(256), 0, s, n_list, M.rowptr.p, M.col.p, M.val.p, xp, yu, rows);
 }
 
 // single-precision copies of B and B^T for the matrix-free S_m = B diag(M_u)^-1 B^T inside the approximate-preconditioner

@@ -574,6 +574,32 @@ bool p_lattice_ensure(ifem_ctx *ctx) {
   return true;
 }
 
+// the velocity nodes as a full lattice (ctx.hpp::ULattice): the same eligibility, decided and built on first use, once per context
+bool u_lattice_ensure(ifem_ctx *ctx) {
+  ULattice &L = ctx->u_lattice;
+  if (L.state != 0) return L.state > 0;
+  L.state = -1;
+  const int dim = ctx->dim, deg = ctx->kv;
+  if (!p_lattice_ensure(ctx)) return false; // (one rank, no hanging-node line, uniform box cells, Q1 pressure in 2D / 3D)
+  int nloc = 1;
+  for (int d = 0; d < dim; ++d) nloc *= deg + 1;
+  if ((deg != 1 && deg != 2) || ctx->nu != nloc || ctx->nUo != ctx->nUl) return false;
+  hipStream_t s = ctx->stream;
+  const std::vector<double> vc = ctx->vcoords.download(s);
+  const std::vector<int32_t> cu = ctx->cell_unodes.download(s);
+  if (vc.size() != size_t(ctx->n_cells) * ctx->np * dim || cu.size() != size_t(ctx->n_cells) * ctx->nu) return false;
+  std::vector<int32_t> nol, lon;
+  if (!lattice_map_u(dim, deg, ctx->n_cells, ctx->nUo, vc.data(), cu.data(), ctx->mf_h, L.n, nol, lon)) return false;
+  for (int d = 0; d < dim; ++d)
+    if (L.n[d] != deg * (ctx->p_lattice.n[d] - 1) + 1) return false;
+  L.deg = deg;
+  L.node_of_lattice.upload(nol.data(), nol.size(), s);
+  L.lattice_of_node.upload(lon.data(), lon.size(), s);
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  L.state = 1;
+  return true;
+}
+
 // ---- cell tables of the matrix-free apply on several ranks: interior cells (all nodes owned) first, then the cells that
 // touch a ghost node; order kept inside both groups (the Morton locality survives)
 __global__ void k_cell_flag(int64_t n_cells, int nu, const int32_t *__restrict__ cell_unodes, int32_t n_owned, int64_t *__restrict__ flag) {

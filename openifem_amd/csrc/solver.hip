@@ -269,6 +269,14 @@ static void sm_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   const SmStencil &T = lc->sm_stencil;
   key.push_back(uint64_t(sm_stencil_ready(lc))); key.push_back(uint64_t(T.n_irregular));
   key_ptr(key, T.table.p); key_ptr(key, T.cls.p); key_ptr(key, T.rows.p); key_ptr(key, lc->p_lattice.node_of_lattice.p);
+  // S_m in operator form launches the B^T and B products: which ones, and the tables of the stencil ones (bb_stencil.hip)
+  const BbStencil &Q = lc->bb_stencil;
+  for (int which = 0; which < 2; ++which) {
+    const BbStencil::Block &K = which ? Q.bt : Q.b;
+    key.push_back(uint64_t(bb_stencil_ready(lc, which))); key.push_back(uint64_t(K.n_irregular));
+    key_ptr(key, K.table.p); key_ptr(key, K.cls.p); key_ptr(key, K.rows.p);
+  }
+  key_ptr(key, lc->u_lattice.node_of_lattice.p); key_ptr(key, lc->B.val.p); key_ptr(key, lc->Bt.val.p);
 }
 static void uu_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   (void)bjac_f32_ptr(lc); // lazy state (the single-precision copy of the inverse node blocks) stays outside the graph
@@ -1182,6 +1190,34 @@ void sm_apply_probe(ifem_ctx *ctx, int path, const double *x, double *y, int64_t
   info[3] = on ? int64_t(T.table.n * sizeof(double)) : 0;
 }
 
+// ifem_test_b_apply: y = B x (which 0), y = B^T x (1) or y += B^T x (2) on device vectors, x ghost-extended, y owned.  path 0: the fp64 CSR
+// product of the assembled block; 1: what the solves launch (the tables are made first, as a solve's set-up makes them); 2 / 3: switch the stencil
+// products of this context off / on again (x, y unused; 3 also makes the tables of the present blocks).  info: 0 when the product of `which` is the
+// CSR one, otherwise the number of table builds this context has made so far | classes | irregular rows | table bytes
+void b_apply_probe(ifem_ctx *ctx, int which, int path, const double *x, double *y, int64_t info[4]) {
+  BbStencil &T = ctx->bb_stencil;
+  const int blk = which ? 1 : 0;
+  if (path == 2 || path == 3) {
+    T.off = path == 2;
+    ctx->graph_epoch++; // captured cycles are keyed on the products they launch
+    if (path == 3) bb_stencil_setup(ctx, 0);
+  } else {
+    if (path == 1) bb_stencil_setup(ctx, 0);
+    const bool stencil = path == 1 && bb_stencil_ready(ctx, blk);
+    if (which == 0) {
+      if (stencil) bb_stencil_apply_b(ctx, x, y);
+      else spmv_b_rows(ctx, x, y, ctx->B.n_rows, nullptr);
+    } else if (stencil) bb_stencil_apply_bt(ctx, x, y, which == 2);
+    else spmv_bt_rows(ctx, x, y, ctx->Bt.n_rows, nullptr, which == 2);
+  }
+  const bool on = bb_stencil_ready(ctx, blk);
+  const BbStencil::Block &K = blk ? T.bt : T.b;
+  info[0] = on ? T.builds : 0;
+  info[1] = on ? K.classes : 0;
+  info[2] = on ? K.n_irregular : 0;
+  info[3] = on ? int64_t(K.table.n * sizeof(double)) : 0;
+}
+
 // right-hand side of the condensed system after an assembly that treated the hanging dofs as ordinary ones:
 // b = C^T (b^ - A^ c0) on the regular rows, d_h c0_h on the hanging rows (distribute_local_to_global semantics)
 void hanging_condense_rhs(ifem_ctx *ctx, int use_nonzero) {
@@ -1409,6 +1445,7 @@ void ins_solve(ifem_ctx *ctx, const ifem_ins_params *P, const ifem_solver_opts *
   SolveState S{ctx, P, o};
   carve_workspace(S);
   Clock total;
+  bb_stencil_setup(ctx, o->verbose); // (re)builds and probes the lattice tables of B and B^T when an assembly wrote the blocks: set-up time only
   ctx->pc_used = 0;
   ctx->spmv_uu_ms_total = 0;
   ctx->timing.spmv_uu_calls = 0;
