@@ -129,7 +129,18 @@ typedef struct {
                                  fifth of the time) -- an experiment switch, off by default */
   int32_t sm_mg;              /* 1 (default): when coarser levels are attached (ifem_mg_attach) and S_m is explicit, the
                                  S_m solve of the preconditioner (mpi_insim.cpp:86-112) is CG preconditioned by one multigrid
-                                 V-cycle, same stopping rule on the true residual; 0: plain CG as in the reference */
+                                 V-cycle, same stopping rule on the true residual; 0: plain CG as in the reference;
+                                 2 (opt-in): S_m^-1 by fast diagonalisation (sm_direct.hip) where the level qualifies, exactly the
+                                 behaviour of 1 elsewhere.  A level qualifies when it is the finest level of a uniform axis-aligned
+                                 Q2/Q1 box on one rank without hanging-node lines (ifem_tuning::mf_uniform on), explicit_schur is on,
+                                 no SCnsIM assembly has written its blocks, it has at most 513 pressure nodes per axis, the
+                                 constrained velocity dofs are whole faces per component (no-slip, free and normal-only faces; a face
+                                 that holds one tangential component only keeps CG), the block is not singular (the enclosed flow
+                                 keeps CG), and x = direct(e) reproduces a probe vector through the assembled S_m to 1e-7 -- probed
+                                 again whenever S_m is re-formed; a failed probe keeps CG on that context from then on.  S_m^-1 is
+                                 then six dense 1D contractions on the FP64 matrix cores and one scale (the solution to rounding, so
+                                 sm_rel / sm_abs are met trivially); the coarser S_m levels are not touched,
+                                 ifem_solve_stats::cg_sm_iters stays as it is and sm_mg_levels is 0 */
   int32_t mg_smooth;          /* 2: Chebyshev-Jacobi smoothing steps before and after the coarse correction */
   double  mg_cheb_ratio;      /* 4: the smoother targets the eigenvalues of D^-1 S_m in [lambda_max / ratio, lambda_max] */
   int32_t mg_smooth_u;        /* 2: smoothing steps of the A_uu V-cycle (IFEM_AINV_MG) */

@@ -111,6 +111,14 @@ int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b
  * info = {1 the stencil product is in use / 0, its classes, its irregular rows (produced by the CSR kernel), bytes of its table}. */
 int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]);
 
+/* The S_m solve of the block preconditioner (solver.hip::solve_sm) on host vectors of n_pnodes (owned) doubles: x = what it produces for b under
+ * the options o (NULL: the defaults), by fast diagonalisation (sm_direct.hip) where ifem_solver_opts::sm_mg = 2, the level qualifies and its
+ * factors passed the probe against the present S_m, by (multigrid-preconditioned) CG to max(sm_abs, sm_rel ||b||) elsewhere.  Forms S_m, and
+ * with sm_mg = 2 the factors, when they are not there yet, as a solve would.  After an assembly.
+ * info = {1 direct / 0 CG, CG iterations, the probe value max |S_m x - e| / max |e| of the factors x 1e18 as an integer (0: CG), bytes of the
+ * factor tables}. */
+int ifem_test_sm_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int64_t info[4]);
+
 /* The products with the off-diagonal blocks on host vectors.  which 0: y = B x (x: dim * n_unodes_local doubles, node-interleaved, ghost entries
  * filled by the caller; y: n_pnodes_owned), 1: y = B^T x (x: n_pnodes_local; y: dim * n_unodes_owned), 2: y += B^T x (y in and out).  After an
  * assembly that left the blocks behind.  No exchange is made: on several ranks every rank multiplies what it is given.

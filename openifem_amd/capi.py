@@ -149,9 +149,12 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
-           "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply",
+           "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply", "ifem_test_sm_solve",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
+
+# ifem_solver_opts::sm_mg: plain CG | multigrid-preconditioned CG (the default) | the fast-diagonalisation solve where the level qualifies, SM_MG elsewhere
+SM_CG, SM_MG, SM_DIRECT = 0, 1, 2
 
 # ops of ifem_test_vec_kernel (IFEM_TVK_*)
 (TVK_MDOT, TVK_MDOT_SELF, TVK_MAXPY, TVK_MAXPY_NORM, TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32, TVK_AXPY,
@@ -250,6 +253,7 @@ def load():
                                              C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_test_mp_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_sm_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_test_sm_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_b_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
@@ -623,6 +627,14 @@ class Context:
         x, info = np.zeros(len(b)), np.zeros(2, np.int32)
         self._chk(self.L.ifem_test_mp_solve(self.h, C.byref(self.opts if opts is None else opts), _ptr(b), _ptr(x), _ptr(info)))
         return x, bool(info[0]), int(info[1])
+
+    def sm_solve(self, b, opts=None):
+        """(x, info): the S_m solve of the block preconditioner for the host vector b (owned pressure nodes) under `opts` (default: self.opts).
+        info = [1 direct / 0 CG, CG iterations, probe value x 1e18 of the direct path or 0, bytes of its factor tables] -- ifem_test_sm_solve"""
+        b = np.ascontiguousarray(b, float)
+        x, info = np.zeros(len(b)), np.zeros(4, np.int64)
+        self._chk(self.L.ifem_test_sm_solve(self.h, C.byref(self.opts if opts is None else opts), _ptr(b), _ptr(x), _ptr(info)))
+        return x, info
 
     def sm_apply(self, path, x=None):
         """(y, info): y = S_m x for the host vector x (owned pressure nodes); path 0 the fp64 CSR product of the assembled matrix, 1 the

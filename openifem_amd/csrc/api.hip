@@ -1116,6 +1116,22 @@ int ifem_test_mp_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b
   IFEM_API_END
 }
 
+int ifem_test_sm_solve(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int64_t info[4]) {
+  IFEM_API_BEGIN
+  if (!b || !x || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_solve: b, x and info");
+  if (!ctx->assembled && !ctx->geo.valid) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_solve called before an assembly that left B, B^T and diag(M_u) behind");
+  const ifem_solver_opts oo = opts_or_default(o);
+  const size_t n = size_t(ctx->nPo);
+  DBuf<double> db, dx;
+  db.upload(b, n, ctx->stream);
+  dx.alloc(n);
+  if (n) IFEM_HIP_CHECK(hipMemsetAsync(dx.p, 0, n * sizeof(double), ctx->stream));
+  sm_solve_probe(ctx, &oo, db.p, dx.p, info);
+  if (n) IFEM_HIP_CHECK(hipMemcpyAsync(x, dx.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
 int ifem_test_sm_apply(ifem_ctx *ctx, int path, const double *x, double *y, int64_t info[4]) {
   IFEM_API_BEGIN
   if (path < 0 || path > 3 || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_sm_apply: path 0..3 and info");

@@ -429,6 +429,28 @@ struct SmStencil {
   DBuf<int32_t> counter; // [1] device count of the irregular rows
 };
 
+// x = S_m^-1 b by fast diagonalisation on a uniform Q2/Q1 box level whose constrained velocity dofs are whole faces (sm_direct.hip;
+// ifem_solver_opts::sm_mg = 2): S_m^-1 = (Q_z (x) Q_y (x) Q_x) diag(1 / (lambda_x + lambda_y + lambda_z)) (Q_z (x) Q_y (x) Q_x)^T.  Decided,
+// and probed against the assembled S_m, whenever S_m is re-formed (`version`); the factors of an axis are kept while its key (cells, edge,
+// masks) stays.
+struct SmDirect {
+  int64_t version = -1; // ifem_ctx::sm_version the decision belongs to
+  bool ready = false;   // the factors stand and passed the probe of that version
+  bool failed = false;  // a probe failed: the context keeps CG from then on
+  int64_t builds = 0;   // axis eigen-solves this context has made (a re-formed S_m with the same keys adds none)
+  double probe = 0;     // max |S_m x - e| / max |e| of the last probe
+  double build_ms = 0;  // host time of the last factor build
+  int npad[3] = {0, 0, 0}; // nodes per axis rounded up to the MFMA tile (16)
+  // per axis: the key (cells, edge, masks of the own / the other components) of the tables below
+  int key_n[3] = {0, 0, 0}, key_own[3] = {0, 0, 0}, key_other[3] = {0, 0, 0};
+  double key_h[3] = {0, 0, 0}, lam_min[3] = {0, 0, 0}, lam_max[3] = {0, 0, 0};
+  DBuf<double> Q[3], Qt[3]; // [npad][npad] row-major, zero-padded: Q and its transpose
+  DBuf<double> lam[3];      // [n] eigenvalues of the axis
+  DBuf<double> w0, w1;      // lattice-ordered work vectors of the contractions
+  DBuf<int64_t> scan;       // [3 + 18] constrained dofs per component, face-centre flags (k_smd_masks)
+  size_t bytes() const { size_t b = 0; for (int a = 0; a < 3; ++a) b += (Q[a].n + Qt[a].n + lam[a].n) * sizeof(double); return b; }
+};
+
 // The velocity nodes of the same level as the full lattice n[d] = deg cells_d + 1 (setup.hip::u_lattice_ensure, host side
 // lattice.cpp::lattice_map_u): pressure point j sits at velocity point deg j.  Same eligibility and `state` protocol as PLattice.
 struct ULattice {
@@ -511,6 +533,7 @@ struct ifem_ctx {
   ifem::PLattice p_lattice; // the pressure nodes as a full lattice, where they are one (shared by the two readers below)
   ifem::MpDirect mp_direct; // M_p^-1 by line solves where the level is a full uniform lattice (mp_direct.hip; ifem_solver_opts::mp_solver)
   ifem::SmStencil sm_stencil; // S_m x from lattice stencil tables where the level is one (sm_stencil.hip)
+  ifem::SmDirect sm_direct;   // S_m^-1 by fast diagonalisation where the level qualifies (sm_direct.hip; ifem_solver_opts::sm_mg = 2)
   ifem::ULattice u_lattice;   // the velocity nodes as a full lattice, where they are one
   ifem::BbStencil bb_stencil; // B x and B^T x from lattice stencil tables (bb_stencil.hip)
   int64_t bb_version = 0;     // B / B^T values were written (re-integrated, masked, or stabilised by an SCnsIM assembly)

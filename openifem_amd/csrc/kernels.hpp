@@ -157,6 +157,13 @@ void spmv_sm_rows(ifem_ctx *ctx, const double *xp, double *yp, int64_t n_list, c
 void sm_stencil_setup(ifem_ctx *ctx, int verbose);
 inline bool sm_stencil_ready(const ifem_ctx *ctx) { return ctx->sm_stencil.ready && !ctx->sm_stencil.off && ctx->sm_stencil.version == ctx->sm_version; }
 void sm_stencil_apply(ifem_ctx *ctx, const double *x, double *y);
+// sm_direct.hip: x = S_m^-1 b by fast diagonalisation (ifem_solver_opts::sm_mg = 2).  sm_direct_setup: set-up time only, after sm_stencil_setup
+// (allocates, synchronises): decides the level, builds the factors of a new key and probes them against the present S_m whenever S_m was
+// re-formed since it last looked.  sm_direct_ready: solve_sm may take sm_direct_apply (seven launches, no allocation; b and x may not alias)
+void sm_direct_setup(ifem_ctx *ctx, int verbose);
+inline bool sm_direct_ready(const ifem_ctx *ctx) { return ctx->sm_direct.ready && ctx->sm_direct.version == ctx->sm_version; }
+void sm_direct_apply(ifem_ctx *ctx, const double *b, double *x);
+void sm_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int64_t info[4]); // ifem_test_sm_solve on device vectors
 // bb_stencil.hip: y = B x and y (+)= B^T x from stencil tables over the pressure and velocity lattices of a uniform box level.  bb_stencil_setup:
 // solve set-up only (allocates, synchronises): (re)builds and probes the tables of both blocks when an assembly wrote them since it last looked
 // (ifem_ctx::bb_version).  bb_stencil_ready(which: 0 B, 1 B^T): spmv_b / spmv_bt / the B^T arm of spmv_uu take the stencil product (no

@@ -143,6 +143,7 @@ static void sm_ensure(SolveState &S) {
     if (c->Sm.n_rows == 0) build_schur_pattern(c);
     schur_numeric(c);
     sm_stencil_setup(c, S.o->verbose); // (re)builds and probes the lattice stencil tables when S_m was re-formed: set-up time, never inside sm_apply
+    if (S.o->sm_mg == 2) sm_direct_setup(c, S.o->verbose); // the fast-diagonalisation factors and their probe (sm_direct.hip), with the product above
     return;
   }
   // same matrix, distributed: pattern from the pressure lattice, values by probing
@@ -973,6 +974,12 @@ static void solve_sm(SolveState &S, const double *b, double *x) {
   const bool lowp = approx_kind(o);
   const double tol = std::max(o->sm_abs, o->sm_rel * S.p_src_norm);
   sm_ensure(S);
+  // ifem_solver_opts::sm_mg = 2, a uniform box level whose factors passed the probe of the present S_m (sm_direct.hip): six contractions and a
+  // scale, the solution to rounding; the coarser levels are not touched, cg_sm_iters stays as it is, sm_mg_levels stays 0
+  if (o->sm_mg == 2 && sm_direct_ready(c)) {
+    sm_direct_apply(c, b, x);
+    return;
+  }
   const OpFn sm = [&](const double *u, double *y) { sm_apply(S, u, y, lowp); };
   // multigrid-preconditioned CG when coarser levels are attached (every level needs its S_m explicitly: Jacobi smoothing)
   // (the finest level may apply S_m as two SpMVs -- several ranks without the 2-deep pressure halo, e.g. the strips of an unstructured
@@ -1165,6 +1172,20 @@ void mp_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, d
   S.p_src_norm = std::sqrt(dot_all(S, S.npo, b, b));
   info[0] = solve_mp(S, b, x) ? 1 : 0;
   info[1] = int32_t(S.st.cg_mp_iters);
+}
+
+// ifem_test_sm_solve: x = what solve_sm produces for b under o; info = {1 direct / 0 CG, CG iterations, probe value x 1e18 (0: no direct path),
+// bytes of the factor tables}
+void sm_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, double *x, int64_t info[4]) {
+  SolveState S{ctx, nullptr, o};
+  carve_workspace(S);
+  S.p_src_norm = std::sqrt(dot_all(S, S.npo, b, b));
+  solve_sm(S, b, x);
+  const bool direct = o->sm_mg == 2 && sm_direct_ready(ctx);
+  info[0] = direct ? 1 : 0;
+  info[1] = int64_t(S.st.cg_sm_iters);
+  info[2] = direct ? int64_t(std::llround(std::min(ctx->sm_direct.probe, 9.0) * 1e18)) : 0;
+  info[3] = direct ? int64_t(ctx->sm_direct.bytes()) : 0;
 }
 
 // ifem_test_sm_apply: y = S_m x on device vectors of owned pressure nodes.  path 0: the fp64 CSR product of the assembled matrix (one rank); 1: sm_apply
