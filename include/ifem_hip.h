@@ -393,7 +393,10 @@ typedef struct {
   /* optional (all NULL: pressure levels only): the same for the velocity NODES (applied to the dim components of a node),
    * rows of P_u = owned velocity nodes of `fine`, columns = local velocity nodes of `coarse`, R_u = P_u^T; inj_u
    * [n_unodes_owned of coarse]: the owned velocity node of `fine` at the same point (nested meshes: the coarse evaluation
-   * point is the fine one restricted by injection) -- enables IFEM_AINV_MG */
+   * point is the fine one restricted by injection) -- enables IFEM_AINV_MG.
+   * Every weight of pu_w and ru_w must be EXACT IN SINGLE PRECISION (double(float(w)) == w): the node transfers store them as float (the
+   * weights of nested Q1 / Q2 interpolation, products of 1, 3/4, 3/8, -1/8, 1/2, are); ifem_mg_attach returns IFEM_E_BADPARAM for any other
+   * weight.  pp_w and rp_w are applied in double precision and carry no such restriction. */
   int64_t n_fine_u_owned, n_coarse_u_local;
   const int64_t *pu_ptr; const int32_t *pu_col; const double *pu_w;
   const int64_t *ru_ptr; const int32_t *ru_col; const double *ru_w;

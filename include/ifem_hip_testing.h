@@ -93,6 +93,43 @@ int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double 
 int ifem_test_uu_fused_product(ifem_ctx *ctx, int prec, int mode, int first, double a, double b, const double *x, double *xs, double *r, double *d,
                                int block_cap, int64_t geo[2]);
 
+/* The host launchers of the multigrid kernels (mg.hip, as declared in kernels.hpp: the dispatch inside them is part of what runs), ONE per call, on
+ * host data: device scratch, upload, the call, a stream synchronisation, download.  Single-rank contexts.  Every array an op WRITES has
+ * IFEM_TMG_PAD more entries than the op may touch; on the device the whole array starts as 0xff bytes (NaN) and comes back whole: an entry the op
+ * left out is NaN, and so is the padding unless the op wrote past its end.  Single-precision device vectors cross the interface as doubles, rounded
+ * on the way in and widened on the way out.
+ *
+ * ifem_test_mg_transfer: a CSR transfer table of n_rows x n_cols (ptr: n_rows + 1, col / w: ptr[n_rows] entries), checked on the host as
+ * ifem_mg_attach checks its tables (spanning, non-decreasing, columns in range, n_cols < 2^29); needs a created context only, whose dim selects the
+ * node kernels.
+ *   kind 0: y = W x by mg_csr_apply, the scalar transfer of the S_m cycle: x n_cols doubles, y n_rows (+ pad) doubles, fp64 weights
+ *   kind 1: mg_csr_mask, then mg_csr_apply_nodes_f32, the node transfer of the A_uu cycle: x n_cols * dim, y n_rows * dim (+ pad), both float on the
+ *           device; flag_in [n_cols * dim] / flag_out [n_rows * dim] (either may be NULL): non-zero drops that component of the column / row node */
+enum { IFEM_TMG_PAD = 8 };
+int ifem_test_mg_transfer(ifem_ctx *ctx, int kind, int64_t n_rows, int64_t n_cols, const int64_t *ptr, const int32_t *col, const double *w,
+                          const uint8_t *flag_in, const uint8_t *flag_out, const double *x, double *y);
+
+/* ifem_test_mg_vec_kernel: the vector kernels of the two V-cycles on n entries (outputs: n + IFEM_TMG_PAD).  [f]: float on the device.
+ *   IFEM_TMG_CHEB_INIT            out0 = coef[0] in0 in1                                  in0 = D^-1, in1 = r
+ *   IFEM_TMG_CHEB_STEP            out0 += out2, out1 -= in1, out2 = coef[0] out2 + coef[1] in0 out1      in0 = D^-1, in1 = t; out0 / out1 / out2 = x / r / d,
+ *                                 in and out; in0 and in1 return what the device holds after the call (they must come back unchanged)
+ *   IFEM_TMG_VEC_RECIP            out0 = 1 / out0, a zero gives 1 (in place)
+ *   IFEM_TMG_VEC_ROUGH            out0 = the rough start vector of the power iteration, offset m
+ *   IFEM_TMG_CVT_D2F              out0 [f] = in0                IFEM_TMG_CVT_F2D   out0 = in0 [f]
+ *   IFEM_TMG_AXPY_F32V            out0 [f] += float(coef[0]) in0 [f] (in place)
+ *   IFEM_TMG_VC_EXIT              out0 = in0 [f] + in1 [f]      IFEM_TMG_VC_EXIT_F32   the same with out0 [f]
+ *   IFEM_TMG_INJECT_NODES         out0 [n * dim] = in0 [m * dim] at the nodes idx [n] (values in [-1, m); -1 gives zeros): n coarse, m fine nodes
+ * the node-block ops read the inverse node blocks of the context (ifem_uu_block_diag(ctx, 0, .)): after an assembly, n = dim * n_unodes
+ *   IFEM_TMG_VC_ENTRY             out0 [f] = in0, out1 [f] = coef[0] B out0               IFEM_TMG_VC_ENTRY_F32   the same with in0 [f]
+ *   IFEM_TMG_CHEB_INIT_BLOCK_F32  out0 [f] = coef[0] B in0 [f]
+ * Arguments an op does not use may be NULL. */
+enum {
+  IFEM_TMG_CHEB_INIT = 0, IFEM_TMG_CHEB_STEP, IFEM_TMG_VEC_RECIP, IFEM_TMG_VEC_ROUGH, IFEM_TMG_CVT_D2F, IFEM_TMG_CVT_F2D, IFEM_TMG_AXPY_F32V,
+  IFEM_TMG_VC_EXIT, IFEM_TMG_VC_EXIT_F32, IFEM_TMG_INJECT_NODES, IFEM_TMG_VC_ENTRY, IFEM_TMG_VC_ENTRY_F32, IFEM_TMG_CHEB_INIT_BLOCK_F32, IFEM_TMG_COUNT
+};
+int ifem_test_mg_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int64_t m, const double *coef, const int32_t *idx, double *in0, double *in1,
+                            double *out0, double *out1, double *out2);
+
 /* The M_p solve of the block preconditioner (solver.hip::solve_mp) on host vectors of n_pnodes (owned) doubles: x = what it produces for b under
  * the options o (NULL: the defaults), by the tensor-product line solves where the level qualifies and ifem_solver_opts::mp_solver = 0, by CG to
  * max(mp_abs, mp_rel ||b||) elsewhere.  info = {1 direct / 0 CG, CG iterations}.  After an assembly that integrated M_p (a multigrid level: after

@@ -150,6 +150,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
            "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply", "ifem_test_sm_solve",
+           "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
 
@@ -159,6 +160,11 @@ SM_CG, SM_MG, SM_DIRECT = 0, 1, 2
 # ops of ifem_test_vec_kernel (IFEM_TVK_*)
 (TVK_MDOT, TVK_MDOT_SELF, TVK_MAXPY, TVK_MAXPY_NORM, TVK_MDOT_F32, TVK_MAXPY_F32, TVK_MAXPY_F32_NORM, TVK_SCALE_STORE_F32, TVK_AXPY,
  TVK_AXPBY, TVK_SCALE_TO2, TVK_DIV, TVK_MINMAX) = range(13)
+
+# ops of ifem_test_mg_vec_kernel (IFEM_TMG_*) and the padding behind every array the multigrid test aids write (IFEM_TMG_PAD)
+(TMG_CHEB_INIT, TMG_CHEB_STEP, TMG_VEC_RECIP, TMG_VEC_ROUGH, TMG_CVT_D2F, TMG_CVT_F2D, TMG_AXPY_F32V, TMG_VC_EXIT, TMG_VC_EXIT_F32,
+ TMG_INJECT_NODES, TMG_VC_ENTRY, TMG_VC_ENTRY_F32, TMG_CHEB_INIT_BLOCK_F32) = range(13)
+TMG_PAD = 8
 
 # ifem_abi_sizeof(which): the ctypes mirror of every struct of the header
 ABI_STRUCTS = None  # filled below (needs every class defined)
@@ -255,6 +261,8 @@ def load():
     L.ifem_test_sm_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_sm_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_b_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_test_mg_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7
+    L.ifem_test_mg_vec_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
     L.ifem_kprof_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -619,6 +627,34 @@ class Context:
         x = np.zeros(len(a))
         self._chk(self.L.ifem_test_cg_device(self.h, len(a), _ptr(a), _ptr(jac), _ptr(b), iters, _ptr(x)))
         return x
+
+    def test_mg_transfer(self, kind, n_cols, ptr, col, w, x, flag_in=None, flag_out=None):
+        """y = W x for the CSR table (ptr, col, w) of len(ptr) - 1 rows and n_cols columns through the launchers of mg.hip: kind 0 the scalar
+        transfer (mg_csr_apply, fp64), kind 1 the masked node transfer (mg_csr_mask + mg_csr_apply_nodes_f32; x and y hold dim components per
+        node and are float on the device).  Returns the WHOLE output, TMG_PAD guard entries included (NaN when untouched) -- ifem_test_mg_transfer"""
+        ptr, col = np.ascontiguousarray(ptr, np.int64), np.ascontiguousarray(col, np.int32)
+        w, x = np.ascontiguousarray(w, float), np.ascontiguousarray(x, float)
+        flag_in = None if flag_in is None else np.ascontiguousarray(flag_in, np.uint8)
+        flag_out = None if flag_out is None else np.ascontiguousarray(flag_out, np.uint8)
+        n_rows, per = len(ptr) - 1, (self.dim if kind == 1 else 1)
+        assert len(col) == len(w) and x.size == n_cols * per
+        assert flag_in is None or flag_in.size == n_cols * per
+        assert flag_out is None or flag_out.size == n_rows * per
+        y = np.zeros(n_rows * per + TMG_PAD)
+        self._chk(self.L.ifem_test_mg_transfer(self.h, kind, n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(w), _ptr(flag_in), _ptr(flag_out),
+                                               _ptr(x), _ptr(y)))
+        return y
+
+    def test_mg_vec_kernel(self, op, n, m=0, coef=None, idx=None, in0=None, in1=None, out0=None, out1=None, out2=None):
+        """one host launcher of the multigrid vector kernels (TMG_*) on C-contiguous float64 host arrays (idx: int32); the out arrays hold
+        TMG_PAD entries more than the op writes and come back whole; in0 / in1 are rewritten by TMG_CHEB_STEP only -- ifem_test_mg_vec_kernel"""
+        for a in (coef, in0, in1, out0, out1, out2):
+            assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous)
+        assert idx is None or (idx.dtype == np.int32 and idx.flags.c_contiguous)
+        per = self.dim if op == TMG_INJECT_NODES else 1
+        for a in (out0, out1, out2):
+            assert a is None or a.size == n * per + TMG_PAD
+        self._chk(self.L.ifem_test_mg_vec_kernel(self.h, op, n, m, _ptr(coef), _ptr(idx), _ptr(in0), _ptr(in1), _ptr(out0), _ptr(out1), _ptr(out2)))
 
     def mp_solve(self, b, opts=None):
         """(x, direct?, CG iterations): the M_p solve of the block preconditioner for the host vector b (owned pressure nodes) under

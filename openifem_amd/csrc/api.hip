@@ -469,6 +469,9 @@ int ifem_mg_attach(ifem_ctx *fine, ifem_ctx *coarse, const ifem_mg_transfer *t) 
     for (int64_t k = 0; k < nu; ++k) {
       if (t->pu_col[k] < 0 || t->pu_col[k] >= coarse->nUl) throw Error(IFEM_E_BADPARAM, "ifem_mg_attach: P_u column out of range");
       if (t->ru_col[k] < 0 || t->ru_col[k] >= fine->nUo) throw Error(IFEM_E_BADPARAM, "ifem_mg_attach: R_u column out of range");
+      // the node transfers read their weights as float (mg.hip::mg_csr_mask): a weight that single precision cannot hold would be rounded silently
+      if (double(float(t->pu_w[k])) != t->pu_w[k]) throw Error(IFEM_E_BADPARAM, "ifem_mg_attach: a P_u weight (pu_w) is not exact in single precision");
+      if (double(float(t->ru_w[k])) != t->ru_w[k]) throw Error(IFEM_E_BADPARAM, "ifem_mg_attach: an R_u weight (ru_w) is not exact in single precision");
     }
     for (int64_t i = 0; i < coarse->nUo; ++i)
       if ((t->inj_u[i] < 0 && !(replica && t->inj_u[i] == -1)) || t->inj_u[i] >= fine->nUo)
@@ -1098,6 +1101,195 @@ int ifem_test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double 
   if (n <= 0 || iters < 0 || !a || !b || !x) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: n > 0, iters >= 0, a, b and x");
   if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_cg_device: single-rank contexts");
   test_cg_device(ctx, n, a, jac, b, iters, x);
+  IFEM_API_END
+}
+
+// ---- test aids of the multigrid kernels (mg.hip).  Every device array an op writes has IFEM_TMG_PAD entries behind what the op may write and starts
+// as 0xff bytes (NaN): the host gets the whole array back, so an entry left out and a write past the end both show.
+extern "C++" {
+namespace {
+template <typename T>
+struct GuardedOut { // device output of n + IFEM_TMG_PAD entries of T, exchanged with a host array of as many doubles
+  DBuf<T> d;
+  size_t n = 0;
+  // NaN everywhere; in_out: the first n entries are the host's (rounded to T)
+  void open(const double *host, size_t n_, bool in_out, hipStream_t s) {
+    n = n_;
+    d.alloc(n + IFEM_TMG_PAD);
+    IFEM_HIP_CHECK(hipMemsetAsync(d.p, 0xff, (n + IFEM_TMG_PAD) * sizeof(T), s));
+    if (in_out && n) {
+      std::vector<T> h(host, host + n);
+      IFEM_HIP_CHECK(hipMemcpyAsync(d.p, h.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
+      IFEM_HIP_CHECK(hipStreamSynchronize(s)); // h leaves scope
+    }
+  }
+  void close(double *host, hipStream_t s) {
+    std::vector<T> h(n + IFEM_TMG_PAD);
+    IFEM_HIP_CHECK(hipMemcpyAsync(h.data(), d.p, h.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < h.size(); ++i) host[i] = double(h[i]);
+  }
+};
+// device input of n entries of T from a host array of doubles (rounded to T)
+template <typename T>
+void upload_as(DBuf<T> &d, const double *host, size_t n, hipStream_t s) {
+  std::vector<T> h(host, host + n);
+  d.upload(h.data(), n, s);
+  IFEM_HIP_CHECK(hipStreamSynchronize(s)); // h leaves scope
+}
+} // namespace
+} // extern "C++"
+
+int ifem_test_mg_transfer(ifem_ctx *ctx, int kind, int64_t n_rows, int64_t n_cols, const int64_t *ptr, const int32_t *col, const double *w,
+                          const uint8_t *flag_in, const uint8_t *flag_out, const double *x, double *y) {
+  IFEM_API_BEGIN
+  if (kind < 0 || kind > 1 || n_rows < 0 || n_cols < 0 || !ptr || !y) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: kind 0 / 1, n_rows >= 0, n_cols >= 0, ptr and y");
+  if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: single-rank contexts");
+  if (n_cols >= (int64_t(1) << 29)) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: packed entries hold 29 column bits");
+  // the table as ifem_mg_attach checks it: a malformed one would send the kernels out of bounds
+  const int64_t nnz = ptr[n_rows];
+  if (ptr[0] != 0 || nnz < 0) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: row pointers do not span the table");
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (ptr[r + 1] < ptr[r]) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: row pointers decrease");
+  if ((nnz && (!col || !w)) || (n_cols && !x)) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: col, w and x");
+  for (int64_t k = 0; k < nnz; ++k)
+    if (col[k] < 0 || col[k] >= n_cols) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_transfer: column out of range");
+  hipStream_t s = ctx->stream;
+  const size_t dim = size_t(ctx->dim);
+  MgCsr M;
+  M.n_rows = n_rows;
+  M.ptr.upload(ptr, size_t(n_rows) + 1, s);
+  M.col.upload(col, size_t(nnz), s);
+  M.w.upload(w, size_t(nnz), s);
+  if (kind == 0) {
+    DBuf<double> dx;
+    dx.upload(x, size_t(n_cols), s);
+    GuardedOut<double> dy;
+    dy.open(nullptr, size_t(n_rows), false, s);
+    mg_csr_apply(ctx, M, dx.p, dy.d.p);
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+    dy.close(y, s);
+  } else {
+    DBuf<uint8_t> fi, fo, mask;
+    if (flag_in) fi.upload(flag_in, size_t(n_cols) * dim, s);
+    if (flag_out) fo.upload(flag_out, size_t(n_rows) * dim, s);
+    DBuf<float> dx;
+    upload_as(dx, x, size_t(n_cols) * dim, s);
+    GuardedOut<float> dy;
+    dy.open(nullptr, size_t(n_rows) * dim, false, s);
+    mg_csr_mask(ctx, M, fi.p, fo.p, mask);
+    mg_csr_apply_nodes_f32(ctx, M, dx.p, mask, dy.d.p);
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+    dy.close(y, s);
+  }
+  IFEM_HIP_CHECK(hipGetLastError());
+  IFEM_API_END
+}
+
+int ifem_test_mg_vec_kernel(ifem_ctx *ctx, int op, int64_t n, int64_t m, const double *coef, const int32_t *idx, double *in0, double *in1,
+                            double *out0, double *out1, double *out2) {
+  IFEM_API_BEGIN
+  if (op < 0 || op >= IFEM_TMG_COUNT || n < 0 || !out0) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: op, n >= 0 and out0");
+  if (ctx->halo.nranks > 1) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: single-rank contexts");
+  const bool block = op == IFEM_TMG_VC_ENTRY || op == IFEM_TMG_VC_ENTRY_F32 || op == IFEM_TMG_CHEB_INIT_BLOCK_F32;
+  const bool need_in0 = op != IFEM_TMG_VEC_RECIP && op != IFEM_TMG_VEC_ROUGH;
+  const bool need_in1 = op == IFEM_TMG_CHEB_INIT || op == IFEM_TMG_CHEB_STEP || op == IFEM_TMG_VC_EXIT || op == IFEM_TMG_VC_EXIT_F32;
+  const bool need_coef = op == IFEM_TMG_CHEB_INIT || op == IFEM_TMG_CHEB_STEP || op == IFEM_TMG_AXPY_F32V || block;
+  const bool need_out1 = op == IFEM_TMG_CHEB_STEP || op == IFEM_TMG_VC_ENTRY || op == IFEM_TMG_VC_ENTRY_F32;
+  if ((need_in0 && !in0) || (need_in1 && !in1) || (need_coef && !coef) || (need_out1 && !out1) || (op == IFEM_TMG_CHEB_STEP && !out2))
+    throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: a null array this op uses");
+  const size_t dim = size_t(ctx->dim), N = size_t(n);
+  if (block && (!ctx->assembled || n != int64_t(dim) * ctx->nUo || ctx->bjac.n != size_t(ctx->nUo) * dim * dim))
+    throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: the node-block ops run after an assembly, n = dim * n_unodes");
+  if (op == IFEM_TMG_INJECT_NODES) {
+    if (m < 0 || (n && !idx)) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: the injection needs m >= 0 fine nodes and idx");
+    for (int64_t i = 0; i < n; ++i)
+      if (idx[i] < -1 || idx[i] >= m) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_vec_kernel: injection index out of range");
+  }
+  hipStream_t s = ctx->stream;
+  DBuf<double> a0, a1;
+  DBuf<float> f0, f1;
+  DBuf<int32_t> di;
+  GuardedOut<double> o0, o1, o2;
+  GuardedOut<float> g0, g1;
+  switch (op) {
+  case IFEM_TMG_CHEB_INIT:
+    a0.upload(in0, N, s); a1.upload(in1, N, s);
+    o0.open(nullptr, N, false, s);
+    cheb_init(ctx, n, coef[0], a0.p, a1.p, o0.d.p);
+    break;
+  case IFEM_TMG_CHEB_STEP:
+    a0.upload(in0, N, s); a1.upload(in1, N, s);
+    o0.open(out0, N, true, s); o1.open(out1, N, true, s); o2.open(out2, N, true, s);
+    cheb_step(ctx, n, coef[0], coef[1], a0.p, a1.p, o0.d.p, o1.d.p, o2.d.p);
+    break;
+  case IFEM_TMG_VEC_RECIP:
+    o0.open(out0, N, true, s);
+    vec_recip(ctx, n, o0.d.p);
+    break;
+  case IFEM_TMG_VEC_ROUGH:
+    o0.open(nullptr, N, false, s);
+    vec_rough(ctx, n, m, o0.d.p);
+    break;
+  case IFEM_TMG_CVT_D2F:
+    a0.upload(in0, N, s);
+    g0.open(nullptr, N, false, s);
+    v_cvt_d2f(ctx, n, a0.p, g0.d.p);
+    break;
+  case IFEM_TMG_CVT_F2D:
+    upload_as(f0, in0, N, s);
+    o0.open(nullptr, N, false, s);
+    v_cvt_f2d(ctx, n, f0.p, o0.d.p);
+    break;
+  case IFEM_TMG_AXPY_F32V:
+    upload_as(f0, in0, N, s);
+    g0.open(out0, N, true, s);
+    v_axpy_f32v(ctx, n, float(coef[0]), f0.p, g0.d.p);
+    break;
+  case IFEM_TMG_VC_EXIT:
+    upload_as(f0, in0, N, s); upload_as(f1, in1, N, s);
+    o0.open(nullptr, N, false, s);
+    vc_exit(ctx, n, f0.p, f1.p, o0.d.p);
+    break;
+  case IFEM_TMG_VC_EXIT_F32:
+    upload_as(f0, in0, N, s); upload_as(f1, in1, N, s);
+    g0.open(nullptr, N, false, s);
+    vc_exit_f32(ctx, n, f0.p, f1.p, g0.d.p);
+    break;
+  case IFEM_TMG_INJECT_NODES:
+    a0.upload(in0, size_t(m) * dim, s);
+    di.upload(idx, N, s);
+    o0.open(nullptr, N * dim, false, s);
+    mg_inject_nodes(ctx, n, di.p, a0.p, o0.d.p);
+    break;
+  case IFEM_TMG_VC_ENTRY:
+    a0.upload(in0, N, s);
+    g0.open(nullptr, N, false, s); g1.open(nullptr, N, false, s);
+    vc_entry(ctx, coef[0], a0.p, g0.d.p, g1.d.p);
+    break;
+  case IFEM_TMG_VC_ENTRY_F32:
+    upload_as(f0, in0, N, s);
+    g0.open(nullptr, N, false, s); g1.open(nullptr, N, false, s);
+    vc_entry_f32(ctx, coef[0], f0.p, g0.d.p, g1.d.p);
+    break;
+  default: // IFEM_TMG_CHEB_INIT_BLOCK_F32
+    upload_as(f0, in0, N, s);
+    g0.open(nullptr, N, false, s);
+    cheb_init_block_f32(ctx, coef[0], f0.p, g0.d.p);
+    break;
+  }
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  IFEM_HIP_CHECK(hipGetLastError());
+  if (o0.d.p) o0.close(out0, s);
+  if (g0.d.p) g0.close(out0, s);
+  if (o1.d.p) o1.close(out1, s);
+  if (g1.d.p) g1.close(out1, s);
+  if (o2.d.p) o2.close(out2, s);
+  if (op == IFEM_TMG_CHEB_STEP && n) { // the two read-only inputs as the device holds them after the call
+    IFEM_HIP_CHECK(hipMemcpyAsync(in0, a0.p, N * sizeof(double), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipMemcpyAsync(in1, a1.p, N * sizeof(double), hipMemcpyDeviceToHost, s));
+    IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  }
   IFEM_API_END
 }
 

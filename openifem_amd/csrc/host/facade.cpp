@@ -48,7 +48,8 @@ int guard(F f) {
 // the nested transfers of the cylinder meshes (multigrid.hpp::nested_prolongation / nested_injection) between refinement levels
 // `level` and level - 1, checked on the host -- out[0]: max |row sum - 1| of P_u and P_p (partition of unity), out[1]: number of
 // coarse velocity nodes c whose fine twin's row of P_u is not the unit vector e_c, out[2]: max error of a linear function at the
-// fine velocity nodes that sit where the parent's d-linear map puts them (every patch but the curved ring), out[3]: their share
+// fine velocity nodes that sit where the parent's d-linear map puts them (every patch but the curved ring), out[3]: their share,
+// out[4]: number of weights of P_u that single precision cannot hold
 template <int dim>
 static void nested_check(int level, int kv, double *out) {
   Triangulation<dim> tf, tc;
@@ -97,7 +98,10 @@ static void nested_check(int level, int kv, double *out) {
     ++n_straight;
     err = std::max(err, std::fabs(v - f(df.unode_coords[(size_t)i])));
   }
-  out[0] = rs; out[1] = double(bad); out[2] = err; out[3] = double(n_straight) / double(df.n_unodes);
+  // the velocity weights ifem_mg_attach would reject: the node transfers of the A_uu V-cycle hold them in single precision
+  int64_t inexact = 0;
+  for (const double w : Pu.w) inexact += double(float(w)) != w ? 1 : 0;
+  out[0] = rs; out[1] = double(bad); out[2] = err; out[3] = double(n_straight) / double(df.n_unodes); out[4] = double(inexact);
 }
 
 extern "C" {

@@ -248,16 +248,14 @@ bool hanging_offset(ifem_ctx *ctx, int use_nonzero);
 void hanging_condense_rhs(ifem_ctx *ctx, int use_nonzero); // solver.hip: b = C^T (b^ - A^ c0), hanging rows d c0
 
 // mg.hip: transfers and smoother updates of the multigrid inside the preconditioner
-void mg_csr_apply(ifem_ctx *ctx, const MgCsr &M, const double *x, double *y, bool add);
+void mg_csr_apply(ifem_ctx *ctx, const MgCsr &M, const double *x, double *y);
 void cheb_init(ifem_ctx *ctx, int64_t n, double c0, const double *dinv, const double *r, double *d);
 void cheb_step(ifem_ctx *ctx, int64_t n, double a, double b, const double *dinv, const double *t, double *x, double *r, double *d);
 void vec_recip(ifem_ctx *ctx, int64_t n, double *d);
 void vec_rough(ifem_ctx *ctx, int64_t n, int64_t offset, double *x);
 void uu_block_diag_mf(ifem_ctx *ctx); // ctx->bjac := inverse node blocks of the matrix-free A_uu (coarse multigrid levels)
 void mg_csr_mask(ifem_ctx *ctx, const MgCsr &M, const uint8_t *flag_in, const uint8_t *flag_out, DBuf<uint8_t> &mask);
-void mg_csr_apply_nodes(ifem_ctx *ctx, const MgCsr &M, const double *x, const DBuf<uint8_t> &mask, double *y);
 void mg_inject_nodes(ifem_ctx *ctx, int64_t n_nodes, const int32_t *inj, const double *fine, double *coarse);
-void cheb_init_block(ifem_ctx *ctx, double c0, const double *r, double *d);
 void cheb_init_block_f32(ifem_ctx *ctx, double c0, const float *r, float *d);
 void mg_csr_apply_nodes_f32(ifem_ctx *ctx, const MgCsr &M, const float *x, const DBuf<uint8_t> &mask, float *y);
 void v_cvt_d2f(ifem_ctx *ctx, int64_t n, const double *x, float *y);

@@ -13,23 +13,21 @@ static inline unsigned mgrid(int64_t n) {
   return unsigned(g < 1 ? 1 : (g > 16384 ? 16384 : g));
 }
 
-// y_row (+)= sum_k w_k x[col_k]: one thread per row (<= 8 entries for a prolongation row, <= 27 for a restriction row)
-template <bool ADD>
+// y_row = sum_k w_k x[col_k]: one thread per row (<= 8 entries for a prolongation row, <= 27 for a restriction row)
 __global__ __launch_bounds__(256) void k_mg_csr(int64_t n_rows, const int64_t *__restrict__ ptr, const int32_t *__restrict__ col,
                                                 const double *__restrict__ w, const double *__restrict__ x,
                                                 double *__restrict__ y) {
   for (int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < n_rows; r += int64_t(gridDim.x) * blockDim.x) {
     double s = 0;
     for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k) s += w[k] * x[col[k]];
-    if (ADD) y[r] += s; else y[r] = s;
+    y[r] = s;
   }
 }
 
-void mg_csr_apply(ifem_ctx *ctx, const MgCsr &M, const double *x, double *y, bool add) {
+void mg_csr_apply(ifem_ctx *ctx, const MgCsr &M, const double *x, double *y) {
   if (!M.n_rows) return;
   KScope ks(ctx, IFEM_KC_MG_TRANSFER, double(M.col.n) * 20.0 + double(M.n_rows) * 16.0);
-  if (add) hipLaunchKernelGGL((k_mg_csr<true>), dim3(mgrid(M.n_rows)), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, M.col.p, M.w.p, x, y);
-  else hipLaunchKernelGGL((k_mg_csr<false>), dim3(mgrid(M.n_rows)), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, M.col.p, M.w.p, x, y);
+  hipLaunchKernelGGL(k_mg_csr, dim3(mgrid(M.n_rows)), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, M.col.p, M.w.p, x, y);
 }
 
 // Chebyshev iteration on D^-1 A (Adams, Brezina, Hu, Tuminaro 2003): d_0 = (1/theta) D^-1 r
@@ -366,9 +364,9 @@ void mg_csr_mask(ifem_ctx *ctx, const MgCsr &M, const uint8_t *flag_in, const ui
   else hipLaunchKernelGGL((k_mg_mask<2>), dim3(mgrid(M.n_rows)), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, M.col.p, M.w.p, flag_in, flag_out, pk);
 }
 
-template <int DIM, int G, typename V>
+template <int DIM, int G>
 __global__ __launch_bounds__(256) void k_mg_csr_nodes(int64_t n_rows, const int64_t *__restrict__ ptr, const uint2 *__restrict__ pk,
-                                                      const V *__restrict__ x, V *__restrict__ y) {
+                                                      const float *__restrict__ x, float *__restrict__ y) {
   const int lig = threadIdx.x % G;
   const int64_t r = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;
   const bool live = r < n_rows;
@@ -397,34 +395,28 @@ __global__ __launch_bounds__(256) void k_mg_csr_nodes(int64_t n_rows, const int6
     double v = s[0];
 #pragma unroll
     for (int c = 1; c < DIM; ++c) v = lig == c ? s[c] : v;
-    y[r * DIM + lig] = V(v);
+    y[r * DIM + lig] = float(v);
   }
 }
 
-template <int DIM, typename V>
-static void launch_csr_nodes(ifem_ctx *ctx, const MgCsr &M, const V *x, const uint8_t *mask, V *y) {
+template <int DIM>
+static void launch_csr_nodes(ifem_ctx *ctx, const MgCsr &M, const float *x, const uint8_t *mask, float *y) {
   const double mean = double(M.col.n) / double(M.n_rows);
   const int g = mean <= 6 ? 4 : (mean <= 12 ? 8 : (mean <= 24 ? 16 : 32));
   const unsigned blocks = unsigned((M.n_rows * g + 255) / 256);
   // one packed 8-byte entry per weight; per row its pointer and DIM outputs; the gathered input is re-used from cache
-  KScope ks(ctx, IFEM_KC_MG_TRANSFER, double(M.col.n) * 8.0 + double(M.n_rows) * (8.0 + DIM * sizeof(V)));
+  KScope ks(ctx, IFEM_KC_MG_TRANSFER, double(M.col.n) * 8.0 + double(M.n_rows) * (8.0 + DIM * sizeof(float)));
   const uint2 *pk = reinterpret_cast<const uint2 *>(mask);
-#define IFEM_CSRN(G) hipLaunchKernelGGL((k_mg_csr_nodes<DIM, G, V>), dim3(blocks), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, pk, x, y)
+#define IFEM_CSRN(G) hipLaunchKernelGGL((k_mg_csr_nodes<DIM, G>), dim3(blocks), dim3(256), 0, ctx->stream, M.n_rows, M.ptr.p, pk, x, y)
   if (g == 4) IFEM_CSRN(4); else if (g == 8) IFEM_CSRN(8); else if (g == 16) IFEM_CSRN(16); else IFEM_CSRN(32);
 #undef IFEM_CSRN
 }
 
-void mg_csr_apply_nodes(ifem_ctx *ctx, const MgCsr &M, const double *x, const DBuf<uint8_t> &mask, double *y) {
-  if (!M.n_rows) return;
-  if (mask.n != M.col.n * 8) throw Error(IFEM_E_BADPARAM, "multigrid transfer without its packed entries (mg_csr_mask)");
-  if (ctx->dim == 3) launch_csr_nodes<3, double>(ctx, M, x, mask.p, y);
-  else launch_csr_nodes<2, double>(ctx, M, x, mask.p, y);
-}
 void mg_csr_apply_nodes_f32(ifem_ctx *ctx, const MgCsr &M, const float *x, const DBuf<uint8_t> &mask, float *y) {
   if (!M.n_rows) return;
   if (mask.n != M.col.n * 8) throw Error(IFEM_E_BADPARAM, "multigrid transfer without its packed entries (mg_csr_mask)");
-  if (ctx->dim == 3) launch_csr_nodes<3, float>(ctx, M, x, mask.p, y);
-  else launch_csr_nodes<2, float>(ctx, M, x, mask.p, y);
+  if (ctx->dim == 3) launch_csr_nodes<3>(ctx, M, x, mask.p, y);
+  else launch_csr_nodes<2>(ctx, M, x, mask.p, y);
 }
 
 __global__ void k_mg_inject(int64_t n_nodes, int dim, const int32_t *__restrict__ inj, const double *__restrict__ fine,
@@ -441,9 +433,9 @@ void mg_inject_nodes(ifem_ctx *ctx, int64_t n_nodes, const int32_t *inj, const d
 }
 
 // d = c0 B r per node (B = inverse diagonal block)
-template <int DIM, typename V>
-__global__ void k_cheb_init_block(int64_t n_nodes, double c0, const float *__restrict__ bj, const V *__restrict__ r,
-                                  V *__restrict__ d) {
+template <int DIM>
+__global__ void k_cheb_init_block(int64_t n_nodes, double c0, const float *__restrict__ bj, const float *__restrict__ r,
+                                  float *__restrict__ d) {
   const int64_t nd = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (nd >= n_nodes) return;
   double rv[DIM];
@@ -454,21 +446,18 @@ __global__ void k_cheb_init_block(int64_t n_nodes, double c0, const float *__res
     double t = 0;
 #pragma unroll
     for (int j = 0; j < DIM; ++j) t += double(bj[nd * DIM * DIM + i * DIM + j]) * rv[j];
-    d[nd * DIM + i] = V(c0 * t);
+    d[nd * DIM + i] = float(c0 * t);
   }
 }
-template <typename V>
-static void cheb_init_block_t(ifem_ctx *ctx, double c0, const V *r, V *d) {
+void cheb_init_block_f32(ifem_ctx *ctx, double c0, const float *r, float *d) {
   const int64_t n = ctx->nUo;
   if (!n) return;
   const dim3 g(unsigned((n + 255) / 256)), b(256);
   const float *bjf = bjac_f32_ptr(ctx);
-  KScope ks(ctx, IFEM_KC_VECTOR, double(n) * ctx->dim * (4.0 * ctx->dim + 2.0 * sizeof(V)));
-  if (ctx->dim == 3) hipLaunchKernelGGL((k_cheb_init_block<3, V>), g, b, 0, ctx->stream, n, c0, bjf, r, d);
-  else hipLaunchKernelGGL((k_cheb_init_block<2, V>), g, b, 0, ctx->stream, n, c0, bjf, r, d);
+  KScope ks(ctx, IFEM_KC_VECTOR, double(n) * ctx->dim * (4.0 * ctx->dim + 2.0 * sizeof(float)));
+  if (ctx->dim == 3) hipLaunchKernelGGL((k_cheb_init_block<3>), g, b, 0, ctx->stream, n, c0, bjf, r, d);
+  else hipLaunchKernelGGL((k_cheb_init_block<2>), g, b, 0, ctx->stream, n, c0, bjf, r, d);
 }
-void cheb_init_block(ifem_ctx *ctx, double c0, const double *r, double *d) { cheb_init_block_t<double>(ctx, c0, r, d); }
-void cheb_init_block_f32(ifem_ctx *ctx, double c0, const float *r, float *d) { cheb_init_block_t<float>(ctx, c0, r, d); }
 
 // conversions between the double vectors of the Krylov solvers and the single-precision level vectors, y (+)= a x
 __global__ void k_cvt_d2f(int64_t n, const double *__restrict__ x, float *__restrict__ y) {

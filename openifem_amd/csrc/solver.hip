@@ -440,14 +440,14 @@ static void mg_sm_vcycle(MgSm &M, size_t l) {
   // restriction r_c = P^T r: gather per LOCAL coarse node from the owned fine nodes, ghost rows travel to their owners
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
-  mg_csr_apply(c, c->mg_Rp, r, cc->mg_vec[0].p, false);
+  mg_csr_apply(c, c->mg_Rp, r, cc->mg_vec[0].p);
   if (c->mg_replica) allreduce_sum_vec(c, cc->mg_vec[0].p, cc->nPo, cc->mg_vec[4].p); // replicated coarse level: sum of the ranks' partial rows
   else halo_reverse_add_p(cc, cc->mg_vec[0].p);
   mg_sm_vcycle(M, l + 1);
   // prolongation e = P x_c from the ghost-extended coarse correction, then x += e, r -= S e
   halo_exchange_p(cc, cc->mg_vec[1].p);
   double *e = c->mg_vec[4].p, *t = c->mg_vec[3].p;
-  mg_csr_apply(c, c->mg_Pp, cc->mg_vec[1].p, e, false);
+  mg_csr_apply(c, c->mg_Pp, cc->mg_vec[1].p, e);
   sm_apply(S, e, t, M.lowp);
   v_axpy(c, S.npo, 1.0, e, x);
   v_axpy(c, S.npo, -1.0, t, r);

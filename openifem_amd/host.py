@@ -1,5 +1,6 @@
 """ctypes binding of the C++ host mirror (csrc/host/facade.cpp): Fluid::MPI::InsIM driven like a reference test."""
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -453,8 +454,18 @@ def nested_transfer_check(dim, level, kv):
     """host/multigrid.cpp::nested_prolongation / nested_injection between the cylinder meshes of refinement `level` and level - 1:
     (max |row sum - 1|, coarse nodes whose fine twin does not interpolate from them alone, error of a linear function on the
     straight patches, share of the fine nodes on straight patches)"""
+    return _nested_transfer_check(dim, level, kv)[:4]
+
+
+def nested_transfer_inexact_weights(dim, level, kv):
+    """number of weights of that velocity prolongation that single precision cannot hold (ifem_mg_attach rejects such a table)"""
+    return int(_nested_transfer_check(dim, level, kv)[4])
+
+
+@functools.lru_cache(maxsize=None)
+def _nested_transfer_check(dim, level, kv):
     L = _lib()
-    out = np.zeros(4)
+    out = np.zeros(5)
     rc = L.ifemx_nested_transfer_check(dim, level, kv, out.ctypes.data_as(C.c_void_p))
     if rc < 0:
         raise HostError(rc, L.ifemx_last_error().decode())

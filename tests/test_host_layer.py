@@ -516,3 +516,32 @@ def test_nested_transfers_of_the_cylinder_levels(dim, level, kv):
     rowsum, bad_twins, lin_err, straight = host.nested_transfer_check(dim, level, kv)
     assert rowsum < 1e-13 and bad_twins == 0 and lin_err < 1e-12
     assert 0.9 < straight < 1.0
+
+
+def _inexact_in_float(w):
+    w = np.asarray(w, float)
+    return int((w.astype(np.float32).astype(np.float64) != w).sum())
+
+
+@pytest.mark.parametrize("dim,reps_f,reps_c", [(3, (4, 4, 4), (2, 2, 2)), (3, (8, 6, 4), (4, 3, 4)), (2, (6, 4), (3, 2)), (2, (8, 8), (8, 4))])
+def test_box_transfer_weights_are_exact_in_single_precision(dim, reps_f, reps_c):
+    """ifem_mg_attach rejects a velocity transfer weight that single precision cannot hold (the node transfers of the A_uu V-cycle store the
+    weights as float): the generators of the box levels, the C++ one and its numpy restatement, give dyadic weights for Q1 and Q2"""
+    from openifem_amd import capi, host
+    for deg in (1, 2):
+        nf, nc = int(np.prod([deg * r + 1 for r in reps_f])), int(np.prod([deg * r + 1 for r in reps_c]))
+        for gen in (capi.box_prolongation, host.box_prolongation):
+            P = gen(reps_f, reps_c, deg, np.arange(nf), np.arange(nc)).tocsr()
+            assert P.nnz >= nf and _inexact_in_float(P.data) == 0
+            assert set(np.abs(P.data).tolist()) <= {a * b * c for a in (1.0, 0.75, 0.5, 0.375, 0.125) for b in (1.0, 0.75, 0.5, 0.375, 0.125)
+                                                    for c in (1.0, 0.75, 0.5, 0.375, 0.125)}
+        for n_c in (1, 3):
+            _, w = capi.lattice_prolongation_1d(2 * n_c, n_c, deg)
+            assert _inexact_in_float(w) == 0
+
+
+@pytest.mark.parametrize("dim,level,kv", [(2, 1, 2), (2, 2, 2), (2, 3, 1), (3, 1, 2)])
+def test_nested_transfer_weights_are_exact_in_single_precision(dim, level, kv):
+    """... and so does the generator of the refinement-history levels (host/multigrid.cpp::nested_prolongation, the cylinder meshes)"""
+    from openifem_amd import host
+    assert host.nested_transfer_inexact_weights(dim, level, kv) == 0
