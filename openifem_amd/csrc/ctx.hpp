@@ -410,23 +410,28 @@ struct MpDirect {
   DBuf<double> w;                // the lattice-ordered work vector of the sweeps
 };
 
-// y = S_m x from stencil tables over the pressure lattice (sm_stencil.hip): on a uniform box every row with the same position signature (per
-// axis the distance to either face, capped at 2) has the same 5^dim stencil.  The tables are re-made and probed against the assembled S_m whenever
-// S_m is re-formed (`version`), at set-up time; rows that differ from their class (`rows`) keep the CSR product.
-struct SmStencil {
-  bool off = false;     // test aid (ifem_test_sm_apply): the context keeps the CSR product
-  int64_t version = -1; // ifem_ctx::sm_version the tables (or the decision against them) belong to
-  bool ready = false;   // ... and they passed the probe: sm_apply takes the stencil path
-  bool failed = false;  // a probe failed: the context keeps the CSR product from then on
-  bool said = false;    // the verbose line of a level that keeps the CSR product has been printed
+// The class tables of one lattice stencil product (lattice_stencil.hpp builds them; S_m: sm_stencil.hip, B and B^T: bb_stencil.hip): on a uniform
+// box every row with the same position signature holds the same numbers.  Rows that differ from their class (`rows`) keep the CSR product.
+struct StencilClasses {
+  bool ready = false;  // the tables belong to the owner's `version` and passed the probe: the product takes the stencil path
+  bool failed = false; // a probe failed: the context keeps the CSR product from then on
+  bool said = false;   // the verbose line of an operator that keeps the CSR product has been printed
   int classes = 0, ncls[3] = {1, 1, 1};
   int64_t n_irregular = 0;
-  DBuf<uint8_t> axcls;   // [n[0] + n[1] + n[2]] per-axis class of every lattice coordinate
+  DBuf<uint8_t> axcls;   // [n[0] + n[1] + n[2]] per-axis class of every coordinate of the row lattice
   DBuf<int32_t> first;   // [ncls[0] + ncls[1] + ncls[2]] first coordinate of every axis class
-  DBuf<double> table;    // [classes][5^dim] stencil of every class in offset order, [classes] max |entry| behind it
-  DBuf<uint16_t> cls;    // [lattice] class of the row at that point, 0xFFFF: irregular
-  DBuf<int32_t> rows;    // [n_irregular] the irregular rows (pressure nodes); capacity lattice / 8 + 1
+  DBuf<double> table;    // [classes][K] dense row of every class (component-major, then offset order), [classes] max |entry| behind it
+  DBuf<uint16_t> cls;    // [row lattice] class of the row at that point, 0xFFFF: irregular
+  DBuf<int32_t> rows;    // [n_irregular] the irregular rows (nodes); capacity lattice / 8 + 1
   DBuf<int32_t> counter; // [1] device count of the irregular rows
+};
+
+// y = S_m x from stencil tables over the pressure lattice (sm_stencil.hip): the signature of a row is, per axis, the distance to either face,
+// capped at 2, and its stencil has 5^dim entries.  The tables are re-made and probed against the assembled S_m whenever S_m is re-formed
+// (`version`), at set-up time.
+struct SmStencil : StencilClasses {
+  bool off = false;     // test aid (ifem_test_sm_apply): the context keeps the CSR product
+  int64_t version = -1; // ifem_ctx::sm_version the tables (or the decision against them) belong to
 };
 
 // x = S_m^-1 b by fast diagonalisation on a uniform Q2/Q1 box level whose constrained velocity dofs are whole faces (sm_direct.hip;
@@ -466,19 +471,7 @@ struct ULattice {
 // Each block has its own tables, read off its own assembled values (with ifem_tuning::geo_cache = 2 both are masked copies: neither is assumed
 // to be the transpose of the other), re-made and probed whenever an assembly wrote the blocks (ifem_ctx::bb_version), at solve set-up.
 struct BbStencil {
-  struct Block {
-    bool ready = false;  // the tables belong to `version` and passed the probe
-    bool failed = false; // a probe failed: this block keeps the CSR product for the life of the context
-    bool said = false;   // the verbose line of a block that keeps the CSR product has been printed
-    int classes = 0, ncls[3] = {1, 1, 1};
-    int64_t n_irregular = 0;
-    DBuf<uint8_t> axcls;   // per-axis class of every coordinate of the row lattice
-    DBuf<int32_t> first;   // first coordinate of every axis class
-    DBuf<double> table;    // [classes][K] dense row of every class (component-major, then offset order), [classes] max |entry| behind it
-    DBuf<uint16_t> cls;    // [row lattice] class of the row at that point, 0xFFFF: irregular
-    DBuf<int32_t> rows;    // the irregular rows (nodes); capacity lattice / 8 + 1
-    DBuf<int32_t> counter; // [1] device count of the irregular rows
-  } b, bt;
+  StencilClasses b, bt;
   bool off = false;     // test aid (ifem_test_b_apply): the context keeps the CSR products
   bool scns = false;    // B / B^T hold the stabilised blocks of an SCnsIM assembly: ineligible until an INS assembly writes them again
   int64_t version = -1; // ifem_ctx::bb_version the tables (or the decision against them) belong to

@@ -216,6 +216,9 @@ void cg1_init(ifem_ctx *ctx, int64_t n, const double *b, const double *diag, dou
 void cg1_dots(ifem_ctx *ctx, int64_t n, const double *r, const double *u, const double *w, bool first);
 void cg1_update(ifem_ctx *ctx, int64_t n, const double *diag, double *u, const double *w, double *p, double *s, double *x, double *r);
 void v_minmax(ifem_ctx *ctx, int64_t n, const double *x, double *mn, double *mx);
+// the comparison of a set-up probe on the device: got -= ref, *ref_max = max |ref|, *err = max |got - ref|; false: one of them is not finite
+// (an entry nobody produced, a NaN in either vector).  Synchronises; three scalars come back.
+bool v_probe_diff(ifem_ctx *ctx, int64_t n, const double *ref, double *got, double *ref_max, double *err);
 // test aid (ifem_test_cg_device): solver.hip::cg_device on A = diag(a), host arrays in and out, exactly `iters` iterations
 void test_cg_device(ifem_ctx *ctx, int64_t n, const double *a, const double *jac, const double *b, int iters, double *x);
 // x[dof] = value for constrained dofs (AffineConstraints::distribute, Dirichlet lines) of the fluid set `which`; the launch itself on any

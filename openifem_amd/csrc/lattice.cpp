@@ -1,4 +1,4 @@
-// lattice.cpp -- host side of the lattice readers (mp_direct.hip, sm_stencil.hip): plain C++, no device call.
+// lattice.cpp -- host side of the lattice readers (mp_direct.hip; the axis classes of lattice_stencil.hpp for sm_stencil.hip and bb_stencil.hip): plain C++, no device call.
 #include <algorithm>
 #include <cmath>
 #include "lattice.hpp"

@@ -1429,6 +1429,18 @@ void v_minmax(ifem_ctx *ctx, int64_t n, const double *x, double *mn, double *mx)
   *mn = ctx->h_scal[0]; *mx = ctx->h_scal[1];
 }
 
+bool v_probe_diff(ifem_ctx *ctx, int64_t n, const double *ref, double *got, double *ref_max, double *err) {
+  double lo = 0, hi = 0;
+  v_minmax(ctx, n, ref, &lo, &hi);
+  *ref_max = std::max(std::fabs(lo), std::fabs(hi));
+  v_axpy(ctx, n, -1.0, ref, got); // got -= ref
+  v_minmax(ctx, n, got, &lo, &hi);
+  *err = std::max(std::fabs(lo), std::fabs(hi));
+  const double sq = v_dot(ctx, n, got, got); // (a NaN passes a minimum / maximum unseen, not a sum)
+  IFEM_HIP_CHECK(hipGetLastError());
+  return std::isfinite(sq) && std::isfinite(*err) && std::isfinite(*ref_max) && *err < 1e299;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // node-block Jacobi: inverse of the dim x dim diagonal blocks of A_uu
 template <int DIM>

@@ -245,15 +245,8 @@ static bool smd_probe(ifem_ctx *ctx, double *err_out) {
   sm_direct_apply(ctx, de.p, dx.p);
   if (sm_stencil_ready(ctx)) sm_stencil_apply(ctx, dx.p, dy.p);
   else spmv_sm(ctx, dx.p, dy.p, /*use_f32=*/false);
-  double lo = 0, hi = 0;
-  v_minmax(ctx, n, de.p, &lo, &hi);
-  const double emax = std::max(std::fabs(lo), std::fabs(hi));
-  v_axpy(ctx, n, -1.0, de.p, dy.p); // dy = S_m x - e
-  v_minmax(ctx, n, dy.p, &lo, &hi);
-  const double err = std::max(std::fabs(lo), std::fabs(hi));
-  const double sq = v_dot(ctx, n, dy.p, dy.p); // (a NaN passes a minimum / maximum unseen, not a sum)
-  IFEM_HIP_CHECK(hipGetLastError());
-  const bool finite = std::isfinite(sq) && std::isfinite(err) && std::isfinite(emax) && err < 1e299 && emax > 0;
+  double emax = 0, err = 0;
+  const bool finite = v_probe_diff(ctx, n, de.p, dy.p, &emax, &err) && emax > 0; // dy = S_m x - e
   if (err_out) *err_out = finite ? err / emax : INFINITY;
   return finite && err <= 1e-7 * emax;
 }

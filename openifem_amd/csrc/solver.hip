@@ -273,7 +273,7 @@ static void sm_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   // S_m in operator form launches the B^T and B products: which ones, and the tables of the stencil ones (bb_stencil.hip)
   const BbStencil &Q = lc->bb_stencil;
   for (int which = 0; which < 2; ++which) {
-    const BbStencil::Block &K = which ? Q.bt : Q.b;
+    const StencilClasses &K = which ? Q.bt : Q.b;
     key.push_back(uint64_t(bb_stencil_ready(lc, which))); key.push_back(uint64_t(K.n_irregular));
     key_ptr(key, K.table.p); key_ptr(key, K.cls.p); key_ptr(key, K.rows.p);
   }
@@ -1188,6 +1188,14 @@ void sm_solve_probe(ifem_ctx *ctx, const ifem_solver_opts *o, const double *b, d
   info[3] = direct ? int64_t(ctx->sm_direct.bytes()) : 0;
 }
 
+// what the two test aids below report of a lattice stencil product: `first` | classes | irregular rows | table bytes, zeros while it is off
+static void stencil_info(const StencilClasses &T, bool on, int64_t first, int64_t info[4]) {
+  info[0] = on ? first : 0;
+  info[1] = on ? T.classes : 0;
+  info[2] = on ? T.n_irregular : 0;
+  info[3] = on ? int64_t(T.table.n * sizeof(double)) : 0;
+}
+
 // ifem_test_sm_apply: y = S_m x on device vectors of owned pressure nodes.  path 0: the fp64 CSR product of the assembled matrix (one rank); 1: sm_apply
 // as the solves of the default options call it (several ranks: collective, the distributed explicit product or the two SpMVs); 2 / 3: switch the
 // stencil path of this context off / on again (x, y unused; 3 also makes the tables of the present S_m when that is formed already)
@@ -1204,11 +1212,7 @@ void sm_apply_probe(ifem_ctx *ctx, int path, const double *x, double *y, int64_t
     if (path == 0) spmv_sm(ctx, x, y, false);
     else sm_apply(S, x, y, approx_kind(S.o));
   }
-  const bool on = sm_stencil_ready(ctx);
-  info[0] = on ? 1 : 0;
-  info[1] = on ? T.classes : 0;
-  info[2] = on ? T.n_irregular : 0;
-  info[3] = on ? int64_t(T.table.n * sizeof(double)) : 0;
+  stencil_info(T, sm_stencil_ready(ctx), 1, info);
 }
 
 // ifem_test_b_apply: y = B x (which 0), y = B^T x (1) or y += B^T x (2) on device vectors, x ghost-extended, y owned.  path 0: the fp64 CSR
@@ -1231,12 +1235,7 @@ void b_apply_probe(ifem_ctx *ctx, int which, int path, const double *x, double *
     } else if (stencil) bb_stencil_apply_bt(ctx, x, y, which == 2);
     else spmv_bt_rows(ctx, x, y, ctx->Bt.n_rows, nullptr, which == 2);
   }
-  const bool on = bb_stencil_ready(ctx, blk);
-  const BbStencil::Block &K = blk ? T.bt : T.b;
-  info[0] = on ? T.builds : 0;
-  info[1] = on ? K.classes : 0;
-  info[2] = on ? K.n_irregular : 0;
-  info[3] = on ? int64_t(K.table.n * sizeof(double)) : 0;
+  stencil_info(blk ? T.bt : T.b, bb_stencil_ready(ctx, blk), T.builds, info);
 }
 
 // right-hand side of the condensed system after an assembly that treated the hanging dofs as ordinary ones:
