@@ -287,7 +287,8 @@ const char *ifem_last_error(void);
 /* sizeof of the structs above as this library was compiled, for a binding to check its mirror against:
  * 0 ifem_mesh_desc, 1 ifem_partition, 2 ifem_ins_params, 3 ifem_solver_opts, 4 ifem_solve_stats, 5 ifem_scns_params,
  * 6 ifem_timing, 7 ifem_tuning, 8 ifem_mg_transfer, 9 ifem_fsi_solid, 10 ifem_fsi_stats, 11 ifem_comm_stats, 12 ifem_kprof_entry,
- * 13 ifem_sa_params; -1 for anything else */
+ * 13 ifem_sa_params; -1 for anything else, with one exception: 64 answers for ifem_scnsex_stats -- the contiguous range ends at 13,
+ * the index behind it answers -1, which callers use to find the end of the list */
 int64_t ifem_abi_sizeof(int which);
 int ifem_device_count(void);
 void ifem_default_solver_opts(ifem_solver_opts *o);
@@ -523,6 +524,42 @@ int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double
 /* test hook: the assembled matrix as CSR over the nodes (two-call protocol of ifem_export_csr: rowptr [n_unodes_owned + 1]
  * first with col = val = NULL) */
 int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val);
+
+/* ---- Fluid::MPI::SCnsEX (source/mpi_scnsex.cpp): the explicit split solver of the slightly compressible equations, the reference's
+ * solver for acoustics (tests/acoustic_duct_wave_mpi_scnsex).  Velocity and pressure have the SAME degree and live on the same nodes
+ * (:12-14): the context is created with n_pnodes == n_unodes and cell_pnodes = the vertex nodes of cell_unodes (a Q1/Q1 box mesh as it
+ * is; Q2/Q2 with the pressure numbered like the velocity).  Per outer iteration two scalar SPD systems are solved: the velocity matrix
+ * is I_dim (x) A_v, A_v = mu K + rho / dt M + rho M_sigma (:258-267), the pressure matrix A_p = (M / dt + M_sigma) / atm (:271-277).
+ * Both are kept unconstrained, one value per block of the A_uu node pattern; the block CSR of A_uu is never allocated
+ * (ifem_uu_stored_bytes stays 0).  Constraints come through ifem_set_constraints(ctx, 1, ...) only: SCnsEX solves for absolute
+ * values and never uses the zero set (mpi_scnsex.h:77-80).  sigma_pml and body_force come from ifem_set_scns_fields.
+ * ONE deliberate deviation: CG is preconditioned by Jacobi where the reference uses BoomerAMG (:407-417) -- preconditioner only;
+ * zero start vector and the stopping rule 1e-6 ||rhs|| are the reference's.
+ * Scope: single-rank contexts without hanging-node lines whose velocity and pressure node tables agree; anything else is
+ * IFEM_E_BADPARAM with a message, from the entry point, before any launch.  No refinement, no attached turbulence model. */
+typedef struct {
+  uint32_t outer_iterations;    /* outer iterations of the step (ITR + 1 of the last console line, :492-498) */
+  uint32_t vel_iters, pre_iters; /* VEL_ITR / PRE_ITR of the last outer iteration */
+  uint32_t reserved_;           /* padding, always 0 */
+  double vel_res, pre_res;      /* VEL_RES / PRE_RES of the last outer iteration */
+  double abs_res, rel_res;      /* ABS_RES / REL_RES of the last outer iteration (rel_res is NaN for a state at rest, as in the reference) */
+} ifem_scnsex_stats;
+/* SCnsEX::assemble(true, .), the matrices (:248-279): integrates A_v, A_p and their diagonals.  Re-run only when viscosity, rho, dt
+ * or the sigma_pml field changed since the last call; the other entry points call it themselves. */
+int ifem_scnsex_setup(ifem_ctx *ctx, const ifem_scns_params *p);
+/* SCnsEX::assemble(., velocity), the right-hand side (:282-340, 344-376) at IFEM_VEC_EVAL / IFEM_VEC_PRESENT into the velocity
+ * (velocity != 0: [0, dim n)) or the pressure block ([dim n, (dim + 1) n)) of IFEM_VEC_RHS; the velocity side includes the Neumann
+ * faces and the lift rhs_c <- P_c (rhs_c - A_v g_c) of the constraint values, constrained rows are 0 */
+int ifem_scnsex_assemble_rhs(ifem_ctx *ctx, const ifem_scns_params *p, int velocity);
+/* SCnsEX::solve(velocity) (:389-427): CG from zero to 1e-6 ||rhs|| on the block of IFEM_VEC_RHS into the same block of
+ * IFEM_VEC_UPDATE (intermediate_solution), then nonzero_constraints.distribute */
+int ifem_scnsex_solve(ifem_ctx *ctx, int velocity, uint32_t *iters, double *res);
+/* the outer loop of SCnsEX::run_one_step (:448-503) from IFEM_VEC_PRESENT, which is replaced by the converged evaluation point;
+ * IFEM_E_NEWTON_MAXIT is the reference's "Too many iterations!" (:462-463) */
+int ifem_scnsex_step(ifem_ctx *ctx, const ifem_scns_params *p, double tolerance, int max_iterations, ifem_scnsex_stats *stats);
+/* test hook: the unconstrained matrices as CSR over the nodes, which = 0: A_v, 1: A_p (two-call protocol of ifem_export_csr: rowptr
+ * [n_unodes_owned + 1] first with col = val = NULL) */
+int ifem_scnsex_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val);
 
 /* ---- fluid-side inputs of MPI::FSI produced on the device (source/mpi_fsi.cpp) --------------------
  * What the FSI driver computes on the fluid mesh before every fluid step (mpi_fsi.cpp:1189-1208), from the solid as every

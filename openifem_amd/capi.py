@@ -75,6 +75,12 @@ class SaParams(C.Structure):
 SA_PRESENT, SA_EVAL, SA_UPDATE, SA_RHS = range(4)  # IFEM_SA_*
 
 
+class ScnsexStats(C.Structure):
+    """ifem_scnsex_stats"""
+    _fields_ = [("outer_iterations", C.c_uint32), ("vel_iters", C.c_uint32), ("pre_iters", C.c_uint32), ("reserved_", C.c_uint32),
+                ("vel_res", C.c_double), ("pre_res", C.c_double), ("abs_res", C.c_double), ("rel_res", C.c_double)]
+
+
 class SolverOpts(C.Structure):
     _fields_ = [("fgmres_restart", C.c_int32), ("fgmres_maxit", C.c_int32), ("fgmres_rel", C.c_double),
                 ("fgmres_abs", C.c_double), ("mp_rel", C.c_double), ("mp_abs", C.c_double),
@@ -152,7 +158,8 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply", "ifem_test_sm_solve",
            "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
-           "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr"]
+           "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr",
+           "ifem_scnsex_setup", "ifem_scnsex_assemble_rhs", "ifem_scnsex_solve", "ifem_scnsex_step", "ifem_scnsex_export_csr"]
 
 # ifem_solver_opts::sm_mg: plain CG | multigrid-preconditioned CG (the default) | the fast-diagonalisation solve where the level qualifies, SM_MG elsewhere
 SM_CG, SM_MG, SM_DIRECT = 0, 1, 2
@@ -285,6 +292,11 @@ def load():
     L.ifem_sa_newton_step.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_int, C.c_double, C.c_int, C.c_void_p]
     L.ifem_sa_update_eddy_viscosity.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_void_p]
     L.ifem_sa_export_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_scnsex_setup.argtypes = [C.c_void_p, C.POINTER(ScnsParams)]
+    L.ifem_scnsex_assemble_rhs.argtypes = [C.c_void_p, C.POINTER(ScnsParams), C.c_int]
+    L.ifem_scnsex_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    L.ifem_scnsex_step.argtypes = [C.c_void_p, C.POINTER(ScnsParams), C.c_double, C.c_int, C.POINTER(ScnsexStats)]
+    L.ifem_scnsex_export_csr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_abi_sizeof.argtypes = [C.c_int]
     L.ifem_abi_sizeof.restype = C.c_int64
     _lib = L
@@ -314,6 +326,7 @@ class CommStats(C.Structure):  # ifem_comm_stats
 
 ABI_STRUCTS = [MeshDesc, Partition, InsParams, SolverOpts, SolveStats, ScnsParams, Timing, Tuning, MgTransfer, FsiSolid, FsiStats,
                CommStats, KprofEntry, SaParams]
+ABI_SCNSEX_STATS = 64  # ifem_abi_sizeof(64) = sizeof(ifem_scnsex_stats): outside the contiguous list, whose end callers find by its first -1
 
 
 def export_rows(L, ctx, row0, nrows, which=0):
@@ -870,6 +883,36 @@ class Context:
         self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), None, None))
         col, val = np.zeros(rp[-1], np.int32), np.zeros(rp[-1])
         self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), _ptr(col), _ptr(val)))
+        return sp.csr_matrix((val, col, rp), shape=(n, self.n_u // self.dim))
+
+    # ---- Fluid::MPI::SCnsEX on scalar node matrices (mpi_scnsex.cpp); velocity and pressure on the same nodes
+    def scnsex_setup(self, params):
+        self._chk(self.L.ifem_scnsex_setup(self.h, C.byref(params)))
+
+    def scnsex_assemble_rhs(self, params, velocity):
+        """the velocity ([: dim n]) or pressure ([dim n :]) block of VEC_RHS at VEC_EVAL / VEC_PRESENT"""
+        self._chk(self.L.ifem_scnsex_assemble_rhs(self.h, C.byref(params), int(velocity)))
+
+    def scnsex_solve(self, velocity):
+        """(CG iterations, last residual); the solution is the same block of VEC_UPDATE"""
+        it, res = C.c_uint32(0), C.c_double(0)
+        self._chk(self.L.ifem_scnsex_solve(self.h, int(velocity), C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def scnsex_step(self, params, tol=1e-6, maxit=8):
+        """one time step from VEC_PRESENT; returns ifem_scnsex_stats"""
+        st = ScnsexStats()
+        self._chk(self.L.ifem_scnsex_step(self.h, C.byref(params), tol, maxit, C.byref(st)))
+        return st
+
+    def scnsex_export_csr(self, which):
+        """the unconstrained A_v (which = 0) or A_p (1) over the nodes"""
+        import scipy.sparse as sp
+        n = self.n_unodes_owned
+        rp = np.zeros(n + 1, np.int64)
+        self._chk(self.L.ifem_scnsex_export_csr(self.h, which, _ptr(rp), None, None))
+        col, val = np.zeros(rp[-1], np.int32), np.zeros(rp[-1])
+        self._chk(self.L.ifem_scnsex_export_csr(self.h, which, _ptr(rp), _ptr(col), _ptr(val)))
         return sp.csr_matrix((val, col, rp), shape=(n, self.n_u // self.dim))
 
     def rhs_norm(self):

@@ -164,6 +164,7 @@ int64_t ifem_abi_sizeof(int which) {
   case 11: return sizeof(ifem_comm_stats);
   case 12: return sizeof(ifem_kprof_entry);
   case 13: return sizeof(ifem_sa_params);
+  case 64: return sizeof(ifem_scnsex_stats);
   default: return -1;
   }
 }
@@ -704,6 +705,7 @@ int ifem_set_scns_fields(ifem_ctx *ctx, const double *sigma_pml, const double *b
   IFEM_API_BEGIN
   hipStream_t s = ctx->stream;
   const size_t ncq = (size_t)ctx->n_cells * ctx->nq;
+  if (sigma_pml || ctx->sigma_pml.n) ctx->ex.fields_version++; // the PML field is given or released: the matrices of the explicit solver hold it
   if (sigma_pml) ctx->sigma_pml.upload(sigma_pml, ncq, s); else ctx->sigma_pml.release();
   if (body_force) ctx->body_force.upload(body_force, ncq * ctx->dim, s); else ctx->body_force.release();
   if (fsi_stress) ctx->fsi_stress.upload(fsi_stress, (size_t)(ctx->dim * (ctx->dim + 1) / 2) * ctx->nUl, s); else ctx->fsi_stress.release();
@@ -860,6 +862,60 @@ int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val
   if (!ctx->sa.assembled) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr called before ifem_sa_assemble");
   const auto c = ctx->Auu.col.download(s);
   const auto v = ctx->sa.val.download(s);
+  for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
+  IFEM_API_END
+}
+
+// ---- Fluid::MPI::SCnsEX (scnsex.hip)
+static void ex_need_ctx(const ifem_ctx *ctx) {
+  if (ctx) return;
+  if (ifem_device_count() <= 0) throw Error(IFEM_E_NODEVICE, "no HIP device: libifem_hip has no CPU fallback");
+  throw Error(IFEM_E_BADPARAM, "ifem_scnsex_*: no context");
+}
+
+int ifem_scnsex_setup(ifem_ctx *ctx, const ifem_scns_params *p) {
+  IFEM_API_BEGIN
+  ex_need_ctx(ctx);
+  scnsex_setup(ctx, p);
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_scnsex_assemble_rhs(ifem_ctx *ctx, const ifem_scns_params *p, int velocity) {
+  IFEM_API_BEGIN
+  ex_need_ctx(ctx);
+  scnsex_assemble_rhs(ctx, p, velocity);
+  IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  IFEM_API_END
+}
+
+int ifem_scnsex_solve(ifem_ctx *ctx, int velocity, uint32_t *iters, double *res) {
+  IFEM_API_BEGIN
+  ex_need_ctx(ctx);
+  scnsex_solve(ctx, velocity, iters, res);
+  IFEM_API_END
+}
+
+int ifem_scnsex_step(ifem_ctx *ctx, const ifem_scns_params *p, double tolerance, int max_iterations, ifem_scnsex_stats *stats) {
+  IFEM_API_BEGIN
+  ex_need_ctx(ctx);
+  if (stats) *stats = ifem_scnsex_stats{};
+  scnsex_step(ctx, p, tolerance, max_iterations, stats);
+  IFEM_API_END
+}
+
+int ifem_scnsex_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val) {
+  IFEM_API_BEGIN
+  ex_need_ctx(ctx);
+  scnsex_check(ctx);
+  if (which < 0 || which > 1 || !rowptr) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_export_csr: which must be 0 or 1, rowptr an array");
+  hipStream_t s = ctx->stream;
+  const auto rp = ctx->Auu.rowptr.download(s);
+  for (int64_t i = 0; i <= ctx->nUo; ++i) rowptr[i] = rp[i] - rp[0];
+  if (!col || !val) return IFEM_OK;
+  if (!ctx->ex.ready) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_export_csr called before ifem_scnsex_setup");
+  const auto c = ctx->Auu.col.download(s);
+  const auto v = (which == 0 ? ctx->ex.av : ctx->ex.ap).download(s);
   for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
   IFEM_API_END
 }

@@ -390,6 +390,22 @@ struct SaState {
 } // namespace ifem
 
 namespace ifem {
+// Fluid::MPI::SCnsEX, the explicit split solver (scnsex.hip): velocity and pressure live on the same nodes, both matrices are scalar and
+// kept unconstrained on the node pattern of A_uu (one value per block, as SaState::val).  Allocated by the first ifem_scnsex_setup.
+struct ExState {
+  DBuf<double> av, ap;        // [Auu.nnzb] A_v = mu K + rho / dt M + rho M_sigma, A_p = (M / dt + M_sigma) / atm
+  DBuf<double> dvn, dpn, dvs; // their diagonals over the nodes [nUl]; diag(A_v) once per component [dim * nUl]: the Jacobi diagonal of the stacked system
+  DBuf<double> w[5];          // CG work vectors [dim * nUl]
+  DBuf<double> last, red;     // last_solution of the outer loop [(dim + 1) nUl]; the two squared norms of an outer iteration
+  double key[3] = {0, 0, 0};  // mu, rho, dt the matrices were integrated for
+  int64_t fields_version = 0, key_fields = -1; // ifem_set_scns_fields calls that gave or released the PML field / the one the matrices belong to
+  int64_t order = -1;         // PlanarCsr::order_version of A_uu the values were scattered for
+  bool ready = false;
+  int equal_order = 0;        // 0: not looked at yet, 1: pressure nodes == velocity nodes, -1: different counts (Taylor-Hood), -2: different tables
+};
+} // namespace ifem
+
+namespace ifem {
 // The pressure nodes of a uniform box level as the full lattice n[0] x n[1] (x n[2]) (setup.hip::p_lattice_ensure, host side lattice.cpp): one
 // table for its readers, the direct M_p solve (mp_direct.hip) and the S_m stencil product (sm_stencil.hip).  Decided once per context: one rank,
 // no hanging-node line, ifem_ctx::mf_uniform, Q1 pressure in 2D / 3D, the map node -> lattice point a bijection onto the whole box.
@@ -546,6 +562,7 @@ struct ifem_ctx {
   ifem::Hanging hang; // hanging-node lines (hanging.hip)
   ifem::FsiState fsi; // solid + scratch of the device-side FSI inputs (fsi.hip)
   ifem::SaState sa;   // Spalart-Allmaras turbulence model on the velocity nodes (sa.hip)
+  ifem::ExState ex;   // Fluid::MPI::SCnsEX: scalar node matrices of the explicit split solver (scnsex.hip)
   // multigrid (ifem_mg_attach): the next coarser level (not owned) and the pressure transfers to it; per-level state of
   // the S_m V-cycle: 1/diag(S_m), largest eigenvalue of D^-1 S_m, scratch vectors [nPl]
   ifem_ctx *mg_coarse = nullptr;

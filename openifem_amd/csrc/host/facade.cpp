@@ -18,7 +18,7 @@ struct Handle {
   std::unique_ptr<Fluid::MPI::FluidSolver<3>> s3;
   std::ostringstream log;
 };
-// the formulation named by the driver: "InsIM" (mpi_insim.h) or "SCnsIM" (mpi_scnsim.h)
+// the formulation named by the driver: "InsIM" (mpi_insim.h), "SCnsIM" (mpi_scnsim.h), "SCnsEX" (mpi_scnsex.h), ...
 template <int dim>
 std::unique_ptr<Fluid::MPI::FluidSolver<dim>> make_solver(const char *kind, Triangulation<dim> &t,
                                                           const Parameters::AllParameters &params, int device) {
@@ -27,7 +27,8 @@ std::unique_ptr<Fluid::MPI::FluidSolver<dim>> make_solver(const char *kind, Tria
   if (k == "SCnsIM") return std::unique_ptr<Fluid::MPI::FluidSolver<dim>>(new Fluid::MPI::SCnsIM<dim>(t, params, device));
   if (k == "InsIMEX") return std::unique_ptr<Fluid::MPI::FluidSolver<dim>>(new Fluid::MPI::InsIMEX<dim>(t, params, device));
   if (k == "SUPGInsIM") return std::unique_ptr<Fluid::MPI::FluidSolver<dim>>(new Fluid::MPI::SUPGInsIM<dim>(t, params, device));
-  throw std::invalid_argument("unknown fluid solver '" + k + "' (InsIM, InsIMEX, SCnsIM, SUPGInsIM)");
+  if (k == "SCnsEX") return std::unique_ptr<Fluid::MPI::FluidSolver<dim>>(new Fluid::MPI::SCnsEX<dim>(t, params, device));
+  throw std::invalid_argument("unknown fluid solver '" + k + "' (InsIM, InsIMEX, SCnsIM, SUPGInsIM, SCnsEX)");
 }
 // assemble / solve / solver_opts live in the two solver families, not in FluidSolver (as in the reference)
 template <int dim, class FI, class FS>
@@ -35,6 +36,8 @@ void with_family(Fluid::MPI::FluidSolver<dim> *s, FI fi, FS fs) {
   if (auto *a = dynamic_cast<Fluid::MPI::InsIM<dim> *>(s)) fi(*a);
   else if (auto *x = dynamic_cast<Fluid::MPI::InsIMEX<dim> *>(s)) fi(*x);
   else if (auto *b = dynamic_cast<Fluid::MPI::SUPGFluidSolver<dim> *>(s)) fs(*b);
+  else if (dynamic_cast<Fluid::MPI::SCnsEX<dim> *>(s))
+    throw std::invalid_argument("SCnsEX has no assemble / solve / solver_opts of the implicit families: run_one_step and ifemx_scnsex_last_step");
   else throw std::logic_error("unknown solver family");
 }
 template <class F>
@@ -513,6 +516,28 @@ int ifemx_turbulence_setup(void *hv, int32_t *node, double *value, int64_t *n_li
   });
 }
 
+// SCnsEX::set_hard_coded_boundary_condition_time(id, time) (mpi_scnsex.cpp:84-97) and the counters of its most recent run_one_step
+int ifemx_set_hard_coded_boundary_condition_time(void *hv, unsigned id, double time) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto set = [&](auto *s) {
+      if (!s) throw std::invalid_argument("set_hard_coded_boundary_condition_time: not an SCnsEX solver");
+      s->set_hard_coded_boundary_condition_time(id, time);
+    };
+    if (h->dim == 2) set(dynamic_cast<Fluid::MPI::SCnsEX<2> *>(h->s2.get())); else set(dynamic_cast<Fluid::MPI::SCnsEX<3> *>(h->s3.get()));
+  });
+}
+int ifemx_scnsex_last_step(void *hv, ifem_scnsex_stats *st) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto get = [&](auto *s) {
+      if (!s || !st) throw std::invalid_argument("ifemx_scnsex_last_step: not an SCnsEX solver, or no output");
+      *st = s->last_step;
+    };
+    if (h->dim == 2) get(dynamic_cast<Fluid::MPI::SCnsEX<2> *>(h->s2.get())); else get(dynamic_cast<Fluid::MPI::SCnsEX<3> *>(h->s3.get()));
+  });
+}
+
 int ifemx_run(void *hv) {
   auto *h = static_cast<Handle *>(hv);
   return guard([&] { if (h->dim == 2) h->s2->run(); else h->s3->run(); });
@@ -567,11 +592,11 @@ int ifemx_last_stats(void *hv, ifem_solve_stats *st) {
 int ifemx_last_newton(void *hv, int32_t *newton_iterations, int32_t *fgmres_iterations) {
   auto *h = static_cast<Handle *>(hv);
   return guard([&] {
-    auto get = [&](auto &s) {
+    auto get = [&](auto &s) { // (members of FluidSolver: every family)
       if (newton_iterations) *newton_iterations = int32_t(s.last_newton_iterations);
       if (fgmres_iterations) *fgmres_iterations = int32_t(s.last_fgmres_iterations);
     };
-    if (h->dim == 2) with_family<2>(h->s2.get(), get, get); else with_family<3>(h->s3.get(), get, get);
+    if (h->dim == 2) get(*h->s2); else get(*h->s3);
   });
 }
 int ifemx_assemble(void *hv, int use_nonzero) {
@@ -592,7 +617,9 @@ ifem_solver_opts *ifemx_solver_opts(void *hv) {
   auto *h = static_cast<Handle *>(hv);
   ifem_solver_opts *o = nullptr;
   auto get = [&](auto &s) { o = &s.solver_opts; };
-  if (h->dim == 2) with_family<2>(h->s2.get(), get, get); else with_family<3>(h->s3.get(), get, get);
+  try {
+    if (h->dim == 2) with_family<2>(h->s2.get(), get, get); else with_family<3>(h->s3.get(), get, get);
+  } catch (const std::exception &e) { g_err = e.what(); } // (SCnsEX keeps none: NULL)
   return o;
 }
 ifem_ctx *ifemx_ctx(void *hv) {

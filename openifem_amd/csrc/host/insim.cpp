@@ -1,6 +1,7 @@
 #include "insim.hpp"
 #include <cmath>
 #include <iomanip>
+#include "../ctx.hpp"
 
 namespace ifem_host {
 namespace Utils {
@@ -266,6 +267,29 @@ std::vector<double> FluidSolver<dim>::update_stress() {
   std::vector<double> s((size_t)(dim * dim) * (size_t)dofs.n_unodes);
   check(ifem_update_stress(ctx, parameters.viscosity, s.data()), "update_stress");
   return s;
+}
+
+template <int dim>
+void FluidSolver<dim>::upload_fields() {
+  if (!body_force && !sigma_pml_field) return;
+  const auto &d = dofs;
+  ifem::FeTables fe;
+  ifem::build_fe_tables(fe, dim, d.kv);
+  constexpr int nv = 1 << dim;
+  const size_t n_cells = d.cell_unodes.size() / d.nu;
+  std::vector<double> pml, bf;
+  if (sigma_pml_field) pml.resize(n_cells * fe.nq);
+  if (body_force) bf.resize(n_cells * fe.nq * dim);
+  for (size_t c = 0; c < n_cells; ++c)
+    for (int q = 0; q < fe.nq; ++q) {
+      std::array<double, dim> x{};
+      for (int v = 0; v < nv; ++v)
+        for (int e = 0; e < dim; ++e) x[e] += fe.psi[q * nv + v] * d.vcoords[(c * nv + v) * dim + e];
+      if (sigma_pml_field) pml[c * fe.nq + q] = (*sigma_pml_field)(x, 0);
+      if (body_force)
+        for (int e = 0; e < dim; ++e) bf[(c * fe.nq + q) * dim + e] = (*body_force)(x, e);
+    }
+  check(ifem_set_scns_fields(ctx, pml.empty() ? nullptr : pml.data(), bf.empty() ? nullptr : bf.data(), nullptr), "initialize_system");
 }
 
 template <int dim>

@@ -3,6 +3,7 @@
 //   Fluid::MPI::FluidSolver<dim>     include/mpi_fluid_solver.h:89-151   (run, run_one_step, setup_dofs,
 //                                    make_constraints, initialize_system, get_current_solution, hooks)
 //   Fluid::MPI::InsIM<dim>           include/mpi_insim.h:35-99           (assemble, solve, run_one_step, run)
+//   Fluid::MPI::SCnsEX<dim>          include/mpi_scnsex.h:33-122         (run_one_step, run, set_hard_coded_boundary_condition_time)
 // Same member names, argument meaning and error behaviour (exceptions with the reference's messages); the
 // PETSc matrices/vectors are replaced by one ifem_ctx (device) reached only through the C ABI of ifem_hip.h.
 #pragma once
@@ -141,6 +142,9 @@ protected:
   friend class SpalartAllmaras<dim>;
   std::unique_ptr<TurbulenceModel<dim>> turbulence_model;
   void check(int rc, const char *what) const;
+  // evaluates body_force / sigma_pml_field at the quadrature points and uploads them (once per initialize_system of the slightly
+  // compressible solvers: SUPGFluidSolver, SCnsEX)
+  void upload_fields();
   // the same formulation on another triangulation (a coarser multigrid level); nullptr: this family keeps no levels
   virtual std::unique_ptr<FluidSolver<dim>> make_level_solver(Triangulation<dim> &) const { return nullptr; }
   // builds the next coarser level (recursively the whole chain) and attaches it; false when there is none
@@ -245,8 +249,6 @@ public:
   ifem_solve_stats last_stats{};
 
 protected:
-  // evaluates body_force / sigma_pml_field at the quadrature points and uploads them (once per initialize_system)
-  void upload_fields();
   using FluidSolver<dim>::parameters;
   using FluidSolver<dim>::time;
   using FluidSolver<dim>::ctx;
@@ -277,6 +279,28 @@ public:
   ifem_scns_params scns_params() const;
 
 private:
+  using FluidSolver<dim>::parameters;
+  using FluidSolver<dim>::time;
+  using FluidSolver<dim>::ctx;
+  using FluidSolver<dim>::check;
+};
+
+// Fluid::MPI::SCnsEX<dim> (include/mpi_scnsex.h, source/mpi_scnsex.cpp): the explicit split solver -- per outer iteration one scalar
+// velocity system and one pressure system, both on the device (ifem_scnsex_*); derives from FluidSolver as in the reference
+template <int dim>
+class SCnsEX : public FluidSolver<dim> {
+public:
+  SCnsEX(Triangulation<dim> &, const Parameters::AllParameters &, int device = 0);
+  void run() override;
+  void run_one_step(bool apply_nonzero_constraints, bool assemble_system = true) override;
+  void initialize_system() override;
+  // the time after which the hard coded values of boundary `id` are no longer re-evaluated (mpi_scnsex.cpp:84-97)
+  void set_hard_coded_boundary_condition_time(const unsigned int id, const double time);
+  ifem_scns_params scns_params() const;
+  ifem_scnsex_stats last_step{}; // counters of the most recent run_one_step
+
+private:
+  std::map<unsigned int, double> boundary_condition_time_limits;
   using FluidSolver<dim>::parameters;
   using FluidSolver<dim>::time;
   using FluidSolver<dim>::ctx;

@@ -19,32 +19,9 @@ SUPGFluidSolver<dim>::SUPGFluidSolver(Triangulation<dim> &tria, const Parameters
 }
 
 template <int dim>
-void SUPGFluidSolver<dim>::upload_fields() {
-  if (!this->body_force && !this->sigma_pml_field) return;
-  const auto &d = this->dofs;
-  ifem::FeTables fe;
-  ifem::build_fe_tables(fe, dim, d.kv);
-  constexpr int nv = 1 << dim;
-  const size_t n_cells = d.cell_unodes.size() / d.nu;
-  std::vector<double> pml, bf;
-  if (this->sigma_pml_field) pml.resize(n_cells * fe.nq);
-  if (this->body_force) bf.resize(n_cells * fe.nq * dim);
-  for (size_t c = 0; c < n_cells; ++c)
-    for (int q = 0; q < fe.nq; ++q) {
-      std::array<double, dim> x{};
-      for (int v = 0; v < nv; ++v)
-        for (int e = 0; e < dim; ++e) x[e] += fe.psi[q * nv + v] * d.vcoords[(c * nv + v) * dim + e];
-      if (this->sigma_pml_field) pml[c * fe.nq + q] = (*this->sigma_pml_field)(x, 0);
-      if (this->body_force)
-        for (int e = 0; e < dim; ++e) bf[(c * fe.nq + q) * dim + e] = (*this->body_force)(x, e);
-    }
-  check(ifem_set_scns_fields(ctx, pml.empty() ? nullptr : pml.data(), bf.empty() ? nullptr : bf.data(), nullptr), "initialize_system");
-}
-
-template <int dim>
 void SUPGFluidSolver<dim>::initialize_system() {
   FluidSolver<dim>::initialize_system();
-  upload_fields();
+  this->upload_fields();
   if (this->turbulence_model) this->turbulence_model->initialize_system(); // (mpi_supg_solver.cpp:290-293)
 }
 

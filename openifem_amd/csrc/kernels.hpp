@@ -85,6 +85,13 @@ void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out);
 int sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log);
 void sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
 
+// scnsex.hip -- Fluid::MPI::SCnsEX (mpi_scnsex.cpp) on scalar node matrices; state in ctx->ex
+void scnsex_check(ifem_ctx *ctx); // refuses what the solver does not cover (hanging-node lines, partitioned contexts, Taylor-Hood)
+void scnsex_setup(ifem_ctx *ctx, const ifem_scns_params *p);
+void scnsex_assemble_rhs(ifem_ctx *ctx, const ifem_scns_params *p, int velocity);
+void scnsex_solve(ifem_ctx *ctx, int velocity, uint32_t *iters, double *res_out);
+void scnsex_step(ifem_ctx *ctx, const ifem_scns_params *p, double tolerance, int max_iterations, ifem_scnsex_stats *stats);
+
 // linalg.hip -- all on ctx->stream.  Block vectors are [u (dim*nUl) | p (nPl)]; "owned" ranges only.
 struct VecLayout {
   int64_t n_u_owned; // dim*nUo

@@ -40,6 +40,8 @@ def _lib():
     L.ifemx_insim_create_cylinder.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.ifemx_add_hard_coded_boundary_condition.argtypes = [C.c_void_p, C.c_int, BC_FN]
     L.ifemx_run.argtypes = [C.c_void_p]
+    L.ifemx_set_hard_coded_boundary_condition_time.argtypes = [C.c_void_p, C.c_uint, C.c_double]
+    L.ifemx_scnsex_last_step.argtypes = [C.c_void_p, C.POINTER(capi.ScnsexStats)]
     L.ifemx_setup.argtypes = [C.c_void_p, C.c_int]
     L.ifemx_run_one_step.argtypes = [C.c_void_p, C.c_int]
     L.ifemx_run_one_step2.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -84,7 +86,7 @@ def _lib():
 
 
 class FluidSolver:
-    """Fluid::MPI::InsIM<dim> / SCnsIM<dim> on a colorised subdivided_hyper_rectangle (or the cylinder mesh of
+    """Fluid::MPI::InsIM<dim> / SCnsIM<dim> / SCnsEX<dim> on a colorised subdivided_hyper_rectangle (or the cylinder mesh of
     Utils::GridCreator), configured by a .prm text and driven like the reference's test drivers."""
     KIND = "InsIM"
 
@@ -501,6 +503,22 @@ class SCnsIM(FluidSolver):
 
 class SUPGInsIM(FluidSolver):
     KIND = "SUPGInsIM"
+
+
+class SCnsEX(FluidSolver):
+    """Fluid::MPI::SCnsEX<dim>: the explicit split solver (velocity and pressure degree equal).  No assemble / solve / opts of the implicit
+    families: run(), run_one_step() and last_step()."""
+    KIND = "SCnsEX"
+
+    def set_hard_coded_boundary_condition_time(self, bid, time):
+        """the time after which the hard coded values of boundary `bid` are no longer re-evaluated"""
+        self._chk(self.L.ifemx_set_hard_coded_boundary_condition_time(self.h, int(bid), float(time)))
+
+    def last_step(self):
+        """ifem_scnsex_stats of the most recent run_one_step"""
+        st = capi.ScnsexStats()
+        self._chk(self.L.ifemx_scnsex_last_step(self.h, C.byref(st)))
+        return st
 
 
 def channel_prm(dim=3, dt=1e-3, end_time=8e-2, refinements=0):
