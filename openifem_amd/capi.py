@@ -876,14 +876,18 @@ class Context:
         self._chk(self.L.ifem_sa_update_eddy_viscosity(self.h, C.byref(params), _ptr(out)))
         return out
 
-    def sa_export_csr(self):
+    def _export_node_csr(self, fn, *lead):
+        """a scalar matrix on the A_uu node pattern: fn(handle, *lead, rowptr, col, val), first for the row pointers alone"""
         import scipy.sparse as sp
         n = self.n_unodes_owned
         rp = np.zeros(n + 1, np.int64)
-        self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), None, None))
+        self._chk(fn(self.h, *lead, _ptr(rp), None, None))
         col, val = np.zeros(rp[-1], np.int32), np.zeros(rp[-1])
-        self._chk(self.L.ifem_sa_export_csr(self.h, _ptr(rp), _ptr(col), _ptr(val)))
+        self._chk(fn(self.h, *lead, _ptr(rp), _ptr(col), _ptr(val)))
         return sp.csr_matrix((val, col, rp), shape=(n, self.n_u // self.dim))
+
+    def sa_export_csr(self):
+        return self._export_node_csr(self.L.ifem_sa_export_csr)
 
     # ---- Fluid::MPI::SCnsEX on scalar node matrices (mpi_scnsex.cpp); velocity and pressure on the same nodes
     def scnsex_setup(self, params):
@@ -907,13 +911,7 @@ class Context:
 
     def scnsex_export_csr(self, which):
         """the unconstrained A_v (which = 0) or A_p (1) over the nodes"""
-        import scipy.sparse as sp
-        n = self.n_unodes_owned
-        rp = np.zeros(n + 1, np.int64)
-        self._chk(self.L.ifem_scnsex_export_csr(self.h, which, _ptr(rp), None, None))
-        col, val = np.zeros(rp[-1], np.int32), np.zeros(rp[-1])
-        self._chk(self.L.ifem_scnsex_export_csr(self.h, which, _ptr(rp), _ptr(col), _ptr(val)))
-        return sp.csr_matrix((val, col, rp), shape=(n, self.n_u // self.dim))
+        return self._export_node_csr(self.L.ifem_scnsex_export_csr, which)
 
     def rhs_norm(self):
         v = C.c_double()

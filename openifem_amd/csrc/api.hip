@@ -766,24 +766,38 @@ int ifem_scns_newton_step(ifem_ctx *ctx, const ifem_scns_params *p, const ifem_s
   });
 }
 
-// ---- Fluid::MPI::SpalartAllmaras (sa.hip).  A context only exists where a device does: without one the caller has none to pass.
-static void sa_need_ctx(const ifem_ctx *ctx) {
+// ---- the models on scalar node matrices (sa.hip, scnsex.hip).  A context only exists where a device does: without one the caller has none to
+// pass.  prefix: "ifem_sa_*" or "ifem_scnsex_*"
+static void need_ctx(const ifem_ctx *ctx, const char *prefix) {
   if (ctx) return;
   if (ifem_device_count() <= 0) throw Error(IFEM_E_NODEVICE, "no HIP device: libifem_hip has no CPU fallback");
-  throw Error(IFEM_E_BADPARAM, "ifem_sa_*: no context");
+  throw Error(IFEM_E_BADPARAM, std::string(prefix) + ": no context");
 }
+// owned rows of a scalar matrix on the A_uu node pattern: the row pointers alone while col or val is missing, else all three
+static void export_node_csr(ifem_ctx *ctx, const DBuf<double> &values, bool ready, const char *not_ready_msg, int64_t *rowptr, int32_t *col, double *val) {
+  hipStream_t s = ctx->stream;
+  const auto rp = ctx->Auu.rowptr.download(s);
+  for (int64_t i = 0; i <= ctx->nUo; ++i) rowptr[i] = rp[i] - rp[0];
+  if (!col || !val) return;
+  if (!ready) throw Error(IFEM_E_BADPARAM, not_ready_msg);
+  const auto c = ctx->Auu.col.download(s);
+  const auto v = values.download(s);
+  for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
+}
+
+// ---- Fluid::MPI::SpalartAllmaras (sa.hip)
 static inline bool sa_vec_ok(int v) { return v >= 0 && v < IFEM_SA_N_VECS; }
 
 int ifem_sa_set_wall_points(ifem_ctx *ctx, int64_t n, const double *pts) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_set_wall_points(ctx, n, pts);
   IFEM_API_END
 }
 
 int ifem_sa_get_wall_distance(ifem_ctx *ctx, double *host_out) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_check(ctx);
   if (!host_out) throw Error(IFEM_E_BADPARAM, "ifem_sa_get_wall_distance: no output array");
   sa_ensure(ctx);
@@ -794,14 +808,14 @@ int ifem_sa_get_wall_distance(ifem_ctx *ctx, double *host_out) {
 
 int ifem_sa_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *node, const double *inhom) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_set_constraints(ctx, which, n, node, inhom);
   IFEM_API_END
 }
 
 int ifem_sa_vec_set(ifem_ctx *ctx, int vec, const double *host) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_check(ctx);
   if (!sa_vec_ok(vec) || !host) throw Error(IFEM_E_BADPARAM, "ifem_sa_vec_set: bad vector id or no data");
   sa_ensure(ctx);
@@ -812,7 +826,7 @@ int ifem_sa_vec_set(ifem_ctx *ctx, int vec, const double *host) {
 
 int ifem_sa_vec_get(ifem_ctx *ctx, int vec, double *host) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_check(ctx);
   if (!sa_vec_ok(vec) || !host) throw Error(IFEM_E_BADPARAM, "ifem_sa_vec_get: bad vector id or no output array");
   sa_ensure(ctx);
@@ -823,7 +837,7 @@ int ifem_sa_vec_get(ifem_ctx *ctx, int vec, double *host) {
 
 int ifem_sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_assemble(ctx, p, use_nonzero);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
@@ -831,51 +845,38 @@ int ifem_sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero) {
 
 int ifem_sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_solve(ctx, use_nonzero, iters, res);
   IFEM_API_END
 }
 
 int ifem_sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log) {
   return api_count([&] {
-    sa_need_ctx(ctx);
+    need_ctx(ctx, "ifem_sa_*");
     return sa_newton_step(ctx, p, apply_nonzero, tolerance, max_iterations, log);
   });
 }
 
 int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_update_eddy_viscosity(ctx, p, host_out);
   IFEM_API_END
 }
 
 int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val) {
   IFEM_API_BEGIN
-  sa_need_ctx(ctx);
+  need_ctx(ctx, "ifem_sa_*");
   sa_check(ctx);
   if (!rowptr) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr: no rowptr array");
-  hipStream_t s = ctx->stream;
-  const auto rp = ctx->Auu.rowptr.download(s);
-  for (int64_t i = 0; i <= ctx->nUo; ++i) rowptr[i] = rp[i] - rp[0];
-  if (!col || !val) return IFEM_OK;
-  if (!ctx->sa.assembled) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr called before ifem_sa_assemble");
-  const auto c = ctx->Auu.col.download(s);
-  const auto v = ctx->sa.val.download(s);
-  for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
+  export_node_csr(ctx, ctx->sa.val, ctx->sa.assembled, "ifem_sa_export_csr called before ifem_sa_assemble", rowptr, col, val);
   IFEM_API_END
 }
 
 // ---- Fluid::MPI::SCnsEX (scnsex.hip)
-static void ex_need_ctx(const ifem_ctx *ctx) {
-  if (ctx) return;
-  if (ifem_device_count() <= 0) throw Error(IFEM_E_NODEVICE, "no HIP device: libifem_hip has no CPU fallback");
-  throw Error(IFEM_E_BADPARAM, "ifem_scnsex_*: no context");
-}
-
 int ifem_scnsex_setup(ifem_ctx *ctx, const ifem_scns_params *p) {
   IFEM_API_BEGIN
-  ex_need_ctx(ctx);
+  need_ctx(ctx, "ifem_scnsex_*");
   scnsex_setup(ctx, p);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
@@ -883,7 +884,7 @@ int ifem_scnsex_setup(ifem_ctx *ctx, const ifem_scns_params *p) {
 
 int ifem_scnsex_assemble_rhs(ifem_ctx *ctx, const ifem_scns_params *p, int velocity) {
   IFEM_API_BEGIN
-  ex_need_ctx(ctx);
+  need_ctx(ctx, "ifem_scnsex_*");
   scnsex_assemble_rhs(ctx, p, velocity);
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   IFEM_API_END
@@ -891,14 +892,14 @@ int ifem_scnsex_assemble_rhs(ifem_ctx *ctx, const ifem_scns_params *p, int veloc
 
 int ifem_scnsex_solve(ifem_ctx *ctx, int velocity, uint32_t *iters, double *res) {
   IFEM_API_BEGIN
-  ex_need_ctx(ctx);
+  need_ctx(ctx, "ifem_scnsex_*");
   scnsex_solve(ctx, velocity, iters, res);
   IFEM_API_END
 }
 
 int ifem_scnsex_step(ifem_ctx *ctx, const ifem_scns_params *p, double tolerance, int max_iterations, ifem_scnsex_stats *stats) {
   IFEM_API_BEGIN
-  ex_need_ctx(ctx);
+  need_ctx(ctx, "ifem_scnsex_*");
   if (stats) *stats = ifem_scnsex_stats{};
   scnsex_step(ctx, p, tolerance, max_iterations, stats);
   IFEM_API_END
@@ -906,17 +907,10 @@ int ifem_scnsex_step(ifem_ctx *ctx, const ifem_scns_params *p, double tolerance,
 
 int ifem_scnsex_export_csr(ifem_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val) {
   IFEM_API_BEGIN
-  ex_need_ctx(ctx);
+  need_ctx(ctx, "ifem_scnsex_*");
   scnsex_check(ctx);
   if (which < 0 || which > 1 || !rowptr) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_export_csr: which must be 0 or 1, rowptr an array");
-  hipStream_t s = ctx->stream;
-  const auto rp = ctx->Auu.rowptr.download(s);
-  for (int64_t i = 0; i <= ctx->nUo; ++i) rowptr[i] = rp[i] - rp[0];
-  if (!col || !val) return IFEM_OK;
-  if (!ctx->ex.ready) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_export_csr called before ifem_scnsex_setup");
-  const auto c = ctx->Auu.col.download(s);
-  const auto v = (which == 0 ? ctx->ex.av : ctx->ex.ap).download(s);
-  for (int64_t k = 0; k < rowptr[ctx->nUo]; ++k) { col[k] = c[rp[0] + k]; val[k] = v[rp[0] + k]; }
+  export_node_csr(ctx, which == 0 ? ctx->ex.av : ctx->ex.ap, ctx->ex.ready, "ifem_scnsex_export_csr called before ifem_scnsex_setup", rowptr, col, val);
   IFEM_API_END
 }
 

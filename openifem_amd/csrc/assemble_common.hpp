@@ -1,6 +1,7 @@
 // assemble_common.hpp -- argument block and small helpers shared by the InsIM assembly driver (assemble.hip) and its cell
 // kernels (assemble3.hip: 3D Q2/Q1 on the FP64 matrix cores; assemble2.hip: every other (dim, kv), quadrature-point-outer with
-// register accumulators); Geo and the small inverses also serve assemble_scns.hip and sa.hip.
+// register accumulators); Geo, the small inverses, the cell geometry of the d-linear map, the Neumann face term, pick and grid_for also
+// serve the one-wavefront-per-cell kernels of assemble_scns.hip, sa.hip and scnsex.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -66,6 +67,54 @@ __device__ inline R inv_small(const R *J, R *Ji) {
     return det;
   }
 }
+
+// ---- cell geometry under the d-linear map of the 2^DIM vertices, for the one-wavefront-per-cell kernels of sa.hip, scnsex.hip and
+// assemble_scns.hip (assemble2.hip / assemble3.hip form J from tensor factors and keep their own)
+// J = sum_v X_v (x) dpsi_v at quadrature point q of the table dpsi ([point][2^DIM][DIM]; q = 0: dpsi is the point's own rows), Ji = J^-1;
+// returns det J.  Keep it forced inline, and pass table and index from a cell kernel's quadrature loop: the loops of the callers sit at the
+// unroller's thresholds, and with either changed some 3D kernels spill or take more registers (profiles/scalar_node_refactor.txt)
+template <int DIM>
+__device__ __forceinline__ double cell_jacobian(const double *X, const double *dpsi, double *Ji, int q = 0) {
+  constexpr int NP = 1 << DIM;
+  double J[DIM * DIM];
+  for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
+  for (int v = 0; v < NP; ++v)
+    for (int d = 0; d < DIM; ++d)
+      for (int e = 0; e < DIM; ++e) J[d * DIM + e] += X[v * DIM + d] * dpsi[(q * NP + v) * DIM + e];
+  return inv_small<DIM>(J, Ji);
+}
+
+// Neumann pressure faces of cell cc (mpi_scnsim.cpp:521-549, mpi_scnsex.cpp:312-340): fe[a * DIM + c] -= int_f N_a p n_c over every face whose
+// boundary id is listed in A.neumann_id.  The lanes lane, lane + stride, ... of the cell's group share the entries; X: the cell's vertices
+template <int DIM, int NU, class Args>
+__device__ __forceinline__ void neumann_faces(const Args &A, const FeTables &T, int64_t cc, const double *X, int lane, int stride, double *fe) {
+  constexpr int NP = 1 << DIM;
+  for (int f = 0; f < 2 * DIM; ++f) {
+    const int bid = A.cell_face_bid[cc * 2 * DIM + f];
+    if (bid < 0) continue;
+    double pbc = 0; bool hit = false;
+    for (int k = 0; k < A.n_neumann; ++k) if (A.neumann_id[k] == bid) { pbc = A.neumann_p[k]; hit = true; }
+    if (!hit) continue;
+    const int nd = f >> 1; const double sgn = (f & 1) ? 1.0 : -1.0;
+    for (int i = lane; i < NU * DIM; i += stride) {
+      const int a = i / DIM, c = i - a * DIM;
+      double acc = 0;
+      for (int qf = 0; qf < T.nqf; ++qf) {
+        double Ji[DIM * DIM];
+        const double det = cell_jacobian<DIM>(X, &T.fdpsi[(f * T.nqf + qf) * NP * DIM], Ji);
+        acc += T.fphi[(f * T.nqf + qf) * NU + a] * (sgn * Ji[nd * DIM + c]) * pbc * fabs(det) * T.fw[qf];
+      }
+      fe[i] -= acc;
+    }
+  }
+}
+
+// the (dim, kv) instantiation of a launcher or kernel: a = <2, 1>, b = <2, 2>, c = <3, 1>, d = <3, 2>
+template <class F>
+inline F pick(int dim, int kv, F a, F b, F c, F d) { return dim == 2 ? (kv == 1 ? a : b) : (kv == 1 ? c : d); }
+
+// blocks of 256 lanes that cover n
+inline unsigned grid_for(int64_t n) { return unsigned((n + 255) / 256); }
 
 // scatter add into global memory: hardware atomic, or plain read-modify-write when the launch covers one colour
 template <bool ATOMIC>

@@ -9,7 +9,7 @@
 // distribute_local_to_global into A_uu / A_up / A_pu / A_pp.  All shipped SCnsIM cases are Q1/Q1
 // (12 or 32 local dofs), where this kernel is latency-, not throughput-bound.
 #include <hip/hip_runtime.h>
-#include "ctx.hpp"
+#include "assemble_common.hpp"
 #include "kernels.hpp"
 
 namespace ifem {
@@ -48,24 +48,6 @@ struct ScnsArgs {
   int use_inhom;
   int inc; // IFEM_FORM_SUPG_INSIM: the incompressible integrand of mpi_insim_supg.cpp
 };
-
-template <int DIM>
-__device__ inline double inv_s(const double *J, double *Ji) {
-  if constexpr (DIM == 2) {
-    const double det = J[0] * J[3] - J[1] * J[2];
-    const double r = 1.0 / det;
-    Ji[0] = J[3] * r; Ji[1] = -J[1] * r; Ji[2] = -J[2] * r; Ji[3] = J[0] * r;
-    return det;
-  } else {
-    const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
-    const double det = J[0] * c00 + J[1] * c01 + J[2] * c02;
-    const double r = 1.0 / det;
-    Ji[0] = c00 * r; Ji[3] = c01 * r; Ji[6] = c02 * r;
-    Ji[1] = (J[2] * J[7] - J[1] * J[8]) * r; Ji[4] = (J[0] * J[8] - J[2] * J[6]) * r; Ji[7] = (J[1] * J[6] - J[0] * J[7]) * r;
-    Ji[2] = (J[1] * J[5] - J[2] * J[4]) * r; Ji[5] = (J[2] * J[3] - J[0] * J[5]) * r; Ji[8] = (J[0] * J[4] - J[1] * J[3]) * r;
-    return det;
-  }
-}
 
 // per quadrature point data kept in LDS
 template <int DIM>
@@ -183,12 +165,8 @@ __global__ __launch_bounds__(64 * WPB) void k_scns_assemble(ScnsArgs A) {
   __syncthreads();
   // ---- phase 1: geometry, fields and stabilisation parameters per quadrature point (:146-289)
   for (int q = lane; q < NQ; q += 64) {
-    double J[DIM * DIM], Ji[DIM * DIM];
-    for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
-    for (int v = 0; v < NP; ++v)
-      for (int d = 0; d < DIM; ++d)
-        for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * T.dpsi[(q * NP + v) * DIM + e];
-    const double det = inv_s<DIM>(J, Ji);
+    double Ji[DIM * DIM];
+    const double det = cell_jacobian<DIM>(S.X, T.dpsi, Ji, q);
     QPoint<DIM> &Q = S.qp[q];
     Q.JxW = fabs(det) * T.w[q];
     for (int a = 0; a < NU; ++a)
@@ -311,31 +289,7 @@ __global__ __launch_bounds__(64 * WPB) void k_scns_assemble(ScnsArgs A) {
   }
   __syncthreads();
   // Neumann faces (:521-549)
-  if (A.n_neumann != 0 && active) {
-    for (int f = 0; f < 2 * DIM; ++f) {
-      const int bid = A.cell_face_bid[cc * 2 * DIM + f];
-      if (bid < 0) continue;
-      double pbc = 0; bool hit = false;
-      for (int k = 0; k < A.n_neumann; ++k) if (A.neumann_id[k] == bid) { pbc = A.neumann_p[k]; hit = true; }
-      if (!hit) continue;
-      const int nd = f >> 1; const double sgn = (f & 1) ? 1.0 : -1.0;
-      for (int i = lane; i < NU * DIM; i += 64) {
-        const int a = i / DIM, c = i - a * DIM;
-        double acc = 0;
-        for (int qf = 0; qf < T.nqf; ++qf) {
-          double J[DIM * DIM], Ji[DIM * DIM];
-          for (int k = 0; k < DIM * DIM; ++k) J[k] = 0;
-          const double *dps = &T.fdpsi[(f * T.nqf + qf) * NP * DIM];
-          for (int v = 0; v < NP; ++v)
-            for (int d = 0; d < DIM; ++d)
-              for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * dps[v * DIM + e];
-          const double det = inv_s<DIM>(J, Ji);
-          acc += T.fphi[(f * T.nqf + qf) * NU + a] * (sgn * Ji[nd * DIM + c]) * pbc * fabs(det) * T.fw[qf];
-        }
-        S.fe[i] -= acc;
-      }
-    }
-  }
+  if (A.n_neumann != 0 && active) neumann_faces<DIM, NU>(A, T, cc, S.X, lane, 64, S.fe);
   __syncthreads();
   // ---- phase 3: local matrix entries (:291-421) + scatter
   for (int t = lane; t < ND * ND; t += 64) {
@@ -427,11 +381,8 @@ static void launch_scns_t(ifem_ctx *ctx, const ScnsArgs &A) {
 }
 
 static auto scns_launcher(int dim, int kv) -> void (*)(ifem_ctx *, const ScnsArgs &) {
-  if (dim == 2 && kv == 1) return launch_scns_t<2, 1>;
-  if (dim == 2 && kv == 2) return launch_scns_t<2, 2>;
-  if (dim == 3 && kv == 1) return launch_scns_t<3, 1>;
-  if (dim == 3 && kv == 2) return launch_scns_t<3, 2>;
-  throw Error(IFEM_E_BADPARAM, "unsupported (dim, kv)");
+  if (dim < 2 || dim > 3 || kv < 1 || kv > 2) throw Error(IFEM_E_BADPARAM, "unsupported (dim, kv)");
+  return pick(dim, kv, launch_scns_t<2, 1>, launch_scns_t<2, 2>, launch_scns_t<3, 1>, launch_scns_t<3, 2>);
 }
 
 void launch_scns_assemble(ifem_ctx *ctx, const ifem_scns_params *p, int use_nonzero) {
@@ -484,12 +435,9 @@ __global__ __launch_bounds__(256) void k_update_stress(int64_t n_cells, int64_t 
   const int64_t cc = active ? cell : 0;
   const FeTables &T = *fe;
   for (int q = lane; q < NQ; q += 64) {
-    double J[DIM * DIM], Ji[DIM * DIM], G[DIM * DIM];
-    for (int i = 0; i < DIM * DIM; ++i) { J[i] = 0; G[i] = 0; }
-    for (int v = 0; v < NP; ++v)
-      for (int d = 0; d < DIM; ++d)
-        for (int e = 0; e < DIM; ++e) J[d * DIM + e] += vcoords[(cc * NP + v) * DIM + d] * T.dpsi[(q * NP + v) * DIM + e];
-    inv_s<DIM>(J, Ji);
+    double Ji[DIM * DIM], G[DIM * DIM];
+    for (int i = 0; i < DIM * DIM; ++i) G[i] = 0;
+    cell_jacobian<DIM>(&vcoords[cc * NP * DIM], T.dpsi, Ji, q);
     for (int a = 0; a < NU; ++a) {
       const int64_t nd = cell_unodes[cc * NU + a];
       double g[DIM];
@@ -541,14 +489,8 @@ void launch_update_stress(ifem_ctx *ctx, double mu) {
   IFEM_HIP_CHECK(hipMemsetAsync(cnt.p, 0, n * sizeof(double), s));
   IFEM_HIP_CHECK(hipMemsetAsync(ctx->stress.p, 0, ctx->stress.n * sizeof(double), s));
   const unsigned blocks = unsigned((ctx->n_cells + 3) / 4);
-#define IFEM_US(D, K) hipLaunchKernelGGL((k_update_stress<D, K>), dim3(blocks), dim3(256), 0, s, ctx->n_cells, n, ctx->d_fe.p, \
-                                         ctx->xinv.p, ctx->vcoords.p, ctx->cell_unodes.p, ctx->vec[IFEM_VEC_PRESENT].p, mu,   \
-                                         ctx->stress.p, cnt.p)
-  if (dim == 2 && ctx->kv == 1) IFEM_US(2, 1);
-  else if (dim == 2 && ctx->kv == 2) IFEM_US(2, 2);
-  else if (dim == 3 && ctx->kv == 1) IFEM_US(3, 1);
-  else IFEM_US(3, 2);
-#undef IFEM_US
+  hipLaunchKernelGGL(pick(dim, ctx->kv, k_update_stress<2, 1>, k_update_stress<2, 2>, k_update_stress<3, 1>, k_update_stress<3, 2>), dim3(blocks), dim3(256), 0, s,
+                     ctx->n_cells, n, ctx->d_fe.p, ctx->xinv.p, ctx->vcoords.p, ctx->cell_unodes.p, ctx->vec[IFEM_VEC_PRESENT].p, mu, ctx->stress.p, cnt.p);
   hipLaunchKernelGGL(k_stress_avg, dim3(1024), dim3(256), 0, s, n, dim * dim, cnt.p, ctx->stress.p);
   halo_refresh_nodal(ctx, dim * dim, ctx->stress.p); // owned nodes saw every cell that touches them; ghosts take the owner's average
   IFEM_HIP_CHECK(hipStreamSynchronize(s));

@@ -129,6 +129,8 @@ void uu_lift_mf(ifem_ctx *ctx); // apply_mf.hip: inhomogeneity lift of the right
 void shat_refresh(ifem_ctx *ctx, bool f32);
 void spmv_shat(ifem_ctx *ctx, const double *xu, double *yu, bool f32);
 void shat_jacobi(ifem_ctx *ctx, const double *x, double *y);
+// the same masked product for any scalar matrix `val` on the A_uu node pattern (sa.hip, scnsex.hip): ncomp in {1, dim}, flag may be nullptr
+void spmv_node_scalar(ifem_ctx *ctx, int ncomp, const double *val, const uint8_t *flag, const double *diag, const double *x, double *y);
 // y_p = B x_u
 // `part` of the row-parallel products below: 0 all rows, 1 the rows that read owned columns only, 2 the others (several
 // ranks: 1 runs while the halo of x is in flight, 2 after halo_wait; see PlanarCsr::split_rows)

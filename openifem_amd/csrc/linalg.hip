@@ -454,6 +454,15 @@ void spmv_shat(ifem_ctx *ctx, const double *xu, double *yu, bool f32) {
   }
 }
 
+// the same product for the scalar node matrices of sa.hip and scnsex.hip: val on the pattern of A_uu, x and y with ncomp (1 or dim) components
+// per node, 16 lanes per row in every dimension (a Q2 row holds up to 25 / 125 nodes); flag = nullptr: no constrained dofs, diag is not read
+void spmv_node_scalar(ifem_ctx *ctx, int ncomp, const double *val, const uint8_t *flag, const double *diag, const double *x, double *y) {
+  const int64_t n = ctx->nUo;
+  if (n == 0) return;
+  const auto k = ncomp == 1 ? k_spmv_scalar<1, 16, double> : ncomp == 2 ? k_spmv_scalar<2, 16, double> : k_spmv_scalar<3, 16, double>;
+  hipLaunchKernelGGL(k, dim3(blocks_for_rows(n, 16)), dim3(256), 0, ctx->stream, n, ctx->Auu.rowptr.p, ctx->Auu.col.p, val, flag, diag, x, y);
+}
+
 void shat_jacobi(ifem_ctx *ctx, const double *x, double *y) {
   const int64_t n = ctx->nUo;
   if (!n) return;

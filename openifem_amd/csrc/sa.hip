@@ -156,12 +156,8 @@ __global__ __launch_bounds__(64 * WPB) void k_sa_assemble(SaArgs A) {
   __syncthreads();
   // ---- phase 1: geometry, fields and model coefficients per quadrature point (:731-791)
   for (int q = lane; q < NQ; q += 64) {
-    double J[DIM * DIM], Ji[DIM * DIM];
-    for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
-    for (int v = 0; v < NP; ++v)
-      for (int d = 0; d < DIM; ++d)
-        for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * T.dpsi[(q * NP + v) * DIM + e];
-    const double det = inv_small<DIM>(J, Ji);
+    double Ji[DIM * DIM];
+    const double det = cell_jacobian<DIM>(S.X, T.dpsi, Ji, q);
     SaQPoint<DIM> &Q = S.qp[q];
     Q.JxW = fabs(det) * T.w[q];
     double u[DIM], G[DIM * DIM], gnu[DIM];
@@ -289,21 +285,7 @@ void launch_node_points_t(ifem_ctx *ctx, double *xn) {
   IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // `last` is released on return
 }
 
-// ---- the linear system -----------------------------------------------------------------------------------------------------------
-// y = A x over the owned rows, 16 lanes per row (a Q2 row holds up to 25 / 125 nodes)
-__global__ __launch_bounds__(256) void k_sa_spmv(int64_t n_rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
-                                                 const double *__restrict__ x, double *__restrict__ y) {
-  const int64_t row = (int64_t(blockIdx.x) * 256 + threadIdx.x) >> 4;
-  const int lig = threadIdx.x & 15;
-  double acc = 0;
-  if (row < n_rows) {
-    const int64_t rs = rp[row], re = rp[row + 1];
-    for (int64_t k = rs + lig; k < re; k += 16) acc += val[k] * x[col[k]];
-  }
-  for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 16);
-  if (lig == 0 && row < n_rows) y[row] = acc;
-}
-
+// ---- the linear system: y = A x over the owned rows is linalg.hip::spmv_node_scalar with one component ---------------------------------
 // mu_t = f_v1 nu~ rho (:904-911)
 __global__ void k_sa_eddy(int64_t n, const double *__restrict__ nu, double laminar_nu, double rho, double *__restrict__ out) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -312,8 +294,6 @@ __global__ void k_sa_eddy(int64_t n, const double *__restrict__ nu, double lamin
   const double chi = nu[i] / laminar_nu, chi3 = chi * chi * chi;
   out[i] = chi3 / (chi3 + cv1_3) * nu[i] * rho;
 }
-
-inline unsigned grid_for(int64_t n) { return unsigned((n + 255) / 256); }
 
 // ghost entries of a nodal scalar [nUl] := the owners' values (collective; nothing to do on one rank)
 void refresh_ghosts(ifem_ctx *ctx, double *x) {
@@ -367,10 +347,7 @@ void sa_set_wall_points(ifem_ctx *ctx, int64_t n_pts, const double *pts) {
   if (xn.n != (size_t)n * dim) { // the support points depend on the mesh alone: once per context
     xn.alloc((size_t)n * dim);
     IFEM_HIP_CHECK(hipMemsetAsync(xn.p, 0, xn.n * sizeof(double), s));
-    if (dim == 2 && ctx->kv == 1) launch_node_points_t<2, 1>(ctx, xn.p);
-    else if (dim == 2) launch_node_points_t<2, 2>(ctx, xn.p);
-    else if (ctx->kv == 1) launch_node_points_t<3, 1>(ctx, xn.p);
-    else launch_node_points_t<3, 2>(ctx, xn.p);
+    pick(dim, ctx->kv, launch_node_points_t<2, 1>, launch_node_points_t<2, 2>, launch_node_points_t<3, 1>, launch_node_points_t<3, 2>)(ctx, xn.p);
   }
   if (dim == 2) hipLaunchKernelGGL((k_sa_wall_distance<2>), dim3(grid_for(n)), dim3(256), 0, s, n, xn.p, n_pts, dp.p, ctx->sa.wall_d.p);
   else hipLaunchKernelGGL((k_sa_wall_distance<3>), dim3(grid_for(n)), dim3(256), 0, s, n, xn.p, n_pts, dp.p, ctx->sa.wall_d.p);
@@ -426,12 +403,7 @@ void sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero) {
     // algorithmic bytes: the values written + the node data and position tables read
     const int nu = ctx->nu;
     KScope ks(ctx, IFEM_KC_ASSEMBLE, double(nnz) * 8 + double(ctx->n_cells) * (double(nu) * nu * 2 + double(nu) * (4 + 8 * (ctx->dim + 4)) + ctx->np * ctx->dim * 8));
-    if (ctx->n_cells > 0) {
-      if (ctx->dim == 2 && ctx->kv == 1) launch_sa_t<2, 1>(ctx, A);
-      else if (ctx->dim == 2) launch_sa_t<2, 2>(ctx, A);
-      else if (ctx->kv == 1) launch_sa_t<3, 1>(ctx, A);
-      else launch_sa_t<3, 2>(ctx, A);
-    }
+    if (ctx->n_cells > 0) pick(ctx->dim, ctx->kv, launch_sa_t<2, 1>, launch_sa_t<2, 2>, launch_sa_t<3, 1>, launch_sa_t<3, 2>)(ctx, A);
   }
   sa.assembled = true;
   sa.val_order = ctx->Auu.order_version;
@@ -470,7 +442,7 @@ void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out) 
       x = sa.xext.p;
     }
     KScope ks(ctx, IFEM_KC_OTHER, double(ctx->Auu.nnzb) * 12 + double(n) * 24);
-    if (n > 0) hipLaunchKernelGGL(k_sa_spmv, dim3(grid_for(n * 16)), dim3(256), 0, s, n, ctx->Auu.rowptr.p, ctx->Auu.col.p, sa.val.p, x, y);
+    spmv_node_scalar(ctx, 1, sa.val.p, nullptr, nullptr, x, y);
   };
   const OpFn Pop = [&](const double *x, double *y) {
     if (sa.ilu_ok) bilu_apply(ctx, I, /*sweeps=*/-1, x, y);

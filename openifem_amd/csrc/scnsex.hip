@@ -81,12 +81,8 @@ __global__ __launch_bounds__(64 * WPB) void k_ex_setup(ExArgs A) {
   }
   __syncthreads();
   for (int q = lane; q < NQ; q += 64) {
-    double J[DIM * DIM], Ji[DIM * DIM];
-    for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
-    for (int v = 0; v < NP; ++v)
-      for (int d = 0; d < DIM; ++d)
-        for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * T.dpsi[(q * NP + v) * DIM + e];
-    const double det = inv_small<DIM>(J, Ji);
+    double Ji[DIM * DIM];
+    const double det = cell_jacobian<DIM>(S.X, T.dpsi, Ji, q);
     S.JxW[q] = fabs(det) * T.w[q];
     S.sg[q] = A.sigma ? A.sigma[cc * NQ + q] : 0.0; // a missing field is zero (:181-187)
     for (int a = 0; a < NU; ++a)
@@ -162,12 +158,8 @@ __global__ __launch_bounds__(256) void k_ex_rhs(ExArgs A) {
   }
   __syncthreads();
   for (int q = lane; q < NQ; q += LPC) {
-    double J[DIM * DIM], Ji[DIM * DIM];
-    for (int i = 0; i < DIM * DIM; ++i) J[i] = 0;
-    for (int v = 0; v < NP; ++v)
-      for (int d = 0; d < DIM; ++d)
-        for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * T.dpsi[(q * NP + v) * DIM + e];
-    const double det = inv_small<DIM>(J, Ji);
+    double Ji[DIM * DIM];
+    const double det = cell_jacobian<DIM>(S.X, T.dpsi, Ji, q);
     const double JxW = fabs(det) * T.w[q];
     double u[DIM], u0[DIM], G[DIM * DIM], gp[DIM];
     double p = 0, p0 = 0;
@@ -214,31 +206,7 @@ __global__ __launch_bounds__(256) void k_ex_rhs(ExArgs A) {
   }
   __syncthreads();
   // Neumann faces (:312-340)
-  if (vel && A.n_neumann != 0 && active) {
-    for (int f = 0; f < 2 * DIM; ++f) {
-      const int bid = A.cell_face_bid[cc * 2 * DIM + f];
-      if (bid < 0) continue;
-      double pbc = 0; bool hit = false;
-      for (int k = 0; k < A.n_neumann; ++k) if (A.neumann_id[k] == bid) { pbc = A.neumann_p[k]; hit = true; }
-      if (!hit) continue;
-      const int nd = f >> 1; const double sgn = (f & 1) ? 1.0 : -1.0;
-      for (int i = lane; i < NU * DIM; i += LPC) {
-        const int a = i / DIM, c = i - a * DIM;
-        double acc = 0;
-        for (int qf = 0; qf < T.nqf; ++qf) {
-          double J[DIM * DIM], Ji[DIM * DIM];
-          for (int k = 0; k < DIM * DIM; ++k) J[k] = 0;
-          const double *dps = &T.fdpsi[(f * T.nqf + qf) * NP * DIM];
-          for (int v = 0; v < NP; ++v)
-            for (int d = 0; d < DIM; ++d)
-              for (int e = 0; e < DIM; ++e) J[d * DIM + e] += S.X[v * DIM + d] * dps[v * DIM + e];
-          const double det = inv_small<DIM>(J, Ji);
-          acc += T.fphi[(f * T.nqf + qf) * NU + a] * (sgn * Ji[nd * DIM + c]) * pbc * fabs(det) * T.fw[qf];
-        }
-        S.fe[i] -= acc;
-      }
-    }
-  }
+  if (vel && A.n_neumann != 0 && active) neumann_faces<DIM, NU>(A, T, cc, S.X, lane, LPC, S.fe);
   __syncthreads();
   if (!active) return;
   for (int i = lane; i < NF; i += LPC) {
@@ -265,37 +233,9 @@ void launch_rhs_t(ifem_ctx *ctx, const ExArgs &A) {
   hipLaunchKernelGGL((k_ex_rhs<DIM, KV, LPC>), dim3(unsigned((A.n_cells + CPB - 1) / CPB)), dim3(256), smem, ctx->stream, A);
   IFEM_HIP_CHECK(hipGetLastError());
 }
-using ExLaunch = void (*)(ifem_ctx *, const ExArgs &);
-ExLaunch pick(int dim, int kv, ExLaunch a, ExLaunch b, ExLaunch c, ExLaunch d) { return dim == 2 ? (kv == 1 ? a : b) : (kv == 1 ? c : d); }
 
-// ---- 2. masked operators on the node pattern, 16 lanes per row (a Q2 row holds up to 25 / 125 nodes).  x and y hold DIM components per node
-// (DIM = 1: the plain scalar product); flag: the constrained dofs (nullptr: none)
-template <int DIM>
-__global__ __launch_bounds__(256) void k_ex_apply(int64_t n_rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
-                                                  const double *__restrict__ diag, const uint8_t *__restrict__ flag, const double *__restrict__ x, double *__restrict__ y) {
-  const int64_t row = (int64_t(blockIdx.x) * 256 + threadIdx.x) >> 4;
-  const int lig = threadIdx.x & 15;
-  double acc[DIM];
-  for (int c = 0; c < DIM; ++c) acc[c] = 0;
-  if (row < n_rows) {
-    const int64_t rs = rp[row], re = rp[row + 1];
-    for (int64_t k = rs + lig; k < re; k += 16) {
-      const double a = val[k];
-      const int64_t j = int64_t(DIM) * col[k];
-      for (int c = 0; c < DIM; ++c)
-        if (!flag || !flag[j + c]) acc[c] += a * x[j + c];
-    }
-  }
-  for (int c = 0; c < DIM; ++c)
-    for (int o = 8; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 16);
-  if (lig == 0 && row < n_rows)
-    for (int c = 0; c < DIM; ++c) {
-      const int64_t i = int64_t(DIM) * row + c;
-      y[i] = (flag && flag[i]) ? diag[row] * x[i] : acc[c];
-    }
-}
-
-// the lift: rhs_c <- P_c (rhs_c - A_v g_c); g is zero where no line stands
+// ---- 2. the masked operators on the node pattern are linalg.hip::spmv_node_scalar (apply_op below).  The lift: rhs_c <- P_c (rhs_c - A_v g_c);
+// g is zero where no line stands.  16 lanes per row (a Q2 row holds up to 25 / 125 nodes)
 template <int DIM>
 __global__ __launch_bounds__(256) void k_ex_lift(int64_t n_rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
                                                  const uint8_t *__restrict__ flag, const double *__restrict__ g, double *__restrict__ rhs) {
@@ -344,8 +284,6 @@ __global__ __launch_bounds__(256) void k_ex_norms(int64_t n, const double *__res
   }
 }
 
-inline unsigned grid_for(int64_t n) { return unsigned((n + 255) / 256); }
-
 void check_params(const ifem_scns_params *p) {
   if (!p || !(p->dt > 0) || !(p->viscosity > 0) || !(p->rho > 0)) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_*: bad ifem_scns_params (dt, viscosity and rho must be positive)");
   if (p->n_neumann < 0 || p->n_neumann > 8) throw Error(IFEM_E_BADPARAM, "ifem_scnsex_*: ifem_scns_params.n_neumann outside [0, 8]");
@@ -353,19 +291,9 @@ void check_params(const ifem_scns_params *p) {
 
 void apply_op(ifem_ctx *ctx, bool velocity, const double *x, double *y) {
   ExState &ex = ctx->ex;
-  const int64_t n = ctx->nUo;
-  KScope ks(ctx, IFEM_KC_OTHER, double(ctx->Auu.nnzb) * 12 + double(n) * 24 * (velocity ? ctx->dim : 1));
-  if (n == 0) return;
-  const dim3 g(grid_for(n * 16)), b(256);
-  const int64_t *rp = ctx->Auu.rowptr.p;
-  const int32_t *col = ctx->Auu.col.p;
-  hipStream_t s = ctx->stream;
-  if (!velocity) hipLaunchKernelGGL((k_ex_apply<1>), g, b, 0, s, n, rp, col, ex.ap.p, ex.dpn.p, (const uint8_t *)nullptr, x, y);
-  else {
-    const uint8_t *flag = ctx->has_c[1] ? ctx->is_c[1].p : nullptr;
-    if (ctx->dim == 2) hipLaunchKernelGGL((k_ex_apply<2>), g, b, 0, s, n, rp, col, ex.av.p, ex.dvn.p, flag, x, y);
-    else hipLaunchKernelGGL((k_ex_apply<3>), g, b, 0, s, n, rp, col, ex.av.p, ex.dvn.p, flag, x, y);
-  }
+  KScope ks(ctx, IFEM_KC_OTHER, double(ctx->Auu.nnzb) * 12 + double(ctx->nUo) * 24 * (velocity ? ctx->dim : 1));
+  if (!velocity) spmv_node_scalar(ctx, 1, ex.ap.p, nullptr, ex.dpn.p, x, y);
+  else spmv_node_scalar(ctx, ctx->dim, ex.av.p, ctx->has_c[1] ? ctx->is_c[1].p : nullptr, ex.dvn.p, x, y);
 }
 
 void fill_args(ifem_ctx *ctx, const ifem_scns_params *p, ExArgs &A) {
