@@ -242,6 +242,12 @@ typedef struct {
                             cycle skips the passes nothing reads (the zero fill of its solution vectors, the dead direction of the last
                             pre-smoothing step).  w, the Hessenberg arithmetic, the stopping test and the restart residual stay fp64.
                             0: fp64 bases around the conversions, the V-cycle with every pass (for comparing one build with itself) */
+  int32_t mg_lattice_u;  /* 1 (default): between two levels of the A_uu V-cycle that are both uniform boxes of Q2 velocity on one rank without
+                            hanging-node lines, with every axis either kept or halved, the velocity prolongation and restriction take their
+                            weights (products of 1, 3/8, 3/4, -1/8) from the lattice positions of the nodes instead of streaming the CSR tables
+                            of ifem_mg_attach (csrc/mg_lattice.hip).  The tables stay: every row of both is compared with the formula once per
+                            attach, exactly, and a pair with one differing row keeps them.  0: the CSR kernels everywhere (for comparing one
+                            build with itself).  (The field sits in front of the smoother pair: uu_patch_levels stays the last one.) */
   int32_t uu_smoother;   /* smoother of the A_uu V-cycle of IFEM_AINV_MG.  0 (default): Chebyshev on the inverse node blocks (node-block
                             Jacobi).  1: on every level that is a uniform box (mf_uniform in effect) of Q2 velocity on one rank without
                             hanging-node lines, the inverse node blocks are replaced by the additive vertex-patch sum B = sum_v R_v^T A_v^-1

@@ -109,6 +109,20 @@ enum { IFEM_TMG_PAD = 8 };
 int ifem_test_mg_transfer(ifem_ctx *ctx, int kind, int64_t n_rows, int64_t n_cols, const int64_t *ptr, const int32_t *col, const double *w,
                           const uint8_t *flag_in, const uint8_t *flag_out, const double *x, double *y);
 
+/* ifem_test_mg_lattice_transfer: one velocity transfer of the A_uu V-cycle between `fine` and the level attached below it (ifem_mg_attach with
+ * velocity tables), on host vectors that are float on the device, with the Dirichlet flags of the two levels (the constraint object of the last
+ * assembly of `fine`, object 0 before any; the coarse level is set to the same object, as the set-up of a cycle does).  No exchange is made: on
+ * several ranks every rank multiplies what it is given.
+ *   which 0: prolongation, x dim * local velocity nodes of the coarse level, y dim * owned velocity nodes of `fine` (+ IFEM_TMG_PAD)
+ *   which 1: restriction, x dim * owned nodes of `fine`, y dim * local nodes of the coarse level (+ IFEM_TMG_PAD)
+ *   path 0: the CSR kernels on the attached tables (mg_csr_mask + mg_csr_apply_nodes_f32)
+ *   path 1: what a cycle launches: the lattice-formula kernels (csrc/mg_lattice.hip) where the pair passed its checks and
+ *           ifem_tuning::mg_lattice_u is on, the CSR kernels elsewhere
+ * Decides the pair when that has not happened since the attach, as the set-up of a solve would.
+ * info = {state of the pair: 1 lattice formula / -1 keeps CSR, rows of P_u that differ from the formula, rows of R_u that do (-1 each: not
+ * compared, the pair was not eligible), 1: this call ran the lattice kernels / 0} */
+int ifem_test_mg_lattice_transfer(ifem_ctx *fine, int which, int path, const double *x, double *y, int64_t info[4]);
+
 /* ifem_test_mg_vec_kernel: the vector kernels of the two V-cycles on n entries (outputs: n + IFEM_TMG_PAD).  [f]: float on the device.
  *   IFEM_TMG_CHEB_INIT            out0 = coef[0] in0 in1                                  in0 = D^-1, in1 = r
  *   IFEM_TMG_CHEB_STEP            out0 += out2, out1 -= in1, out2 = coef[0] out2 + coef[1] in0 out1      in0 = D^-1, in1 = t; out0 / out1 / out2 = x / r / d,

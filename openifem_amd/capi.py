@@ -113,7 +113,7 @@ class Tuning(C.Structure):
     _fields_ = [("geo_cache", C.c_int32), ("xcd_swizzle", C.c_int32), ("asm_skip", C.c_int32), ("spmv_lanes", C.c_int32),
                 ("sm_lanes", C.c_int32), ("mf_f32", C.c_int32), ("tpp_operator", C.c_int32), ("spmv_pipe", C.c_int32), ("halo_overlap", C.c_int32),
                 ("asm3_variant", C.c_int32), ("cg_single_reduction", C.c_int32), ("asm3_cpb", C.c_int32), ("tpp_milu_permille", C.c_int32), ("tpp_ilu_order", C.c_int64), ("basis_pad", C.c_int64), ("tpp_tri_sweeps", C.c_int32), ("uu_row_order", C.c_int32), ("eig_steps", C.c_int32), ("vcycle_graph_cells", C.c_int32),
-                ("scns_pc", C.c_int32), ("pvv_sweeps", C.c_int32), ("b2pp_sweeps", C.c_int32), ("scns_inner_reorth", C.c_int32), ("scns_inner_left", C.c_int32), ("scns_graph", C.c_int32), ("stored_uu", C.c_int32), ("mf_uniform", C.c_int32), ("inner_f32", C.c_int32), ("uu_smoother", C.c_int32), ("uu_patch_levels", C.c_int32)]
+                ("scns_pc", C.c_int32), ("pvv_sweeps", C.c_int32), ("b2pp_sweeps", C.c_int32), ("scns_inner_reorth", C.c_int32), ("scns_inner_left", C.c_int32), ("scns_graph", C.c_int32), ("stored_uu", C.c_int32), ("mf_uniform", C.c_int32), ("inner_f32", C.c_int32), ("mg_lattice_u", C.c_int32), ("uu_smoother", C.c_int32), ("uu_patch_levels", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -156,7 +156,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
            "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply", "ifem_test_sm_solve",
-           "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel",
+           "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel", "ifem_test_mg_lattice_transfer",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr",
            "ifem_scnsex_setup", "ifem_scnsex_assemble_rhs", "ifem_scnsex_solve", "ifem_scnsex_step", "ifem_scnsex_export_csr"]
@@ -269,6 +269,7 @@ def load():
     L.ifem_test_sm_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_b_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_mg_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7
+    L.ifem_test_mg_lattice_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_test_mg_vec_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7
     L.ifem_true_residual.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ifem_kprof_begin.argtypes = [C.c_void_p]
@@ -657,6 +658,16 @@ class Context:
         self._chk(self.L.ifem_test_mg_transfer(self.h, kind, n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(w), _ptr(flag_in), _ptr(flag_out),
                                                _ptr(x), _ptr(y)))
         return y
+
+    def test_mg_lattice_transfer(self, which, path, x, n_out_nodes):
+        """(y, info): one velocity transfer of the A_uu V-cycle between this level and the one attached below it; which 0 prolongation (x: dim
+        values per coarse node), 1 restriction (x: dim per node of this level); path 0 the CSR kernels, 1 what a cycle launches (the lattice
+        formula where the pair qualifies).  n_out_nodes: velocity nodes of the level written to.  y comes back whole, TMG_PAD guard entries included.
+        info = [state of the pair, P_u rows off the formula, R_u rows off it, 1 when the lattice kernels ran] -- ifem_test_mg_lattice_transfer"""
+        x = np.ascontiguousarray(x, float)
+        y, info = np.zeros(self.dim * n_out_nodes + TMG_PAD), np.zeros(4, np.int64)
+        self._chk(self.L.ifem_test_mg_lattice_transfer(self.h, which, path, _ptr(x), _ptr(y), _ptr(info)))
+        return y, info
 
     def test_mg_vec_kernel(self, op, n, m=0, coef=None, idx=None, in0=None, in1=None, out0=None, out1=None, out2=None):
         """one host launcher of the multigrid vector kernels (TMG_*) on C-contiguous float64 host arrays (idx: int32); the out arrays hold

@@ -193,7 +193,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
 void ifem_default_tuning(ifem_tuning *t) {
   t->geo_cache = 1; t->xcd_swizzle = 1; t->asm_skip = 0; t->spmv_lanes = 32; t->sm_lanes = 32; t->mf_f32 = 1;
   t->tpp_operator = 0; t->spmv_pipe = 1; t->halo_overlap = 1; t->asm3_variant = 0; t->cg_single_reduction = 1; t->asm3_cpb = 2; t->tpp_milu_permille = 950; t->tpp_ilu_order = 2; t->basis_pad = 32 * 33; t->tpp_tri_sweeps = 0; t->uu_row_order = 1; t->eig_steps = 0; t->vcycle_graph_cells = 262144;
-  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->uu_smoother = 0; t->uu_patch_levels = 0;
+  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->mg_lattice_u = 1; t->uu_smoother = 0; t->uu_patch_levels = 0;
 }
 
 int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
@@ -456,6 +456,7 @@ int ifem_mg_attach(ifem_ctx *fine, ifem_ctx *coarse, const ifem_mg_transfer *t) 
   fine->mg_Pu.n_rows = fine->mg_Ru.n_rows = 0;
   // the packed transfer entries (columns, weights and drop bits baked in) and the captured cycles belong to the tables that are replaced
   fine->mg_mask_key[0] = fine->mg_mask_key[1] = -1;
+  fine->mg_lattice_u = MgLatticeU(); // decided anew for the new tables (mg_lattice.hip::mg_lattice_u_setup)
   ++fine->graph_epoch; ++coarse->graph_epoch;
   fine->vc_graph.destroy(); fine->sm_graph.destroy();
   fine->vc_graph.armed = fine->sm_graph.armed = false; fine->vc_graph.key.clear(); fine->sm_graph.key.clear();
@@ -1233,6 +1234,31 @@ int ifem_test_mg_transfer(ifem_ctx *ctx, int kind, int64_t n_rows, int64_t n_col
     dy.close(y, s);
   }
   IFEM_HIP_CHECK(hipGetLastError());
+  IFEM_API_END
+}
+
+int ifem_test_mg_lattice_transfer(ifem_ctx *fine, int which, int path, const double *x, double *y, int64_t info[4]) {
+  IFEM_API_BEGIN
+  if (!fine || which < 0 || which > 1 || path < 0 || path > 1 || !x || !y || !info) throw Error(IFEM_E_BADPARAM, "ifem_test_mg_lattice_transfer: which 0 / 1, path 0 / 1, x, y and info");
+  ifem_ctx *cc = fine->mg_coarse;
+  if (!cc || fine->mg_Pu.n_rows != fine->nUo || fine->nUo <= 0 || fine->mg_Ru.n_rows != cc->nUl)
+    throw Error(IFEM_E_BADPARAM, "ifem_test_mg_lattice_transfer: a level with velocity transfers to an attached coarser level");
+  hipStream_t s = fine->stream;
+  const size_t dim = size_t(fine->dim);
+  cc->asm_constraint_set = fine->asm_constraint_set; // as the set-up of a cycle leaves the chain
+  mg_transfer_u_setup(fine, fine->asm_constraint_set, 0);
+  const bool prolong = which == 0;
+  const size_t n_in = (prolong ? size_t(cc->nUl) : size_t(fine->nUo)) * dim, n_out = (prolong ? size_t(fine->nUo) : size_t(cc->nUl)) * dim;
+  DBuf<float> dx;
+  upload_as(dx, x, n_in, s);
+  GuardedOut<float> dy;
+  dy.open(nullptr, n_out, false, s);
+  mg_transfer_u(fine, prolong, dx.p, dy.d.p, /*csr_only=*/path == 0);
+  IFEM_HIP_CHECK(hipStreamSynchronize(s));
+  dy.close(y, s);
+  IFEM_HIP_CHECK(hipGetLastError());
+  info[0] = fine->mg_lattice_u.state; info[1] = fine->mg_lattice_u.bad_p; info[2] = fine->mg_lattice_u.bad_r;
+  info[3] = (path == 1 && mg_lattice_u_active(fine)) ? 1 : 0;
   IFEM_API_END
 }
 

@@ -482,6 +482,18 @@ struct ULattice {
   DBuf<int32_t> lattice_of_node; // its inverse
 };
 
+// The velocity transfers towards the next coarser level from the lattice weight formula (mg_lattice.hip, mg_lattice.hpp) instead of the CSR
+// tables, kept by the FINE level of the pair.  Decided once per ifem_mg_attach of the pair, at solve set-up (mg_lattice_u_setup): one rank, no
+// replica, no hanging-node line, Q2 velocity, both levels full lattices (ULattice), every axis kept or halved, and the exact checks against
+// mg_inj_u and against every row of mg_Pu / mg_Ru.  Same `state` protocol as PLattice; -1 keeps the CSR kernels.  The kernels read the two
+// levels through ifem_ctx::mgl_map.
+struct MgLatticeU {
+  int state = 0;
+  bool halved[3] = {false, false, false}; // the pair halves the cells of this axis (n_f = 2 n_c - 1); false: n_f == n_c
+  int n_f[3] = {1, 1, 1}, n_c[3] = {1, 1, 1}; // velocity lattice points per axis of the two levels
+  int64_t bad_p = -1, bad_r = -1, bad_inj = -1; // rows of P_u / R_u, coarse nodes of the injection that are not the formula's (-1: not looked at)
+};
+
 // y = B x and y = B^T x from stencil tables over the two lattices (bb_stencil.hip).  A B row at pressure point j couples the velocity points
 // within +-deg of deg j (times dim components); a B^T row at velocity point i the at most 3^dim pressure points j with |i - deg j| <= deg.
 // Each block has its own tables, read off its own assembled values (with ifem_tuning::geo_cache = 2 both are masked copies: neither is assumed
@@ -572,6 +584,9 @@ struct ifem_ctx {
   ifem::MgCsr mg_Pp, mg_Rp, mg_Pu, mg_Ru;
   ifem::DBuf<int32_t> mg_inj_u; // [nUo of the coarse level] coincident owned velocity node of this level
   ifem::DBuf<uint8_t> mg_Pu_mask, mg_Ru_mask; // per weight 8 bytes: {column | components dropped by the Dirichlet flags of the two levels << 29, weight as float} (mg.hip::mg_csr_mask)
+  ifem::DBuf<uint32_t> mgl_map;               // [velocity lattice] node | constrained components << 29 for the set mgl_map_key stands for: what the lattice transfer kernels read a level through (mg_lattice.hip)
+  int64_t mgl_map_key = -1;
+  ifem::MgLatticeU mg_lattice_u;              // the velocity transfers to mg_coarse from the lattice formula, where the pair is one (mg_lattice.hip)
   bool uu_is_stored = true;                   // the last full assembly scattered A_uu (false: ifem_tuning::stored_uu = 0, the matrix-free path)
   bool inhom_any[2] = {false, false};         // constraint object `which` carries a non-zero inhomogeneity somewhere (any rank)
   uint64_t graph_epoch = 0;                   // bumped by ifem_set_tuning / ifem_set_profiling / ifem_mg_attach: solver.hip::graph_run adds it to every replay key

@@ -270,6 +270,15 @@ void mg_csr_mask(ifem_ctx *ctx, const MgCsr &M, const uint8_t *flag_in, const ui
 void mg_inject_nodes(ifem_ctx *ctx, int64_t n_nodes, const int32_t *inj, const double *fine, double *coarse);
 void cheb_init_block_f32(ifem_ctx *ctx, double c0, const float *r, float *d);
 void mg_csr_apply_nodes_f32(ifem_ctx *ctx, const MgCsr &M, const float *x, const DBuf<uint8_t> &mask, float *y);
+// mg_lattice.hip: the velocity transfers of the pair (c, c->mg_coarse) of the A_uu V-cycle.  mg_transfer_u_setup: set-up time only (allocates,
+// synchronises): the packed CSR entries for the constrained-dof set cs of the two levels, and (mg_lattice_u_setup, once per ifem_mg_attach) the
+// decision whether the pair may take its weights from the lattice formula.  mg_transfer_u: what the cycle launches (prolong: coarse x -> fine y,
+// else fine x -> coarse y; no allocation, capture-safe): the lattice kernels where the pair passed and ifem_tuning::mg_lattice_u is on,
+// mg_csr_apply_nodes_f32 elsewhere or with csr_only
+void mg_transfer_u_setup(ifem_ctx *c, int cs, int verbose);
+void mg_lattice_u_setup(ifem_ctx *c, int verbose);
+inline bool mg_lattice_u_active(const ifem_ctx *c) { return c->mg_lattice_u.state == 1 && c->tune.mg_lattice_u != 0; }
+void mg_transfer_u(ifem_ctx *c, bool prolong, const float *x, float *y, bool csr_only = false);
 void v_cvt_d2f(ifem_ctx *ctx, int64_t n, const double *x, float *y);
 void v_cvt_f2d(ifem_ctx *ctx, int64_t n, const float *x, double *y);
 void v_axpy_f32v(ifem_ctx *ctx, int64_t n, float a, const float *x, float *y);

@@ -285,6 +285,8 @@ static void uu_level_key(ifem_ctx *lc, std::vector<uint64_t> &key) {
   key_ptr(key, lc->bjac_f32.p); key_ptr(key, lc->mf_eval.p); key_ptr(key, lc->mf_ycell.p); key_ptr(key, lc->mg_Ru_mask.p); key_ptr(key, lc->mg_Pu_mask.p);
   key_ptr(key, lc->has_c[lc->asm_constraint_set] ? lc->is_c[lc->asm_constraint_set].p : nullptr);
   key.push_back(uint64_t(lc->nUo)); key.push_back(uint64_t(lc->n_cells)); key.push_back(uint64_t(lc->mf_noconv)); key.push_back(uint64_t(lc->tune.xcd_swizzle));
+  // which transfer kernels the level launches towards the next one, and the maps of the lattice ones (mg_lattice.hip)
+  key.push_back(uint64_t(mg_lattice_u_active(lc))); key_ptr(key, lc->mgl_map.p); key_ptr(key, lc->u_lattice.lattice_of_node.p);
   // everything else the captured launches are made of: the epoch moves with ifem_set_tuning / ifem_set_profiling / ifem_mg_attach
   key.push_back(lc->graph_epoch); key.push_back(uint64_t(lc->tune.mf_f32));
   key.push_back(uint64_t(mf_takes_uniform(lc))); for (double hd : lc->mf_h) key_f64(key, hd); // which cell kernels, and their constants
@@ -643,17 +645,8 @@ static void mg_uu_setup(MgUu &M, bool force_bounds = false) {
       uu_block_diag_mf(c);
       c->uu_mg_version = f0->asm_version;
     }
-    if (l + 1 < M.L.size()) { // transfer masks towards the next level: functions of the two constrained-dof sets
-      ifem_ctx *cc = M.L[l + 1].ctx;
-      const int cs = f0->asm_constraint_set;
-      const int64_t key[2] = {c->flag_id[cs], cc->flag_id[cs]};
-      if (c->mg_Pu_mask.n != c->mg_Pu.col.n * 8 || c->mg_mask_key[0] != key[0] || c->mg_mask_key[1] != key[1]) {
-        const uint8_t *ff = c->has_c[cs] ? c->is_c[cs].p : nullptr, *fc = cc->has_c[cs] ? cc->is_c[cs].p : nullptr;
-        mg_csr_mask(c, c->mg_Ru, ff, fc, c->mg_Ru_mask); // rows: local coarse nodes, columns: owned fine nodes
-        mg_csr_mask(c, c->mg_Pu, fc, ff, c->mg_Pu_mask); // rows: owned fine nodes, columns: local coarse nodes
-        c->mg_mask_key[0] = key[0]; c->mg_mask_key[1] = key[1];
-      }
-    }
+    // transfers towards the next level: the packed entries (functions of the two constrained-dof sets) and the choice of the lattice kernels
+    if (l + 1 < M.L.size()) mg_transfer_u_setup(c, f0->asm_constraint_set, S.o->verbose);
     // the smoother's B of this level: the inverse node blocks, or (ifem_tuning::uu_smoother = 1 on an eligible level) the vertex-patch
     // sum of patch.hip, whose tables are made here, outside of any captured cycle.  The bound below is one of B A_uu: each kind keeps its own
     // (ctx.hpp::UuBound)
@@ -752,7 +745,7 @@ static void mg_uu_vcycle(MgUu &M, size_t l) {
   mg_uu_smooth(M, l, mg_uu_sweep(M, l), x, r, pre);
   SolveState &Sc = M.L[l + 1];
   ifem_ctx *cc = Sc.ctx;
-  mg_csr_apply_nodes_f32(c, c->mg_Ru, r, c->mg_Ru_mask, cc->mguf_vec[0].p);
+  mg_transfer_u(c, /*prolong=*/false, r, cc->mguf_vec[0].p);
   // partial restrictions -> the coarse residual: ghost rows to their owners, or (replicated coarse level: every rank holds all rows) the
   // sum over the ranks; from there down nothing is exchanged and the prolongation reads the replica directly
   if (c->mg_replica) allreduce_sum_vec_f32(c, cc->mguf_vec[0].p, int64_t(cc->dim) * cc->nUo, cc->mguf_vec[4].p);
@@ -760,7 +753,7 @@ static void mg_uu_vcycle(MgUu &M, size_t l) {
   mg_uu_vcycle(M, l + 1);
   halo_exchange_f32(cc, cc->mguf_vec[1].p);
   float *e = c->mguf_vec[4].p;
-  mg_csr_apply_nodes_f32(c, c->mg_Pu, cc->mguf_vec[1].p, c->mg_Pu_mask, e);
+  mg_transfer_u(c, /*prolong=*/true, cc->mguf_vec[1].p, e);
   MfFuseT<float> f; // x += e; r -= A e; d = (1/theta) B r: the first direction of the post-smoothing sweep
   f.mode = 3; f.xs = x; f.r = r; f.d = c->mguf_vec[2].p; f.b = Cheb(mg_uu_sweep(M, l, true)).c0();
   const bool dir_follows = smoother_fuse_mode(c, f.mode);
