@@ -25,6 +25,7 @@
  */
 #ifndef IFEM_HIP_H
 #define IFEM_HIP_H
+#include <float.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -496,9 +497,13 @@ int ifem_scns_newton_step(ifem_ctx *ctx, const ifem_scns_params *p, const ifem_s
  * otherwise.
  * Partitioned contexts work as for SCnsIM (owner-computes rows, halo refresh of nu~ and of the Krylov vectors, per-rank ILU(0) of the
  * owned x owned block); every rank passes ALL wall points and the constraint lines of its owned and ghost nodes.
- * Scope: contexts without hanging-node lines (with them: IFEM_E_BADPARAM); no FSI wall function
- * (update_moving_wall_distance, update_boundary_condition, get_shear_velocity), no refinement transfer, no checkpoint
- * payload. */
+ * The wall function at a moving FSI wall (update_moving_wall_distance, update_boundary_condition, get_shear_velocity and the
+ * shear-velocity part of FSI::find_solid_bc) is the group of entry points around ifem_sa_wall below.
+ * A SECOND deliberate choice, there: mpi_fsi.cpp:807 computes image_point = vertex + image_distance * normal and never uses it --
+ * the interpolator of :810-814 is built at the solid vertex itself.  ifem_sa_wall::sample_at_image_point = 0 samples the fluid
+ * velocity at the vertex, as the reference is written; 1 samples it at the image point, the evident intent.
+ * Scope: contexts without hanging-node lines (with them: IFEM_E_BADPARAM); the wall-function entry points additionally refuse
+ * partitioned contexts; no refinement transfer, no checkpoint payload. */
 typedef struct {
   double viscosity, rho, dt; /* parameters.viscosity (laminar mu), fluid_rho, time step */
 } ifem_sa_params;
@@ -530,6 +535,63 @@ int ifem_sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double
 /* test hook: the assembled matrix as CSR over the nodes (two-call protocol of ifem_export_csr: rowptr [n_unodes_owned + 1]
  * first with col = val = NULL) */
 int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val);
+
+/* ---- the wall function of the model at a moving FSI wall: what MPI::FSI does between its fluid-side inputs in every time step
+ * (mpi_fsi.cpp:782-844, 655-660, 1199-1203; mpi_spalart_allmaras.cpp:17-280, 709-719).  The solid-side geometry (which vertices
+ * lie on the wall, their normals, the 2D boundary edges) is handed in by the caller; positions come from the solid of
+ * ifem_fsi_set_solid at its CURRENT position, so a moved solid needs no new ifem_sa_set_moving_wall as long as its vertex count
+ * stays; the normals are those of the call (a wall that turns is set again, which resets the shear velocities).  Scope: SINGLE-RANK contexts without hanging-node lines; a partitioned context is IFEM_E_BADPARAM with a message, before
+ * any launch.  (The reference sums per-rank shear velocities that treat "not found" as 0, mpi_fsi.cpp:836-839, 845-850; the ghost
+ * layer of a partitioned context here would find, and count, a point twice.) */
+typedef struct {
+  int32_t n_vertices;        /* solid_boundary_vertices.size(); position i = index into shear_velocities (mpi_fsi.cpp:972-1021) */
+  const int32_t *vertex;     /* [n_vertices] index into ifem_fsi_solid::vertices (current position) */
+  const double  *normal;     /* [n_vertices][dim] vertex normal = mean of the adjacent boundary-face normals (:795-800); solid-side, given by the caller */
+  int32_t n_edges;           /* dim 2: solid_boundaries; dim 3: 0 */
+  const int32_t *edge;       /* [n_edges][2] POSITIONS in `vertex` of face->vertex(0), ->vertex(1); dim 3: NULL */
+  double image_distance, wall_function_distance;   /* "Wall function image distance", "Wall function effective distance" of the .prm */
+  int32_t sample_at_image_point; /* 0: velocity sampled at the solid vertex, as the reference is written (:810-814 builds the
+                                    interpolator at the vertex; image_point of :807 is never used); 1: at vertex + image_distance * normal */
+} ifem_sa_wall;
+/* the moving distance of a node that has none ("moving_wall_distance = {}", mpi_spalart_allmaras.cpp:427): what
+ * ifem_sa_get_moving_wall returns before the first ifem_sa_update_moving_wall_distance */
+#define IFEM_SA_NO_MOVING_WALL DBL_MAX
+/* stores the lists on the device, shear_velocities.reinit (all 0), moving distance absent and y+ = 201.0 (:427-430).  NULL removes the
+ * moving wall: the context is then as if none had ever been set (the assembly reads the fixed distance again).  Needs the solid of
+ * ifem_fsi_set_solid; vertex / edge entries out of range: IFEM_E_BADPARAM. */
+int ifem_sa_set_moving_wall(ifem_ctx *ctx, const ifem_sa_wall *wall);
+/* the shear-velocity part of FSI::find_solid_bc (mpi_fsi.cpp:782-844): for every wall vertex the sample point is located in the fluid
+ * mesh and IFEM_VEC_PRESENT interpolated there by the code path of ifem_fsi_fluid_at_points; tangential speed |u - (n.u) n|; u_tau by
+ * get_shear_velocity with the vertex's previous u_tau as initial guess.  A point in no cell gives 0.  host_out [n_vertices] may be NULL */
+int ifem_sa_update_shear_velocity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
+/* overwrites shear_velocities (utau [n_vertices], by position in ifem_sa_wall::vertex): a caller that keeps the vector itself, as
+ * update_moving_wall_distance of the reference takes it as an argument (mpi_spalart_allmaras.cpp:17-23), or restores it */
+int ifem_sa_set_shear_velocities(ifem_ctx *ctx, const double *utau);
+/* SpalartAllmaras::get_shear_velocity (mpi_spalart_allmaras.cpp:218-280), a host function that needs no GPU: 0 for |vel| < 1e-10,
+ * vel / sqrt(vel d / nu) in the sublayer vel d / nu < sqrt(5), else at most 30 Newton steps on u_tau u+(u_tau d / nu) = vel from
+ * max(init_guess, 5 nu / d), stopping at |delta| < 1e-2 |u_tau| */
+int ifem_sa_get_shear_velocity(const ifem_sa_params *p, double image_distance, double vel, double init_guess, double *out);
+/* SpalartAllmaras::update_moving_wall_distance (:17-127) for every local node x, brute force: in 2D first the edges in list order (an
+ * edge (v1, v2) is a candidate iff (v1-x).(v1-v2) > 0 and (v2-x).(v2-v1) > 0; ratio r = (v1-x).(v1-v2) / |v2-v1|^2, distance
+ * |x - (v1 + r (v2-v1))|, u_tau = u_tau1 + (u_tau2 - u_tau1) r), then in 2D and 3D the vertices in ascending SOLID VERTEX ID (the order of
+ * the reference's std::map of vertex iterators).  A candidate replaces the minimum only if strictly smaller.  Result d_mov and
+ * y+ = d_mov u_tau(best) / (mu / rho); host_d, host_yplus [n_unodes_local] may be NULL.  From this call on ifem_sa_assemble uses
+ * d(node) = d_mov < d_fixed ? d_mov : d_fixed (:711-719); a later ifem_sa_set_wall_points refreshes it. */
+int ifem_sa_update_moving_wall_distance(ifem_ctx *ctx, const ifem_sa_params *p, double *host_d, double *host_yplus);
+/* read-back hook: d_mov (IFEM_SA_NO_MOVING_WALL while absent) and y+ (201 before the first update), [n_unodes_local], either may be NULL */
+int ifem_sa_get_moving_wall(ifem_ctx *ctx, double *host_d, double *host_yplus);
+/* SpalartAllmaras::update_boundary_condition(first_step) (:130-215) on the two constraint objects of ifem_sa_set_constraints, which the
+ * caller has re-made first (fluid_solver.make_constraints(), mpi_fsi.cpp:1192).  !first_step: the nonzero object becomes a copy of the
+ * zero object with all inhomogeneities 0.  A node QUALIFIES iff (d_mov, or 2.0 while absent) < wall_function_distance and y+ < 200.  A node
+ * touched by an indicator cell gets the line -nu~_present unless it qualifies and its first touching cell is not an indicator cell; that
+ * node and every other qualifying node gets kappa y+ mu / rho - nu~_present (kappa = 0.41); the zero object gets the same nodes with 0.
+ * First touching cell: smallest cell_order[c] (NULL: the local cell index), as in ifem_fsi_find_fluid_bc.  The lines are merged with
+ * right_object_wins: they replace a boundary line on the same node.  n_lines (may be NULL): lines added per object.  Without a cell
+ * indicator: the reference's "No available indicator function for SA model!" as IFEM_E_BADPARAM. */
+int ifem_sa_update_boundary_condition(ifem_ctx *ctx, const ifem_sa_params *p, int first_step, const int32_t *cell_order, int64_t *n_lines);
+/* read-back hook like ifem_get_constraints: flags and inhomogeneities of the model's constraint object `which` over the local nodes
+ * [n_unodes_local] (either pointer may be NULL) */
+int ifem_sa_get_constraints(ifem_ctx *ctx, int which, uint8_t *flags, double *inhom);
 
 /* ---- Fluid::MPI::SCnsEX (source/mpi_scnsex.cpp): the explicit split solver of the slightly compressible equations, the reference's
  * solver for acoustics (tests/acoustic_duct_wave_mpi_scnsex).  Velocity and pressure have the SAME degree and live on the same nodes

@@ -75,6 +75,22 @@ class SaParams(C.Structure):
 SA_PRESENT, SA_EVAL, SA_UPDATE, SA_RHS = range(4)  # IFEM_SA_*
 
 
+class SaWall(C.Structure):
+    """ifem_sa_wall: the solid-side description of a moving wall.  SaWall.make keeps the arrays alive that the pointers name"""
+    _fields_ = [("n_vertices", C.c_int32), ("vertex", C.c_void_p), ("normal", C.c_void_p), ("n_edges", C.c_int32), ("edge", C.c_void_p),
+                ("image_distance", C.c_double), ("wall_function_distance", C.c_double), ("sample_at_image_point", C.c_int32)]
+
+    @classmethod
+    def make(cls, vertex, normal, edges, image_distance, wall_function_distance, sample_at_image_point=False):
+        vertex = np.ascontiguousarray(vertex, np.int32)
+        normal = np.ascontiguousarray(normal, float).reshape(len(vertex), -1)
+        edges = None if edges is None or len(edges) == 0 else np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        w = cls(len(vertex), vertex.ctypes.data, normal.ctypes.data, 0 if edges is None else len(edges), None if edges is None else edges.ctypes.data,
+                image_distance, wall_function_distance, int(sample_at_image_point))
+        w.keep = (vertex, normal, edges)
+        return w
+
+
 class ScnsexStats(C.Structure):
     """ifem_scnsex_stats"""
     _fields_ = [("outer_iterations", C.c_uint32), ("vel_iters", C.c_uint32), ("pre_iters", C.c_uint32), ("reserved_", C.c_uint32),
@@ -160,6 +176,12 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr",
            "ifem_scnsex_setup", "ifem_scnsex_assemble_rhs", "ifem_scnsex_solve", "ifem_scnsex_step", "ifem_scnsex_export_csr"]
+
+# the wall function of the Spalart-Allmaras model at a moving FSI wall (csrc/sa_wall.hip).  Kept apart from EXPORTS, whose "ifem_sa_" entries
+# are the entry points of csrc/sa.hip; load() and __graft_entry__.build() require both lists
+EXPORTS_SA_WALL = ["ifem_sa_set_moving_wall", "ifem_sa_set_shear_velocities", "ifem_sa_update_shear_velocity", "ifem_sa_get_shear_velocity", "ifem_sa_update_moving_wall_distance",
+                   "ifem_sa_get_moving_wall", "ifem_sa_update_boundary_condition", "ifem_sa_get_constraints"]
+SA_NO_MOVING_WALL = np.finfo(float).max  # IFEM_SA_NO_MOVING_WALL
 
 # ifem_solver_opts::sm_mg: plain CG | multigrid-preconditioned CG (the default) | the fast-diagonalisation solve where the level qualifies, SM_MG elsewhere
 SM_CG, SM_MG, SM_DIRECT = 0, 1, 2
@@ -293,6 +315,14 @@ def load():
     L.ifem_sa_newton_step.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_int, C.c_double, C.c_int, C.c_void_p]
     L.ifem_sa_update_eddy_viscosity.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_void_p]
     L.ifem_sa_export_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_sa_set_moving_wall.argtypes = [C.c_void_p, C.POINTER(SaWall)]
+    L.ifem_sa_update_shear_velocity.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_void_p]
+    L.ifem_sa_get_shear_velocity.argtypes = [C.POINTER(SaParams), C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    L.ifem_sa_update_moving_wall_distance.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_void_p, C.c_void_p]
+    L.ifem_sa_get_moving_wall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_sa_update_boundary_condition.argtypes = [C.c_void_p, C.POINTER(SaParams), C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
+    L.ifem_sa_get_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.ifem_sa_set_shear_velocities.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_scnsex_setup.argtypes = [C.c_void_p, C.POINTER(ScnsParams)]
     L.ifem_scnsex_assemble_rhs.argtypes = [C.c_void_p, C.POINTER(ScnsParams), C.c_int]
     L.ifem_scnsex_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -302,6 +332,16 @@ def load():
     L.ifem_abi_sizeof.restype = C.c_int64
     _lib = L
     return L
+
+
+def sa_get_shear_velocity(params, image_distance, vel, init_guess):
+    """SpalartAllmaras::get_shear_velocity on the host (ifem_sa_get_shear_velocity): needs no GPU"""
+    L = load()
+    out = C.c_double(0)
+    rc = L.ifem_sa_get_shear_velocity(C.byref(params), image_distance, vel, init_guess, C.byref(out))
+    if rc < 0:
+        raise IfemError(rc, L.ifem_last_error().decode())
+    return out.value
 
 
 def _ptr(a):
@@ -327,6 +367,7 @@ class CommStats(C.Structure):  # ifem_comm_stats
 
 ABI_STRUCTS = [MeshDesc, Partition, InsParams, SolverOpts, SolveStats, ScnsParams, Timing, Tuning, MgTransfer, FsiSolid, FsiStats,
                CommStats, KprofEntry, SaParams]
+ABI_SA_WALL = 65  # ifem_abi_sizeof(65) = sizeof(ifem_sa_wall), beside it
 ABI_SCNSEX_STATS = 64  # ifem_abi_sizeof(64) = sizeof(ifem_scnsex_stats): outside the contiguous list, whose end callers find by its first -1
 
 
@@ -899,6 +940,47 @@ class Context:
 
     def sa_export_csr(self):
         return self._export_node_csr(self.L.ifem_sa_export_csr)
+
+    # ---- the model's wall function at a moving FSI wall (mpi_fsi.cpp:782-844, mpi_spalart_allmaras.cpp:17-280)
+    def sa_set_moving_wall(self, wall):
+        """wall: an SaWall (SaWall.make) or None to remove the moving wall"""
+        self._chk(self.L.ifem_sa_set_moving_wall(self.h, None if wall is None else C.byref(wall)))
+        self._sa_n_wall = 0 if wall is None else wall.n_vertices
+
+    def sa_update_shear_velocity(self, params):
+        out = np.zeros(getattr(self, "_sa_n_wall", 0))
+        self._chk(self.L.ifem_sa_update_shear_velocity(self.h, C.byref(params), _ptr(out)))
+        return out
+
+    def sa_set_shear_velocities(self, utau):
+        """overwrite shear_velocities, by position in the wall's vertex list"""
+        utau = np.ascontiguousarray(utau, float)
+        assert len(utau) == getattr(self, "_sa_n_wall", 0)
+        self._chk(self.L.ifem_sa_set_shear_velocities(self.h, _ptr(utau)))
+
+    def sa_update_moving_wall_distance(self, params):
+        """(d_mov, y+) over the local nodes"""
+        d, yp = np.zeros(self.n_u // self.dim), np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_update_moving_wall_distance(self.h, C.byref(params), _ptr(d), _ptr(yp)))
+        return d, yp
+
+    def sa_moving_wall(self):
+        """(d_mov, y+) as they stand: SA_NO_MOVING_WALL and 201 before the first update"""
+        d, yp = np.zeros(self.n_u // self.dim), np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_get_moving_wall(self.h, _ptr(d), _ptr(yp)))
+        return d, yp
+
+    def sa_update_boundary_condition(self, params, first_step, cell_order=None):
+        """returns the number of lines merged into each constraint object"""
+        order = None if cell_order is None else np.ascontiguousarray(cell_order, np.int32)
+        n = C.c_int64(0)
+        self._chk(self.L.ifem_sa_update_boundary_condition(self.h, C.byref(params), int(first_step), _ptr(order), C.byref(n)))
+        return n.value
+
+    def sa_get_constraints(self, which):
+        flags, vals = np.zeros(self.n_u // self.dim, np.uint8), np.zeros(self.n_u // self.dim)
+        self._chk(self.L.ifem_sa_get_constraints(self.h, which, _ptr(flags), _ptr(vals)))
+        return flags, vals
 
     # ---- Fluid::MPI::SCnsEX on scalar node matrices (mpi_scnsex.cpp); velocity and pressure on the same nodes
     def scnsex_setup(self, params):

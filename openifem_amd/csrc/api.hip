@@ -10,6 +10,7 @@
 #include "../../include/ifem_hip_testing.h"
 #include "ctx.hpp"
 #include "kernels.hpp"
+#include "sa_wall_function.hpp"
 
 using namespace ifem;
 
@@ -165,6 +166,7 @@ int64_t ifem_abi_sizeof(int which) {
   case 12: return sizeof(ifem_kprof_entry);
   case 13: return sizeof(ifem_sa_params);
   case 64: return sizeof(ifem_scnsex_stats);
+  case 65: return sizeof(ifem_sa_wall);
   default: return -1;
   }
 }
@@ -871,6 +873,63 @@ int ifem_sa_export_csr(ifem_ctx *ctx, int64_t *rowptr, int32_t *col, double *val
   sa_check(ctx);
   if (!rowptr) throw Error(IFEM_E_BADPARAM, "ifem_sa_export_csr: no rowptr array");
   export_node_csr(ctx, ctx->sa.val, ctx->sa.assembled, "ifem_sa_export_csr called before ifem_sa_assemble", rowptr, col, val);
+  IFEM_API_END
+}
+
+// ---- the wall function at a moving FSI wall (sa_wall.hip)
+int ifem_sa_set_moving_wall(ifem_ctx *ctx, const ifem_sa_wall *wall) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_set_moving_wall(ctx, wall);
+  IFEM_API_END
+}
+
+int ifem_sa_update_shear_velocity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_update_shear_velocity(ctx, p, host_out);
+  IFEM_API_END
+}
+
+int ifem_sa_get_shear_velocity(const ifem_sa_params *p, double image_distance, double vel, double init_guess, double *out) {
+  IFEM_API_BEGIN
+  if (!p || !out || !(p->viscosity > 0) || !(p->rho > 0)) throw Error(IFEM_E_BADPARAM, "ifem_sa_get_shear_velocity: bad ifem_sa_params or no output");
+  *out = sa_shear_velocity(p->viscosity / p->rho, image_distance, vel, init_guess);
+  IFEM_API_END
+}
+
+int ifem_sa_update_moving_wall_distance(ifem_ctx *ctx, const ifem_sa_params *p, double *host_d, double *host_yplus) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_update_moving_wall_distance(ctx, p, host_d, host_yplus);
+  IFEM_API_END
+}
+
+int ifem_sa_get_moving_wall(ifem_ctx *ctx, double *host_d, double *host_yplus) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_get_moving_wall(ctx, host_d, host_yplus);
+  IFEM_API_END
+}
+
+int ifem_sa_update_boundary_condition(ifem_ctx *ctx, const ifem_sa_params *p, int first_step, const int32_t *cell_order, int64_t *n_lines) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_update_boundary_condition(ctx, p, first_step, cell_order, n_lines);
+  IFEM_API_END
+}
+
+int ifem_sa_get_constraints(ifem_ctx *ctx, int which, uint8_t *flags, double *inhom) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_get_constraints(ctx, which, flags, inhom);
+  IFEM_API_END
+}
+
+int ifem_sa_set_shear_velocities(ifem_ctx *ctx, const double *utau) {
+  IFEM_API_BEGIN
+  need_ctx(ctx, "ifem_sa_*");
+  sa_set_shear_velocities(ctx, utau);
   IFEM_API_END
 }
 

@@ -386,6 +386,35 @@ struct SaState {
   DBuf<double> xext;                // several ranks: ghost-extended operator input [nUl]
   bool assembled = false, ilu_ok = false;
   int64_t val_order = -1, ilu_order = -1; // PlanarCsr::order_version of A_uu the values were scattered / the ILU(0) was analysed for
+  // the wall function at a moving FSI wall (sa_wall.hip); everything below is empty until ifem_sa_set_moving_wall
+  struct MovingWall {
+    bool set = false, updated = false;  // a wall was given / ifem_sa_update_moving_wall_distance ran since (d_mov is "absent" before)
+    int32_t nv = 0, ne = 0;             // wall vertices, wall edges (dim 2 only)
+    int32_t max_vertex = -1;            // largest entry of `vertex`: a later, smaller solid must not be indexed with it
+    double image_distance = 0, wall_function_distance = 0;
+    int sample_at_image_point = 0;
+    DBuf<int32_t> vertex;  // [nv] index into FsiState::vert
+    DBuf<int32_t> by_id;   // [nv] the positions of `vertex` in ascending solid vertex id: the order of the reference's std::map
+    DBuf<int32_t> edge;    // [ne][2] positions in `vertex`
+    DBuf<double> normal;   // [nv][dim]
+    DBuf<double> utau;     // [nv] shear_velocities
+    DBuf<double> erec, vrec; // records streamed by k_sa_moving_wall: per edge v1 v2 utau1 utau2 |v2 - v1|^2, per vertex (by_id order) v utau
+    DBuf<double> d_mov, yplus; // [nUl] (DBL_MAX = absent, 201 before the first update)
+    DBuf<double> d_eff;    // [nUl] d_mov < d_fixed ? d_mov : d_fixed (:711-719): what SaArgs::wall_d reads once `updated`
+    DBuf<double> pts, val; // [nv][dim] sample points, [nv][dim + 1] the fluid solution there
+    DBuf<int32_t> cell;    // [nv] the fluid cell around each sample point or -1
+    DBuf<uint32_t> order_min; // [nUl] smallest cell_order among the cells that touch the node
+    DBuf<uint32_t> first_ind; // [nUl] bit 0: some indicator cell touches the node, bit 1: the first touching cell is an indicator cell
+    DBuf<int64_t> count;   // [1]
+    void clear() { // as if no moving wall had ever been set
+      set = updated = false;
+      nv = ne = 0;
+      max_vertex = -1;
+      for (DBuf<int32_t> *b : {&vertex, &by_id, &edge, &cell}) b->release();
+      for (DBuf<double> *b : {&normal, &utau, &erec, &vrec, &d_mov, &yplus, &d_eff, &pts, &val}) b->release();
+      order_min.release(); first_ind.release(); count.release();
+    }
+  } mw;
 };
 } // namespace ifem
 

@@ -1033,10 +1033,25 @@ void build_fluid_bins(ifem_ctx *ctx) {
 }
 } // namespace
 
+// the launch of ifem_fsi_fluid_at_points on device arrays (d_st may be nullptr): what sa_wall.hip samples the wall vertices with
+void fsi_fluid_at_points_dev(ifem_ctx *ctx, int32_t n, const double *d_pts, double *d_val, double *d_st, int32_t *d_cell) {
+  if (n <= 0) return;
+  build_fluid_bins(ctx);
+  hipStream_t st = ctx->stream;
+  const int dim = ctx->dim;
+  const double *fl = (ctx->stress_valid && ctx->stress.n == (size_t)dim * dim * ctx->nUl) ? ctx->stress.p : nullptr;
+  if (dim == 2)
+    hipLaunchKernelGGL(k_fluid_at_points<2>, grid_for(n, 128), dim3(128), 0, st, n, d_pts, ctx->n_cells, ctx->kv, ctx->nu, ctx->nUl, ctx->vcoords.p,
+                       ctx->cell_unodes.p, ctx->cell_pnodes.p, ctx->vec[IFEM_VEC_PRESENT].p, fl, fluid_bins_of<2>(ctx), d_val, d_st, d_cell);
+  else
+    hipLaunchKernelGGL(k_fluid_at_points<3>, grid_for(n, 128), dim3(128), 0, st, n, d_pts, ctx->n_cells, ctx->kv, ctx->nu, ctx->nUl, ctx->vcoords.p,
+                       ctx->cell_unodes.p, ctx->cell_pnodes.p, ctx->vec[IFEM_VEC_PRESENT].p, fl, fluid_bins_of<3>(ctx), d_val, d_st, d_cell);
+  IFEM_HIP_CHECK(hipGetLastError());
+}
+
 void fsi_fluid_at_points(ifem_ctx *ctx, int32_t n, const double *points, double *values, double *stress, int32_t *cell) {
   if (n < 0 || (n > 0 && (!points || !values || !cell))) throw Error(IFEM_E_BADPARAM, "ifem_fsi_fluid_at_points: null argument");
   if (n == 0) return;
-  build_fluid_bins(ctx);
   hipStream_t st = ctx->stream;
   const int dim = ctx->dim;
   DBuf<double> d_pts, d_val, d_st;
@@ -1045,13 +1060,7 @@ void fsi_fluid_at_points(ifem_ctx *ctx, int32_t n, const double *points, double 
   d_val.alloc((size_t)n * (dim + 1));
   d_cell.alloc((size_t)n);
   if (stress) d_st.alloc((size_t)n * dim * dim);
-  const double *fl = (ctx->stress_valid && ctx->stress.n == (size_t)dim * dim * ctx->nUl) ? ctx->stress.p : nullptr;
-  if (dim == 2)
-    hipLaunchKernelGGL(k_fluid_at_points<2>, grid_for(n, 128), dim3(128), 0, st, n, d_pts.p, ctx->n_cells, ctx->kv, ctx->nu, ctx->nUl, ctx->vcoords.p,
-                       ctx->cell_unodes.p, ctx->cell_pnodes.p, ctx->vec[IFEM_VEC_PRESENT].p, fl, fluid_bins_of<2>(ctx), d_val.p, d_st.p, d_cell.p);
-  else
-    hipLaunchKernelGGL(k_fluid_at_points<3>, grid_for(n, 128), dim3(128), 0, st, n, d_pts.p, ctx->n_cells, ctx->kv, ctx->nu, ctx->nUl, ctx->vcoords.p,
-                       ctx->cell_unodes.p, ctx->cell_pnodes.p, ctx->vec[IFEM_VEC_PRESENT].p, fl, fluid_bins_of<3>(ctx), d_val.p, d_st.p, d_cell.p);
+  fsi_fluid_at_points_dev(ctx, n, d_pts.p, d_val.p, d_st.p, d_cell.p);
   IFEM_HIP_CHECK(hipMemcpyAsync(values, d_val.p, (size_t)n * (dim + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
   IFEM_HIP_CHECK(hipMemcpyAsync(cell, d_cell.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   if (stress) IFEM_HIP_CHECK(hipMemcpyAsync(stress, d_st.p, (size_t)n * dim * dim * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -516,6 +516,49 @@ int ifemx_turbulence_setup(void *hv, int32_t *node, double *value, int64_t *n_li
   });
 }
 
+// the wall function of the attached Spalart-Allmaras model at a moving FSI wall (turbulence.hpp): test hooks onto the three members the
+// reference's FSI driver calls, and onto connect_indicator_field
+extern "C++" {
+namespace {
+template <int dim>
+Fluid::MPI::SpalartAllmaras<dim> &sa_model(Fluid::MPI::FluidSolver<dim> &s) {
+  auto *sa = dynamic_cast<Fluid::MPI::SpalartAllmaras<dim> *>(s.get_turbulence_model());
+  if (!sa) throw std::invalid_argument("no Spalart-Allmaras model attached");
+  return *sa;
+}
+} // namespace
+} // extern "C++"
+// indicator [n_cells], or NULL / n = 0 for an indicator already on the device (ifem_fsi_update_indicator on the solver's context)
+int ifemx_turbulence_connect_indicator_field(void *hv, const int32_t *indicator, int64_t n) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    const std::vector<int32_t> ind(indicator ? indicator : nullptr, indicator ? indicator + n : nullptr);
+    if (h->dim == 2) sa_model<2>(*h->s2).connect_indicator_field(ind); else sa_model<3>(*h->s3).connect_indicator_field(ind);
+  });
+}
+int ifemx_turbulence_update_moving_wall_distance(void *hv, const ifem_fsi_solid *solid, const ifem_sa_wall *wall, const double *shear_velocities) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    if (!solid || !wall || !shear_velocities) throw std::invalid_argument("update_moving_wall_distance: solid, wall and shear velocities");
+    const std::vector<double> ut(shear_velocities, shear_velocities + std::max(wall->n_vertices, 0));
+    if (h->dim == 2) sa_model<2>(*h->s2).update_moving_wall_distance(*solid, *wall, ut); else sa_model<3>(*h->s3).update_moving_wall_distance(*solid, *wall, ut);
+  });
+}
+int ifemx_turbulence_update_boundary_condition(void *hv, int first_step, int64_t *n_lines) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto run = [&](auto &m) { m.update_boundary_condition(first_step != 0); if (n_lines) *n_lines = m.last_boundary_lines; };
+    if (h->dim == 2) run(sa_model<2>(*h->s2)); else run(sa_model<3>(*h->s3));
+  });
+}
+int ifemx_turbulence_get_shear_velocity(void *hv, double vel, double init_guess, double *out) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    const double v = h->dim == 2 ? sa_model<2>(*h->s2).get_shear_velocity(vel, init_guess) : sa_model<3>(*h->s3).get_shear_velocity(vel, init_guess);
+    if (out) *out = v;
+  });
+}
+
 // SCnsEX::set_hard_coded_boundary_condition_time(id, time) (mpi_scnsex.cpp:84-97) and the counters of its most recent run_one_step
 int ifemx_set_hard_coded_boundary_condition_time(void *hv, unsigned id, double time) {
   auto *h = static_cast<Handle *>(hv);

@@ -1,5 +1,6 @@
 // turbulence.cpp -- host mirror of Fluid::MPI::SpalartAllmaras<dim> (source/mpi_spalart_allmaras.cpp) over the ifem_sa_* entry points.
 #include "turbulence.hpp"
+#include <algorithm>
 #include <iomanip>
 #include <map>
 #include "insim.hpp"
@@ -123,6 +124,61 @@ void SpalartAllmaras<dim>::run_one_step(bool apply_nonzero_constraints) {
     for (int it = 0; it < rc; ++it)
       *fluid.pcout << std::scientific << std::left << " ITR = " << std::setw(2) << it << " ABS_RES = " << log[it * 4] << " REL_RES = " << log[it * 4 + 1]
                    << " GMRES_ITR = " << std::setw(3) << (unsigned)log[it * 4 + 2] << " GMRES_RES = " << log[it * 4 + 3] << std::endl;
+}
+
+template <int dim>
+void SpalartAllmaras<dim>::connect_indicator_field(const std::vector<int32_t> &indicator) {
+  if (!indicator.empty()) {
+    if (indicator.size() != fluid.dofs.cell_unodes.size() / fluid.dofs.nu) throw std::invalid_argument("connect_indicator_field: one entry per cell");
+    fluid.check(ifem_set_cell_fields(fluid.ctx, indicator.data()), "SpalartAllmaras::connect_indicator_field");
+  }
+  has_indicator = true;
+}
+
+template <int dim>
+void SpalartAllmaras<dim>::update_moving_wall_distance(const ifem_fsi_solid &solid, const ifem_sa_wall &w, const std::vector<double> &shear_velocities) {
+  refuse_partitioned();
+  if (w.n_vertices <= 0 || !w.vertex || !w.normal || (int64_t)shear_velocities.size() != w.n_vertices)
+    throw std::invalid_argument("update_moving_wall_distance: wall vertices, normals and one shear velocity per wall vertex");
+  fluid.check(ifem_fsi_set_solid(fluid.ctx, &solid), "SpalartAllmaras::update_moving_wall_distance");
+  const std::vector<int32_t> v(w.vertex, w.vertex + w.n_vertices), e(w.edge ? w.edge : nullptr, w.edge ? w.edge + 2 * (size_t)w.n_edges : nullptr);
+  const std::vector<double> nrm(w.normal, w.normal + (size_t)w.n_vertices * dim);
+  const double key[3] = {w.image_distance, w.wall_function_distance, double(w.sample_at_image_point != 0)};
+  if (v != wall_vertex || e != wall_edge || nrm != wall_normal || !std::equal(key, key + 3, wall_key)) {
+    fluid.check(ifem_sa_set_moving_wall(fluid.ctx, &w), "SpalartAllmaras::update_moving_wall_distance");
+    wall_vertex = v; wall_edge = e; wall_normal = nrm;
+    std::copy(key, key + 3, wall_key);
+  }
+  const auto &par = fluid.parameters;
+  const ifem_sa_params p{par.viscosity, par.fluid_rho, fluid.time.get_delta_t()};
+  fluid.check(ifem_sa_set_shear_velocities(fluid.ctx, shear_velocities.data()), "SpalartAllmaras::update_moving_wall_distance");
+  fluid.check(ifem_sa_update_moving_wall_distance(fluid.ctx, &p, nullptr, nullptr), "SpalartAllmaras::update_moving_wall_distance");
+}
+
+template <int dim>
+void SpalartAllmaras<dim>::update_boundary_condition(bool first_step) {
+  refuse_partitioned();
+  if (!has_indicator) throw std::logic_error("No available indicator function for SA model!");
+  const auto &par = fluid.parameters;
+  const ifem_sa_params p{par.viscosity, par.fluid_rho, fluid.time.get_delta_t()};
+  fluid.check(ifem_sa_update_boundary_condition(fluid.ctx, &p, first_step, nullptr, &last_boundary_lines), "SpalartAllmaras::update_boundary_condition");
+  // the lines of nonzero_constraints after the merge, as constraint_nodes() / constraint_values() report them
+  const size_t n = (size_t)fluid.dofs.n_unodes;
+  std::vector<uint8_t> flags(n);
+  std::vector<double> inhom(n);
+  fluid.check(ifem_sa_get_constraints(fluid.ctx, 1, flags.data(), inhom.data()), "SpalartAllmaras::update_boundary_condition");
+  nodes.clear(); values.clear();
+  for (size_t i = 0; i < n; ++i)
+    if (flags[i]) { nodes.push_back((int32_t)i); values.push_back(inhom[i]); }
+}
+
+template <int dim>
+double SpalartAllmaras<dim>::get_shear_velocity(double vel, double init_guess) {
+  const auto &par = fluid.parameters;
+  const ifem_sa_params p{par.viscosity, par.fluid_rho, fluid.time.get_delta_t()};
+  double out = 0;
+  fluid.check(ifem_sa_get_shear_velocity(&p, par.spalart_allmaras_image_distance, vel, init_guess, &out), "SpalartAllmaras::get_shear_velocity");
+  return out;
 }
 
 template <int dim>

@@ -55,6 +55,7 @@ void fsi_set_solid(ifem_ctx *ctx, const ifem_fsi_solid *s);
 void fsi_update_indicator(ifem_ctx *ctx, int32_t *host_out, int64_t *n_artificial);
 void fsi_find_fluid_bc(ifem_ctx *ctx, double dt, int use_dirichlet_bc, const int32_t *cell_order, ifem_fsi_stats *stats);
 void fsi_fluid_at_points(ifem_ctx *ctx, int32_t n, const double *points, double *values, double *stress, int32_t *cell);
+void fsi_fluid_at_points_dev(ifem_ctx *ctx, int32_t n, const double *d_pts, double *d_val, double *d_st, int32_t *d_cell); // the same on device arrays, no sync
 // api.hip: do the flag arrays of pair k differ (compared on the device); identity of the constrained-dof set `which` after
 // its flags changed
 void flags_differ(ifem_ctx *ctx, int npairs, const DBuf<uint8_t> *const *a, const DBuf<uint8_t> *const *b, double *out);
@@ -84,6 +85,16 @@ void sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero);
 void sa_solve(ifem_ctx *ctx, int use_nonzero, uint32_t *iters, double *res_out);
 int sa_newton_step(ifem_ctx *ctx, const ifem_sa_params *p, int apply_nonzero, double tolerance, int max_iterations, double *log);
 void sa_update_eddy_viscosity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
+const double *sa_node_points(ifem_ctx *ctx); // support points of the local nodes [nUl][dim] on the device, built on first use
+// sa_wall.hip -- the wall function at a moving FSI wall (mpi_spalart_allmaras.cpp:17-280, mpi_fsi.cpp:782-844); state in ctx->sa.mw
+void sa_set_moving_wall(ifem_ctx *ctx, const ifem_sa_wall *w);
+void sa_set_shear_velocities(ifem_ctx *ctx, const double *utau);
+void sa_update_shear_velocity(ifem_ctx *ctx, const ifem_sa_params *p, double *host_out);
+void sa_update_moving_wall_distance(ifem_ctx *ctx, const ifem_sa_params *p, double *host_d, double *host_yplus);
+void sa_get_moving_wall(ifem_ctx *ctx, double *host_d, double *host_yplus);
+void sa_update_boundary_condition(ifem_ctx *ctx, const ifem_sa_params *p, int first_step, const int32_t *cell_order, int64_t *n_lines);
+void sa_get_constraints(ifem_ctx *ctx, int which, uint8_t *flags, double *inhom);
+void sa_wall_refresh_d_eff(ifem_ctx *ctx); // d_eff = min(d_mov, d_fixed) again after the fixed distance changed
 
 // scnsex.hip -- Fluid::MPI::SCnsEX (mpi_scnsex.cpp) on scalar node matrices; state in ctx->ex
 void scnsex_check(ifem_ctx *ctx); // refuses what the solver does not cover (hanging-node lines, partitioned contexts, Taylor-Hood)

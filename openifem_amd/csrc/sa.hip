@@ -11,8 +11,10 @@
 // wall distance with MappingQGeneric(degree), which differs from it on curved cells only.
 // ONE deliberate deviation from the reference: at :757-770 it discards the result of std::min and returns an uninitialised r whenever
 // |S~| > 1e-8.  Here r = min(nu~_present / (S~ kappa^2 d^2), 10) in that branch and r = 10 in the other: the evident intent.
-// Out of scope: the FSI wall function (update_moving_wall_distance, update_boundary_condition, get_shear_velocity), refinement
-// transfer, checkpoint payload and hanging-node lines (refused by sa_check).
+// The FSI wall function (update_moving_wall_distance, update_boundary_condition, get_shear_velocity) is sa_wall.hip; the assembly reads its
+// effective distance min(moving, fixed) through SaArgs::wall_d.
+// Out of scope: refinement transfer, checkpoint payload, hanging-node lines (refused by sa_check), and partitioned contexts for the
+// wall-function entry points.
 // Partitioned contexts: rows of owned nodes only (owner computes, the ghost-layer cells are integrated redundantly), the ghost entries of nu~
 // are refreshed through the velocity halo plan before every assembly and before the eddy viscosity, the operator input before every product,
 // and the preconditioner is the ILU(0) of the owned x owned block (what bilu_analyse keeps).  Every rank passes ALL wall points and the
@@ -333,6 +335,19 @@ void sa_ensure(ifem_ctx *ctx) {
   IFEM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// the support points of the local nodes: they depend on the mesh alone, once per context
+const double *sa_node_points(ifem_ctx *ctx) {
+  DBuf<double> &xn = ctx->sa.node_points;
+  const int64_t n = ctx->nUl;
+  const int dim = ctx->dim;
+  if (xn.n != (size_t)n * dim) {
+    xn.alloc((size_t)n * dim);
+    IFEM_HIP_CHECK(hipMemsetAsync(xn.p, 0, xn.n * sizeof(double), ctx->stream));
+    pick(dim, ctx->kv, launch_node_points_t<2, 1>, launch_node_points_t<2, 2>, launch_node_points_t<3, 1>, launch_node_points_t<3, 2>)(ctx, xn.p);
+  }
+  return xn.p;
+}
+
 void sa_set_wall_points(ifem_ctx *ctx, int64_t n_pts, const double *pts) {
   sa_check(ctx);
   if (n_pts < 0 || (n_pts > 0 && !pts)) throw Error(IFEM_E_BADPARAM, "ifem_sa_set_wall_points: n < 0 or no points");
@@ -341,17 +356,13 @@ void sa_set_wall_points(ifem_ctx *ctx, int64_t n_pts, const double *pts) {
   const int dim = ctx->dim;
   const int64_t n = ctx->nUl;
   DBuf<double> dp;
-  DBuf<double> &xn = ctx->sa.node_points;
   dp.upload(pts, (size_t)n_pts * dim, s);
   KScope ks(ctx, IFEM_KC_OTHER, double(n) * (dim + 1) * 8 + double(n_pts) * dim * 8);
-  if (xn.n != (size_t)n * dim) { // the support points depend on the mesh alone: once per context
-    xn.alloc((size_t)n * dim);
-    IFEM_HIP_CHECK(hipMemsetAsync(xn.p, 0, xn.n * sizeof(double), s));
-    pick(dim, ctx->kv, launch_node_points_t<2, 1>, launch_node_points_t<2, 2>, launch_node_points_t<3, 1>, launch_node_points_t<3, 2>)(ctx, xn.p);
-  }
-  if (dim == 2) hipLaunchKernelGGL((k_sa_wall_distance<2>), dim3(grid_for(n)), dim3(256), 0, s, n, xn.p, n_pts, dp.p, ctx->sa.wall_d.p);
-  else hipLaunchKernelGGL((k_sa_wall_distance<3>), dim3(grid_for(n)), dim3(256), 0, s, n, xn.p, n_pts, dp.p, ctx->sa.wall_d.p);
+  const double *xn = sa_node_points(ctx);
+  if (dim == 2) hipLaunchKernelGGL((k_sa_wall_distance<2>), dim3(grid_for(n)), dim3(256), 0, s, n, xn, n_pts, dp.p, ctx->sa.wall_d.p);
+  else hipLaunchKernelGGL((k_sa_wall_distance<3>), dim3(grid_for(n)), dim3(256), 0, s, n, xn, n_pts, dp.p, ctx->sa.wall_d.p);
   IFEM_HIP_CHECK(hipGetLastError());
+  sa_wall_refresh_d_eff(ctx); // the effective distance of a moving wall follows the new fixed one
   IFEM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -397,7 +408,8 @@ void sa_assemble(ifem_ctx *ctx, const ifem_sa_params *p, int use_nonzero) {
   A.is_c = sa.has_c[w] ? sa.is_c[w].p : nullptr;
   A.cval = sa.has_c[w] ? sa.cval[w].p : nullptr;
   A.fluid = ctx->vec[IFEM_VEC_PRESENT].p;
-  A.nu_eval = sa.vec[IFEM_SA_EVAL].p; A.nu_present = sa.vec[IFEM_SA_PRESENT].p; A.wall_d = sa.wall_d.p;
+  A.nu_eval = sa.vec[IFEM_SA_EVAL].p; A.nu_present = sa.vec[IFEM_SA_PRESENT].p;
+  A.wall_d = sa.mw.updated ? sa.mw.d_eff.p : sa.wall_d.p; // min(moving, fixed) once a moving wall was measured (:711-719)
   A.mu = p->viscosity; A.rho = p->rho; A.dt = p->dt;
   {
     // algorithmic bytes: the values written + the node data and position tables read

@@ -80,6 +80,10 @@ def _lib():
     L.ifemx_attach_turbulence_model.argtypes = [C.c_void_p, C.c_char_p]
     L.ifemx_turbulence_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifemx_turbulence_setup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
+    L.ifemx_turbulence_connect_indicator_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.ifemx_turbulence_update_moving_wall_distance.argtypes = [C.c_void_p, C.POINTER(capi.FsiSolid), C.POINTER(capi.SaWall), C.c_void_p]
+    L.ifemx_turbulence_update_boundary_condition.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.ifemx_turbulence_get_shear_velocity.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.ifemx_channel_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_double]
     L._ifemx_bound = True
     return L
@@ -167,6 +171,33 @@ class FluidSolver:
         self._chk(self.L.ifemx_turbulence_setup(self.h, node.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), C.byref(nl),
                                                 wall.ctypes.data_as(C.c_void_p), C.byref(nw)))
         return node, val, wall
+
+    # the wall function of the attached Spalart-Allmaras model at a moving FSI wall
+    def turbulence_connect_indicator_field(self, indicator=None):
+        """TurbulenceModel::connect_indicator_field: the cell indicator [n_cells], or None for one already on the device"""
+        ind = None if indicator is None else np.ascontiguousarray(indicator, np.int32)
+        self._chk(self.L.ifemx_turbulence_connect_indicator_field(self.h, None if ind is None else ind.ctypes.data_as(C.c_void_p), 0 if ind is None else len(ind)))
+
+    def turbulence_update_moving_wall_distance(self, vertices, cells, bfaces, wall, shear_velocities):
+        """SpalartAllmaras::update_moving_wall_distance with the plain solid description: solid arrays as Context.fsi_set_solid takes them, wall
+        a capi.SaWall, shear_velocities [wall.n_vertices]"""
+        keep = [np.ascontiguousarray(vertices, float), np.ascontiguousarray(cells, np.int32), None if bfaces is None else np.ascontiguousarray(bfaces, np.int32)]
+        ptr = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in keep]
+        solid = capi.FsiSolid(len(keep[0]), len(keep[1]), 0 if keep[2] is None else len(keep[2]), ptr[0], ptr[1], ptr[2], None, None, None)
+        ut = np.ascontiguousarray(shear_velocities, float)
+        assert len(ut) == wall.n_vertices
+        self._chk(self.L.ifemx_turbulence_update_moving_wall_distance(self.h, C.byref(solid), C.byref(wall), ut.ctypes.data_as(C.c_void_p)))
+
+    def turbulence_update_boundary_condition(self, first_step):
+        """SpalartAllmaras::update_boundary_condition; returns the number of lines merged into each constraint object"""
+        n = C.c_int64(0)
+        self._chk(self.L.ifemx_turbulence_update_boundary_condition(self.h, int(first_step), C.byref(n)))
+        return n.value
+
+    def turbulence_get_shear_velocity(self, vel, init_guess):
+        out = C.c_double(0)
+        self._chk(self.L.ifemx_turbulence_get_shear_velocity(self.h, vel, init_guess, C.byref(out)))
+        return out.value
 
     def update_stress(self):
         _, n_u, _ = self.sizes()

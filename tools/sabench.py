@@ -1,6 +1,7 @@
-"""What the Spalart-Allmaras kernels cost (csrc/sa.hip): per-launch time of k_sa_assemble, of the wall-distance kernels with the wall
-faces of a channel, and the per-iteration cost of one S-A solve, each beside its algorithmic bytes and the resulting share of the HBM
-rate.  Measurements to be written down (profiles/sa_model.txt), not thresholds; needs a GPU.
+"""What the Spalart-Allmaras kernels cost (csrc/sa.hip, csrc/sa_wall.hip): per-launch time of k_sa_assemble, of the wall-distance kernels with
+the wall faces of a channel, of the moving-wall update beside the fixed-wall kernel at the same point count, and the per-iteration cost of one
+S-A solve, each beside its algorithmic bytes and the resulting share of the HBM
+rate.  Measurements to be written down (profiles/sa_model.txt, profiles/sa_wall_function.txt), not thresholds; needs a GPU.
 
     python tools/sabench.py --cells 64 --kv 2 --reps 5
 
@@ -22,12 +23,61 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_BYTES_PER_S = 6.29e12  # measured streaming rate of an MI355X (float4 copy); the spec is 8.0e12
 
 
+def _timed(capi, L, ctx, reps, call):
+    call()  # warm-up
+    assert L.ifem_kprof_begin(ctx.h) == 0
+    for _ in range(reps):
+        call()
+    k = capi.kprof_end(L, ctx.h)
+    return (k["other"]["ms"] if "other" in k else sum(v["ms"] for v in k.values())) / reps
+
+
+def moving_wall_leg(capi, L, ctx, m, P, wall, nw, reps, kv):
+    """ifem_sa_update_moving_wall_distance (csrc/sa_wall.hip::k_sa_moving_wall) with nw wall vertices, beside k_sa_wall_distance with the same
+    number of points in the same job: on the 3D box a point cloud (the vertex loop: distance + the u_tau payload), and on a 2D box with about as
+    many nodes a closed nw-gon (the edge loop with its division and square root, then the vertex loop)"""
+    import sa_wall_ref
+    from boxmesh import BoxMesh
+    rng = np.random.default_rng(11)
+    res = {"wall_vertices": nw}
+    # 3D: a point cloud in the middle of the channel; one solid cell, which the point location of the FSI side wants
+    pts = np.array([2.0, 0.5, 0.5]) + 0.3 * rng.uniform(-1, 1, (nw, 3))
+    ctx.fsi_set_solid(pts, np.arange(8, dtype=np.int32)[None, :], None)
+    ctx.sa_set_moving_wall(capi.SaWall.make(rng.permutation(nw).astype(np.int32), np.zeros((nw, 3)), None, 0.02, 0.1))
+    ctx.sa_set_shear_velocities(0.05 + 0.01 * rng.uniform(size=nw))
+    nn = m.n_unodes
+    ms = _timed(capi, L, ctx, reps, lambda: L.ifem_sa_update_moving_wall_distance(ctx.h, P, None, None))
+    ctx.sa_set_moving_wall(None)
+    ms_fixed = _timed(capi, L, ctx, reps, lambda: ctx.sa_set_wall_points(pts))
+    ctx.sa_set_wall_points(wall)  # the channel's walls again, for the legs that follow
+    res["box3d"] = {"nodes": nn, "pairs": nn * nw, "ms": ms, "pairs_per_s": nn * nw / (ms * 1e-3),
+                    "k_sa_wall_distance_ms": ms_fixed, "k_sa_wall_distance_pairs_per_s": nn * nw / (ms_fixed * 1e-3)}
+    # 2D: (n1 - 1) / kv cells per direction give n1^2 ~ nn nodes
+    n1 = int(round(nn ** 0.5))
+    c = (n1 - 1) // kv
+    m2 = BoxMesh((c, c), (0, 0), (1.2, 1.2), kv=kv)
+    c2 = capi.Context(2, kv, m2.vcoords, m2.cell_unodes, m2.cell_pnodes, m2.cell_face_bid, m2.n_unodes, m2.n_pnodes)
+    s = sa_wall_ref.polygon_solid(nw, centre=(0.5713, 0.6091))
+    vertex, normal, edges = sa_wall_ref.polygon_wall(s, rng)
+    ms_fixed = _timed(capi, L, c2, reps, lambda: c2.sa_set_wall_points(s.vertices[vertex]))
+    c2.fsi_set_solid(s.vertices, s.cells, s.bfaces)
+    c2.sa_set_moving_wall(capi.SaWall.make(vertex, normal, edges, 0.02, 0.1))
+    c2.sa_set_shear_velocities(0.05 + 0.01 * rng.uniform(size=nw))
+    ms = _timed(capi, L, c2, reps, lambda: L.ifem_sa_update_moving_wall_distance(c2.h, P, None, None))
+    pairs = m2.n_unodes * 2 * nw  # every node meets nw edges and nw vertices
+    res["box2d"] = {"nodes": m2.n_unodes, "pairs": pairs, "ms": ms, "pairs_per_s": pairs / (ms * 1e-3),
+                    "k_sa_wall_distance_ms": ms_fixed, "k_sa_wall_distance_pairs_per_s": m2.n_unodes * nw / (ms_fixed * 1e-3)}
+    c2.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=64, help="cells per direction of the box")
     ap.add_argument("--kv", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5, help="timed launches of each kernel")
     ap.add_argument("--solve", type=int, default=1, help="0: skip the solve (exact ILU(0) substitution runs in one workgroup)")
+    ap.add_argument("--wall-vertices", type=int, default=4096, help="wall vertices of the moving-wall leg (0: skip it)")
     args = ap.parse_args()
     from openifem_amd import capi
     from boxmesh import BoxMesh
@@ -85,6 +135,8 @@ def main():
     out["k_sa_assemble"] = {"ms": ms, "bytes": by, "hbm_share": by / (ms * 1e-3) / HBM_BYTES_PER_S,
                             "atomics_per_s": m.n_cells * nu * nu / (ms * 1e-3), "families": k}
 
+    if args.wall_vertices:
+        out["moving_wall"] = moving_wall_leg(capi, L, ctx, m, P, wall, args.wall_vertices, args.reps, args.kv)
     print("[sabench] kernels timed", file=sys.stderr, flush=True)
     if args.solve:
         t0 = time.perf_counter()
