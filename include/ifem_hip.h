@@ -195,6 +195,14 @@ typedef struct {
   int32_t asm3_cpb;      /* 2: cells (= wavefronts) per workgroup of that kernel (2, 4 or 8; anything else is IFEM_E_BADPARAM) */
   int32_t tpp_milu_permille; /* SCnsIM, ILU(0) of T_pp: 950 (default); 0 plain ILU(0); w in (0, 1000]: relaxed modified ILU, w/1000 of every dropped
                                 fill-in entry is added to the diagonal of its row */
+  int32_t asm_rows;      /* 1 (default): a full assembly on a context that is one uniform box of 3D Q2 velocity on a full node lattice (one rank,
+                            no hanging-node line, no scalar operator wanted) assembles A_uu by ROW OWNERS (csrc/assemble_rows.hip): one wavefront
+                            integrates the complete rows of up to 8 nodes from all cells that touch them and stores them once -- no atomics on
+                            A_uu, no zero fill, the same bits on every run.  The cell kernel runs beside it for the right-hand side and writes the
+                            point data the rows need (+ 2.6 KB per cell of device memory while the path is taken).  Every other context, and 0:
+                            the cell kernel scatters A_uu with atomics.  (The field fills the 4 bytes that the alignment of
+                            tpp_ilu_order left unused behind tpp_milu_permille: every other field keeps its offset, the struct its size,
+                            and uu_patch_levels stays the last one.) */
   int64_t tpp_ilu_order; /* SCnsIM, explicit T_pp: preconditioner of its inner GMRES -- 2 (default): ILU(0), natural row order when its
                             elimination levels hold >= 1024 rows on average, multicolour otherwise; 0: natural order always (fewest
                             iterations, O(n^(1/dim)) level-scheduled launches); 1: multicolour always (a few dozen levels whatever

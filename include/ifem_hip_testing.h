@@ -39,6 +39,11 @@ int ifem_test_restart_fits(ifem_ctx *ctx, int columns);
  * lengths the context detected (zeros: not a uniform box level; entries past dim are zero), whatever the tuning says. */
 int ifem_test_mf_uniform(ifem_ctx *ctx, double *h);
 
+/* How the last full assembly of the context wrote A_uu (ifem_tuning::asm_rows, csrc/assemble_rows.hip): *state = 1 the row owners ran, -1 they
+ * were asked for and refused (the cell kernel scattered with atomics, as with asm_rows = 0), 0 not asked or no full assembly yet.  verbose != 0:
+ * a refusal is named in one line on stderr. */
+int ifem_test_asm_rows(ifem_ctx *ctx, int verbose, int32_t *state);
+
 /* y_u = A_uu x_u on the velocity part of two context vectors as the single-precision inner solver of IFEM_AINV_MG forms the product
  * (ifem_tuning::inner_f32; solver.hip::uu_apply_f32col): x rounded to float, its ghost entries exchanged as float, single-precision
  * cell arithmetic, fp64 result.  After ifem_ins_assemble / ifem_imex_assemble.  Stages the column in a level vector of the A_uu V-cycle and

@@ -128,7 +128,7 @@ class MgTransfer(C.Structure):
 class Tuning(C.Structure):
     _fields_ = [("geo_cache", C.c_int32), ("xcd_swizzle", C.c_int32), ("asm_skip", C.c_int32), ("spmv_lanes", C.c_int32),
                 ("sm_lanes", C.c_int32), ("mf_f32", C.c_int32), ("tpp_operator", C.c_int32), ("spmv_pipe", C.c_int32), ("halo_overlap", C.c_int32),
-                ("asm3_variant", C.c_int32), ("cg_single_reduction", C.c_int32), ("asm3_cpb", C.c_int32), ("tpp_milu_permille", C.c_int32), ("tpp_ilu_order", C.c_int64), ("basis_pad", C.c_int64), ("tpp_tri_sweeps", C.c_int32), ("uu_row_order", C.c_int32), ("eig_steps", C.c_int32), ("vcycle_graph_cells", C.c_int32),
+                ("asm3_variant", C.c_int32), ("cg_single_reduction", C.c_int32), ("asm3_cpb", C.c_int32), ("tpp_milu_permille", C.c_int32), ("asm_rows", C.c_int32), ("tpp_ilu_order", C.c_int64), ("basis_pad", C.c_int64), ("tpp_tri_sweeps", C.c_int32), ("uu_row_order", C.c_int32), ("eig_steps", C.c_int32), ("vcycle_graph_cells", C.c_int32),
                 ("scns_pc", C.c_int32), ("pvv_sweeps", C.c_int32), ("b2pp_sweeps", C.c_int32), ("scns_inner_reorth", C.c_int32), ("scns_inner_left", C.c_int32), ("scns_graph", C.c_int32), ("stored_uu", C.c_int32), ("mf_uniform", C.c_int32), ("inner_f32", C.c_int32), ("mg_lattice_u", C.c_int32), ("uu_smoother", C.c_int32), ("uu_patch_levels", C.c_int32)]
 
 
@@ -169,7 +169,7 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_fsi_set_solid", "ifem_fsi_update_indicator", "ifem_fsi_find_fluid_bc", "ifem_fsi_get_stress",
            "ifem_get_constraints", "ifem_fsi_fluid_at_points", "ifem_comm_stats_get", "ifem_comm_stats_level", "ifem_true_residual", "ifem_tpp_ilu_probe", "ifem_tpp_override", "ifem_scns_pc_probe", "ifem_test_restart_fits",
            "ifem_kprof_begin", "ifem_kprof_end", "ifem_kprof_family_name", "ifem_export_rows", "ifem_export_uu_pattern", "ifem_vcycle_graph_stats", "ifem_inner_restart_length",
-           "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_uu_vmult_f32col",
+           "ifem_uu_stored_bytes", "ifem_test_mf_uniform", "ifem_test_asm_rows", "ifem_test_uu_vmult_f32col",
            "ifem_test_uu_patch_vmult", "ifem_test_uu_patch_info", "ifem_test_vec_kernel", "ifem_test_cg_device",
            "ifem_test_uu_fused_product", "ifem_test_mp_solve", "ifem_test_sm_apply", "ifem_test_b_apply", "ifem_test_sm_solve",
            "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel", "ifem_test_mg_lattice_transfer",
@@ -279,6 +279,7 @@ def load():
     L.ifem_scns_pc_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.ifem_test_restart_fits.argtypes = [C.c_void_p, C.c_int]
     L.ifem_test_mf_uniform.argtypes = [C.c_void_p, C.c_void_p]
+    L.ifem_test_asm_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.ifem_test_uu_vmult_f32col.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_vmult.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_info.argtypes = [C.c_void_p, C.c_void_p]
@@ -629,6 +630,12 @@ class Context:
             setattr(t, k, v)
         self._chk(self.L.ifem_set_tuning(self.h, C.byref(t)))
         self._tuning = t
+
+    def asm_rows_state(self, verbose=False):
+        """how the last full assembly wrote A_uu: 1 row owners, -1 asked for and refused, 0 not asked / none yet -- ifem_test_asm_rows"""
+        st = C.c_int32(0)
+        self._chk(self.L.ifem_test_asm_rows(self.h, int(verbose), C.byref(st)))
+        return int(st.value)
 
     def uu_stored_bytes(self):
         """device bytes currently allocated for A_uu values (0: ifem_tuning::stored_uu = 0 has kept no block CSR)"""

@@ -195,7 +195,7 @@ void ifem_default_solver_opts(ifem_solver_opts *o) {
 void ifem_default_tuning(ifem_tuning *t) {
   t->geo_cache = 1; t->xcd_swizzle = 1; t->asm_skip = 0; t->spmv_lanes = 32; t->sm_lanes = 32; t->mf_f32 = 1;
   t->tpp_operator = 0; t->spmv_pipe = 1; t->halo_overlap = 1; t->asm3_variant = 0; t->cg_single_reduction = 1; t->asm3_cpb = 2; t->tpp_milu_permille = 950; t->tpp_ilu_order = 2; t->basis_pad = 32 * 33; t->tpp_tri_sweeps = 0; t->uu_row_order = 1; t->eig_steps = 0; t->vcycle_graph_cells = 262144;
-  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->mg_lattice_u = 1; t->uu_smoother = 0; t->uu_patch_levels = 0;
+  t->scns_pc = 2; t->pvv_sweeps = 4; t->b2pp_sweeps = 6; t->scns_inner_reorth = 0; t->scns_inner_left = 1; t->scns_graph = 0; t->stored_uu = 1; t->mf_uniform = 1; t->inner_f32 = 1; t->mg_lattice_u = 1; t->uu_smoother = 0; t->uu_patch_levels = 0; t->asm_rows = 1;
 }
 
 int ifem_set_tuning(ifem_ctx *ctx, const ifem_tuning *t) {
@@ -1705,6 +1705,13 @@ int ifem_test_mf_uniform(ifem_ctx *ctx, double *h) {
   if (!ctx) return IFEM_E_BADPARAM;
   if (h) for (int d = 0; d < 3; ++d) h[d] = ctx->mf_uniform ? ctx->mf_h[d] : 0.0;
   return ifem::mf_takes_uniform(ctx) ? 1 : 0;
+}
+
+int ifem_test_asm_rows(ifem_ctx *ctx, int verbose, int32_t *state) {
+  if (!ctx || !state) return IFEM_E_BADPARAM;
+  *state = ctx->rows_state;
+  if (verbose && ctx->rows_state < 0) fprintf(stderr, "[ifem] A_uu row owners refused: %s\n", ctx->rows_why ? ctx->rows_why : "?");
+  return IFEM_OK;
 }
 
 int ifem_inner_restart_length(ifem_ctx *ctx) { return ctx ? ctx->inner_restart_eff : IFEM_E_BADPARAM; }

@@ -81,15 +81,22 @@ struct CellWork {
 // `cset`: the constraint object the scatter applies (0 / 1), -1: none.
 // imex = 1: InsIMEX::assemble (mpi_insimex.cpp:150-355): every field comes from the present solution, the matrix has no
 // convective terms.
-static void run_cell_kernel(ifem_ctx *ctx, const ifem_ins_params *p, CellWork w, bool shat, int cset, int imex) {
+// rows_uu (with w.uu): A_uu is assembled by row owners (assemble_rows.hip) -- the cell kernel integrates what else there is, writes the
+// point data of the contraction beside it, and the row kernel follows it between the same two events.  Its rows are stored, not added
+// to: no fill of the values.
+static void run_cell_kernel(ifem_ctx *ctx, const ifem_ins_params *p, CellWork w, bool shat, int cset, int imex, bool rows_uu = false) {
   hipStream_t s = ctx->stream;
   const int dim = ctx->dim;
+  const bool scatter_uu = w.uu && !rows_uu;
   const double nuu = w.uu ? double(ctx->Auu.val.n) : 0.0;
+  const double npd = rows_uu ? double(ctx->n_cells) * 27 * 12 : 0.0;
+  if (rows_uu && ctx->rows_pd.n != size_t(npd)) ctx->rows_pd.alloc(size_t(npd), "the point data of the row-owner assembly");
+  if (rows_uu && ctx->rows_fe.n != size_t(ctx->n_cells) * 96) ctx->rows_fe.alloc(size_t(ctx->n_cells) * 96, "the local right-hand sides of the row-owner assembly");
   const double ngeo = w.geo ? double(ctx->Bt.val.n + ctx->B.val.n + ctx->Mp.val.n + ctx->diagMu.n) : 0.0;
   { // system_matrix = 0; mass_matrix = 0; system_rhs = 0  (:163-165)
-    KScope ks_fill(ctx, IFEM_KC_ZERO_FILL, 8.0 * (nuu + ngeo + double(ctx->vec[IFEM_VEC_RHS].n)));
+    KScope ks_fill(ctx, IFEM_KC_ZERO_FILL, 8.0 * ((scatter_uu ? nuu : 0.0) + ngeo + double(ctx->vec[IFEM_VEC_RHS].n)));
     // (a hand-written fill kernel with 16-byte non-temporal stores measures the same 15 ms for the 78 GB at 128^3)
-    if (w.uu) IFEM_HIP_CHECK(hipMemsetAsync(ctx->Auu.val.p, 0, ctx->Auu.val.n * sizeof(double), s));
+    if (scatter_uu) IFEM_HIP_CHECK(hipMemsetAsync(ctx->Auu.val.p, 0, ctx->Auu.val.n * sizeof(double), s));
     if (w.geo) {
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->Bt.val.p, 0, ctx->Bt.val.n * sizeof(double), s));
       IFEM_HIP_CHECK(hipMemsetAsync(ctx->B.val.p, 0, ctx->B.val.n * sizeof(double), s));
@@ -106,8 +113,11 @@ static void run_cell_kernel(ifem_ctx *ctx, const ifem_ins_params *p, CellWork w,
   fill_cell_args(ctx, p, cset, A);
   A.v_mp = ctx->Mp.val.p; A.diagMu = ctx->diagMu.p;
   A.v_s = ctx->want_shat ? ctx->Shat.p : nullptr;
-  A.rhs_only = !w.uu && !w.geo; // (the kernel reads the two skips only when this is 0)
-  A.skip_uu = !w.uu;
+  A.rhs_only = !w.uu && !w.geo; // (the kernel reads the two skips only when this is 0; with row owners the launch still owes the
+                                // right-hand side the terms of the constrained pressure / velocity dofs of B and B^T)
+  A.skip_uu = !scatter_uu;
+  A.pd = rows_uu ? ctx->rows_pd.p : nullptr;
+  A.fe_out = rows_uu ? ctx->rows_fe.p : nullptr;
   A.skip_geo = !w.geo;
   A.debug_skip = ctx->tune.asm_skip;
   A.xcd_swizzle = ctx->tune.xcd_swizzle;
@@ -118,13 +128,15 @@ static void run_cell_kernel(ifem_ctx *ctx, const ifem_ins_params *p, CellWork w,
   // algorithmic traffic / work of the cell kernel: every stored value of the blocks it integrates
   // written once, the right-hand side, per cell the mesh tables and the three nodal vectors it gathers; flops of the
   // component-block form: per (node pair, point) dim^2 (2 FMA) + dim (2 FMA) + 5 products (53 flop in 3D), per (velocity
-  // node, pressure node, point) 2 (1 + dim) when B / B^T / M_p are integrated.  MFMA padding is not counted.
+  // node, pressure node, point) 2 (1 + dim) when B / B^T / M_p are integrated.  MFMA padding is not counted.  Row owners: the same
+  // values and flops from two launches, plus the point data written once by the cells and read once by its owners.
   const int nd = ctx->nu * dim + ctx->np, npc = 1 << dim;
   const double pair = 2.0 * (2 * dim * dim + 2 * dim) + 5.0; // 24 FMA + 5 products in 3D
-  KScope ks_asm(ctx, IFEM_KC_ASSEMBLE, 8.0 * (nuu + ngeo + double(ctx->nUo) * dim + double(ctx->nPo)) + double(ctx->n_cells) * (npc * dim * 8.0 + (ctx->nu + ctx->np) * 4.0 + 3.0 * nd * 8.0),
+  KScope ks_asm(ctx, IFEM_KC_ASSEMBLE, 8.0 * (nuu + 2.0 * (npd + (rows_uu ? 96.0 * double(ctx->n_cells) : 0.0)) + ngeo + double(ctx->nUo) * dim + double(ctx->nPo)) + double(ctx->n_cells) * (npc * dim * 8.0 + (ctx->nu + ctx->np) * 4.0 + 3.0 * nd * 8.0),
                 double(ctx->n_cells) * ctx->nq * ((nuu > 0 ? double(ctx->nu) * ctx->nu * pair : 0.0) + (ngeo > 0 ? double(ctx->nu) * ctx->np * 2.0 * (1 + dim) : 0.0)));
   if (!launch_ins_assemble3_kernel(ctx, A)) // assemble3.hip: 3D Q2/Q1 on the FP64 matrix cores
     launch_ins_assemble2_kernel(ctx, A);    // assemble2.hip (quadrature-point-outer, register accumulators)
+  if (rows_uu) launch_ins_assemble_rows(ctx, A);
   }
   IFEM_HIP_CHECK(hipEventRecord(ctx->ev1, s));
 }
@@ -157,6 +169,8 @@ struct AsmPlan {
   bool unconstrained_first = false; // the masked copies need the unconstrained pass first (M_p and diag(M_u) are then re-integrated too)
   bool stores_uu = false;           // a full assembly that scatters A_uu; a full one that does not is matrix-free (ifem_tuning::stored_uu = 0)
   bool lift = false;                // ... and owes the right-hand side the inhomogeneity lift (apply_mf.hip::uu_lift_mf)
+  bool rows_uu = false;             // ... by row owners (assemble_rows.hip) instead of the cell kernel's atomic scatter
+  const char *rows_refused = nullptr; // why not, when ifem_tuning::asm_rows asked for them
   bool matrix_free() const { return mode == AsmMode::Full && !stores_uu; }
 };
 
@@ -183,6 +197,12 @@ static AsmPlan plan_assembly(const ifem_ctx &c, int w, AsmMode mode) {
   // (hanging_condense_rhs), on the lifted right-hand side.
   pl.stores_uu = full && c.tune.stored_uu != 0;
   pl.lift = pl.matrix_free() && c.has_c[w] && c.inhom_any[w];
+  // ifem_tuning::asm_rows: the stored block by row owners where the context is a uniform 3D Q2 box on a full lattice (a lattice not looked
+  // at yet is decided by the launch, which falls back to the cell kernel's scatter).  InsIMEX matrices take the path as well.
+  if (pl.stores_uu && c.tune.asm_rows != 0) {
+    pl.rows_refused = c.tune.asm3_variant == 1 ? "asm3_variant = 1" : assemble_rows_refusal(c);
+    pl.rows_uu = pl.rows_refused == nullptr;
+  }
   // ifem_tuning::geo_cache = 0 switches the keeping off for full assemblies; a multigrid level keeps its blocks unless geo_cache = 2 and
   // counts ASSEMBLIES of the finest level (its version stamp), not the preconditioner applications that ask.
   const bool may_keep = full ? c.tune.geo_cache == 1 : c.tune.geo_cache != 2;
@@ -255,7 +275,14 @@ void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_non
   if (pl.unconstrained_first) integrate_unconstrained_geometry(ctx, p);
   if (pl.geo == GeoFrom::Masked) mask(ctx, cset);
   // (a multigrid level that took its blocks from the cache has nothing else for the cell kernel to integrate)
-  if (mode != AsmMode::LevelGeometry || pl.geo == GeoFrom::Cell) run_cell_kernel(ctx, p, CellWork{pl.stores_uu, pl.geo == GeoFrom::Cell}, ctx->want_shat && mode != AsmMode::Rhs, cset, imex);
+  bool rows_uu = pl.rows_uu;
+  if (mode == AsmMode::Full) { // the tables of the row owners; without them (no full lattice) and without the path its point data goes
+    if (rows_uu && !assemble_rows_ensure(ctx)) rows_uu = false;
+    if (!rows_uu) { ctx->rows_pd.release(); ctx->rows_fe.release(); }
+    ctx->rows_state = rows_uu ? 1 : (pl.stores_uu && ctx->tune.asm_rows != 0 ? -1 : 0);
+    ctx->rows_why = rows_uu ? nullptr : (pl.rows_refused ? pl.rows_refused : "the velocity nodes are no full lattice");
+  }
+  if (mode != AsmMode::LevelGeometry || pl.geo == GeoFrom::Cell) run_cell_kernel(ctx, p, CellWork{pl.stores_uu, pl.geo == GeoFrom::Cell}, ctx->want_shat && mode != AsmMode::Rhs, cset, imex, rows_uu);
   if (pl.geo != GeoFrom::Kept) ctx->geo.valid = true; // (commit_assembly cleared it if the blocks were to be replaced: a launch that threw leaves no set's blocks behind)
   assemble_epilogue(ctx, pl, cset);
   if (pl.lift) uu_lift_mf(ctx);

@@ -63,14 +63,7 @@ struct Cell4 {
   uint8_t hdr[kAsm3Hdr]; // perm[32] | iperm[32] | permp[8] | srow[32] (setup.hip::build_scat3)
 };
 
-// N_a(q) and the reference gradient of N_a at q from the tensor factors; q9 = (q % 9) * 9, q4 = (q / 9) * 4, a9 = a % 9, a3 = a / 9.
-// The z factor is zero for q = 27 and a >= 27 (padding of the MFMA tiles): no masks in the contraction.
-__device__ __forceinline__ void shape_ref4(const Tabs3 &T, int q9, int q4, int a9, int a3, double &N, double r[3]) {
-  const int i2 = q9 + a9, i1 = q4 + a3;
-  const double n2 = T.N2[i2], dx2 = T.DX2[i2], dy2 = T.DY2[i2], nz = T.Nz[i1], dz = T.dNz[i1];
-  N = n2 * nz;
-  r[0] = dx2 * nz; r[1] = dy2 * nz; r[2] = n2 * dz;
-}
+// (shape_ref4: assemble_common.hpp, shared with the row-owner kernel of assemble_rows.hip)
 __device__ __forceinline__ void shape_phys4(const Tabs3 &T, const double *Jq, int q9, int q4, int a9, int a3, double &N, double g[3]) {
   double r[3];
   shape_ref4(T, q9, q4, a9, a3, N, r);
@@ -412,10 +405,12 @@ __global__ __launch_bounds__(64 * CPB) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int i = 0; i < 9; ++i) {
       S.Ji[q * 9 + i] = Ji[i];
       S.gqs[q * 9 + i] = (A.imex ? 0.0 : A.rho * w * g[i]) + (((i == 0 || i == 4 || i == 8) && !mass_s) ? rdtw : 0.0);
+      if (A.pd) A.pd[(cc * NQ + q) * 12 + 3 + i] = S.gqs[q * 9 + i];
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       S.rwu[q * 3 + c] = A.imex ? 0.0 : A.rho * w * u[c]; // only the matrix reads it (u . grad N_b): no convection in the IMEX matrix
+      if (A.pd) A.pd[(cc * NQ + q) * 12 + c] = S.rwu[q * 3 + c];
       double adv = 0, vc[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
@@ -603,6 +598,10 @@ __global__ __launch_bounds__(64 * CPB) __attribute__((amdgpu_waves_per_eu(2, 2))
   }
   wsync2();
   // ---- rhs scatter (unconstrained owned rows; constrained rows were handled with the diagonal)
+  if (A.fe_out) { // row owners (assemble_rows.hip) gather it
+    for (int i = lane; i < 96; i += 64) A.fe_out[cc * 96 + i] = i < ND ? S.fe[i] : 0.0;
+    return;
+  }
   for (int i = lane; i < ND; i += 64) {
     if (i < NU * DIM) {
       const int c = i / NU, a = i - c * NU;

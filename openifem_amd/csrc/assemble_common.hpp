@@ -48,6 +48,10 @@ struct AsmArgs {
                   // integrate them only where a constrained dof needs their entries for the right-hand side
   int skip_uu;    // geometry-only assembly (multigrid levels): the velocity-velocity block is neither integrated nor scattered
   int debug_skip; // measurement builds only (-DIFEM_ASM_PROBES, ifem_tuning::asm_skip): 1 = no A_uu scatter, 2 = no contraction either
+  double *pd;     // 3D Q2/Q1 cell kernel, optional output: the point data of the A_uu contraction, [cell][27 points][rwu 3 | gqs 9], for the
+                  // row-owner kernel (assemble_rows.hip); nullptr: not written
+  double *fe_out; // with pd: the cell's local right-hand side [cell][96] (velocity [c][a], pressure at 81 + b) goes there instead of being added to
+                  // rhs with atomics -- the row owners sum it in a fixed order
 };
 
 template <int DIM, typename R = double>
@@ -134,6 +138,16 @@ __device__ inline void wsync2() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// 3D Q2 (assemble3.hip, assemble_rows.hip): N_a(q) and the reference gradient of N_a at q from the tensor factors of Tabs3;
+// q9 = (q % 9) * 9, q4 = (q / 9) * 4, a9 = a % 9, a3 = a / 9.
+// The z factor is zero for q = 27 and a >= 27 (padding of the MFMA tiles): no masks in the contraction.
+__device__ __forceinline__ void shape_ref4(const Tabs3 &T, int q9, int q4, int a9, int a3, double &N, double r[3]) {
+  const int i2 = q9 + a9, i1 = q4 + a3;
+  const double n2 = T.N2[i2], dx2 = T.DX2[i2], dy2 = T.DY2[i2], nz = T.Nz[i1], dz = T.dNz[i1];
+  N = n2 * nz;
+  r[0] = dx2 * nz; r[1] = dy2 * nz; r[2] = n2 * dz;
 }
 
 inline void tab1d(Tab1D &t, int kv) {

@@ -669,6 +669,13 @@ struct ifem_ctx {
   ifem::DBuf<uint8_t> hdr3;
   ifem::DBuf<ifem::Tabs3> tabs3;
   bool hdr3_rows = false; // the headers carry the row alignments of the present A_uu row order
+  // row-owner assembly of A_uu (assemble_rows.hip): cell of every lattice cell (once per context); point data of the contraction,
+  // [cell][27][12], written by the cell launch of every such assembly and held only while the path is taken; state of the last full
+  // assembly (1: row owners ran, -1: refused, 0: none yet)
+  ifem::DBuf<int32_t> rows_cell_at;
+  ifem::DBuf<double> rows_pd, rows_fe; // (rows_fe: the cells' local right-hand sides [cell][96], summed by the owners in a fixed order)
+  int rows_state = 0;
+  const char *rows_why = nullptr; // the reason of a refusal
   // constraints (local dof numbering), sets 0 = zero, 1 = nonzero
   ifem::DBuf<uint8_t> is_c[2];
   ifem::DBuf<double> cval[2];

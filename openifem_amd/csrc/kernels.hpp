@@ -27,6 +27,12 @@ enum class AsmMode {
   Full,          // A_uu (or its matrix-free state), B, B^T, M_p, diag(M_u) and the right-hand side
   LevelGeometry, // B, B^T, M_p, diag(M_u) only: a multigrid level of the pressure Schur complement (no A_uu, no right-hand side state)
 };
+// row-owner assembly of A_uu on uniform 3D Q2 boxes (assemble_rows.hip): why a context cannot take it (nullptr: it can; reads only), its
+// tables (false: no full lattice), the launch after the cell launch that wrote A.pd
+struct AsmArgs;
+const char *assemble_rows_refusal(const ifem_ctx &c);
+bool assemble_rows_ensure(ifem_ctx *ctx);
+void launch_ins_assemble_rows(ifem_ctx *ctx, const AsmArgs &A);
 void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode);
 // the part of the argument block that the INS and the SCnsIM cell kernels share (AsmArgs, ScnsArgs: the same field names);
 // `cset`: the constraint object the scatter applies (0 / 1), -1: none
