@@ -363,6 +363,54 @@ int ifem_set_constraints(ifem_ctx *ctx, int which, int32_t n, const int32_t *dof
  * mpi_fluid_solver.cpp:140-152,182-184). */
 int ifem_set_hanging_constraints(ifem_ctx *ctx, int32_t n, const int32_t *dof, const int32_t *ptr, const int32_t *master,
                                  const double *weight);
+/* ---- Adaptive refinement (FluidSolver::refine_mesh, mpi_fluid_solver.cpp:416-488): error estimator and solution transfer.
+ *
+ * KellyErrorEstimator<dim>::estimate(dof_handler, face_quad_formula, {}, present_solution, estimated_error_per_cell, velocity mask)
+ * (:425-431) on the device, for every local cell K
+ *     eta_K = sqrt( h_K / 24 * sum_{F in dK} int_F sum_{c < dim} [d u_c / d n]^2 ds ),
+ * h_K = the cell diameter sqrt(sum_d h_d^2), [.] the difference of the normal derivative between K and the cell on the other side of F,
+ * integrated with QGauss<dim-1>(kv + 1) (face_quad_formula, mpi_fluid_solver.cpp:35); a boundary face contributes 0 (no Neumann map), no
+ * coefficient, strategy cell_diameter_over_24.  A face whose neighbours are finer is integrated subface by subface, each of the 2^(dim-1)
+ * subfaces with the quadrature mapped onto it: K's gradient at the mapped points, the child's on its own face; a fine cell next to a
+ * coarser one integrates its own face against the coarse cell's gradient at the matching points; every cell multiplies by its OWN h_K.
+ * The formula restates the documented behaviour of deal.II's estimator from memory -- deal.II is not part of this repository's reference
+ * tree (SURVEY marks such statements [3P-memory]); no number here was compared with a deal.II run.
+ * All arithmetic is fp64, there are no atomics: every cell evaluates all of its own face integrals (an interior face is evaluated from both
+ * sides), one wavefront per cell, so two calls on the same state return bitwise equal results.
+ *
+ * Scope: single-rank contexts whose cells are all axis-aligned boxes (uniform box meshes and the one-level refined boxes of the host
+ * mirror's distribute_dofs_refined_box), 2D and 3D, kv = 1 and 2.  Anything else is IFEM_E_BADPARAM with a message, before any launch.
+ *
+ * vec: any IFEM_VEC_* (refine_mesh passes IFEM_VEC_PRESENT); its velocity block is read.
+ * face_table: int32 [n_cells][2 dim][IFEM_FACE_STRIDE(dim)], IFEM_FACE_STRIDE = 1 + 2^(dim-1), built on the host (the host mirror's
+ *   make_face_table, host/refine.cpp; what cell->neighbor(f) / neighbor_is_coarser / neighbor_of_coarser_neighbor / has_children give
+ *   deal.II's estimator).  Faces are numbered as in ifem_mesh_desc::cell_face_bid: f = 2 d + side (x-, x+, y-, y+, z-, z+).  Per face:
+ *     [0]     kind | subface << 8: IFEM_FACE_BOUNDARY (no neighbour), IFEM_FACE_EQUAL, IFEM_FACE_COARSER (the neighbour is one level coarser
+ *             and this face is subface `subface` of ITS face), IFEM_FACE_FINER (2^(dim-1) neighbours behind this face)
+ *     [1 ...] the neighbour cell (EQUAL, COARSER: one entry) or the 2^(dim-1) finer cells in tangential-lexicographic order: bit t of the
+ *             position is the upper half along the t-th tangential direction, tangential directions in ascending order; unused entries -1
+ *   The same order numbers the subface of a COARSER entry.  NULL: the table of the previous call on this context (its device copy is kept).
+ * eta_host: [n_cells] or NULL; eta_device: NULL, or receives the context's device array of the result (valid until the next call). */
+#define IFEM_FACE_BOUNDARY 0
+#define IFEM_FACE_EQUAL 1
+#define IFEM_FACE_COARSER 2
+#define IFEM_FACE_FINER 3
+#define IFEM_FACE_STRIDE(dim) (1 + (1 << ((dim) - 1)))
+int ifem_kelly_estimate(ifem_ctx *ctx, int vec, const int32_t *face_table, double *eta_host, const double **eta_device);
+/* SolutionTransfer::interpolate for FE_Q (mpi_fluid_solver.cpp:449-481): every node of the mesh of `dst` receives the value the
+ * finite-element function `vec` of `src` has at that node -- a copy on unchanged cells, the parent's interpolant at the nodes of new
+ * children, the coinciding child node for a re-coarsened parent.  All dim velocity components and the pressure block of `vec` in dst are
+ * written.  The host builds the table (host/refine.cpp::make_transfer_table), one entry per velocity node and one per pressure node of dst:
+ *   *_cell: the cell of src whose closure holds the node (the lowest cell index if there are several)
+ *   *_pos:  the node's position in that cell in units of 1 / (2 deg) per direction, 0 ... 2 deg, packed x | y << 8 | z << 16
+ *           (deg = kv for velocity nodes, 1 for pressure nodes)
+ * The kernel evaluates the tensor-product Lagrange weights at those dyadic points: they are exact in binary and terms of weight 0 are
+ * skipped, so a node that exists in both meshes keeps its value bit for bit -- even where it is a hanging node of the new mesh: as the
+ * reference (:477-481), this entry does NOT call constraints.distribute afterwards.  Both contexts are alive during the call, on one
+ * device, single rank, same dim and kv; anything else, or a table entry out of range, is IFEM_E_BADPARAM before any launch. */
+int ifem_transfer_solution(ifem_ctx *src, ifem_ctx *dst, int vec, const int32_t *u_cell, const int32_t *u_pos, const int32_t *p_cell,
+                           const int32_t *p_pos);
+
 /* cell_property[*].indicator written by MPI::FSI::update_indicator (mpi_fsi.cpp:291-321); NULL = all 0 */
 int ifem_set_cell_fields(ifem_ctx *ctx, const int32_t *indicator);
 
@@ -763,7 +811,8 @@ int ifem_get_timing(ifem_ctx *ctx, ifem_timing *t);
 #define IFEM_KC_SCHUR_SETUP 14  /* geometry blocks, k_schur_numeric */
 #define IFEM_KC_OTHER 15        /* constraints, hanging nodes, halo packing */
 #define IFEM_KC_TPP 16          /* SCnsIM: k_tpp_numeric, the ILU(0) of T_pp (factorisation, level-scheduled triangular solves), its SpMV */
-#define IFEM_KC_COUNT 17
+#define IFEM_KC_REFINE 17       /* refine_mesh: k_kelly (error estimator), k_transfer_solution */
+#define IFEM_KC_COUNT 18
 typedef struct {
   int32_t family;   /* IFEM_KC_* */
   uint32_t scopes;  /* launch-wrapper calls logged (a scope may hold two launches, e.g. the two stages of a reduction) */

@@ -143,7 +143,7 @@ class KprofEntry(C.Structure):
     _fields_ = [("family", C.c_int32), ("scopes", C.c_uint32), ("ms", C.c_double), ("bytes", C.c_double), ("flops", C.c_double)]
 
 
-KC_COUNT = 17  # IFEM_KC_COUNT
+KC_COUNT = 18  # IFEM_KC_COUNT
 
 
 def kprof_end(L, ctx):
@@ -175,7 +175,10 @@ EXPORTS = ["ifem_last_error", "ifem_device_count", "ifem_default_solver_opts", "
            "ifem_test_mg_transfer", "ifem_test_mg_vec_kernel", "ifem_test_mg_lattice_transfer",
            "ifem_sa_set_wall_points", "ifem_sa_get_wall_distance", "ifem_sa_set_constraints", "ifem_sa_vec_set", "ifem_sa_vec_get",
            "ifem_sa_assemble", "ifem_sa_solve", "ifem_sa_newton_step", "ifem_sa_update_eddy_viscosity", "ifem_sa_export_csr",
-           "ifem_scnsex_setup", "ifem_scnsex_assemble_rhs", "ifem_scnsex_solve", "ifem_scnsex_step", "ifem_scnsex_export_csr"]
+           "ifem_scnsex_setup", "ifem_scnsex_assemble_rhs", "ifem_scnsex_solve", "ifem_scnsex_step", "ifem_scnsex_export_csr",
+           "ifem_kelly_estimate", "ifem_transfer_solution"]
+# face kinds of the table ifem_kelly_estimate takes (IFEM_FACE_*): [n_cells][2 dim][1 + 2^(dim-1)], entry 0 = kind | subface << 8
+FACE_BOUNDARY, FACE_EQUAL, FACE_COARSER, FACE_FINER = range(4)
 
 # the wall function of the Spalart-Allmaras model at a moving FSI wall (csrc/sa_wall.hip).  Kept apart from EXPORTS, whose "ifem_sa_" entries
 # are the entry points of csrc/sa.hip; load() and __graft_entry__.build() require both lists
@@ -330,6 +333,8 @@ def load():
     L.ifem_scnsex_step.argtypes = [C.c_void_p, C.POINTER(ScnsParams), C.c_double, C.c_int, C.POINTER(ScnsexStats)]
     L.ifem_scnsex_export_csr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_abi_sizeof.argtypes = [C.c_int]
+    L.ifem_kelly_estimate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifem_transfer_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifem_abi_sizeof.restype = C.c_int64
     _lib = L
     return L
@@ -783,6 +788,24 @@ class Context:
         dof, ptr = np.ascontiguousarray(dof, np.int32), np.ascontiguousarray(ptr, np.int32)
         master, weight = np.ascontiguousarray(master, np.int32), np.ascontiguousarray(weight, float)
         self._chk(self.L.ifem_set_hanging_constraints(self.h, len(dof), _ptr(dof), _ptr(ptr), _ptr(master), _ptr(weight)))
+
+    def kelly_estimate(self, vec=VEC_PRESENT, face_table=None, host=True):
+        """ifem_kelly_estimate: eta_K [n_cells] of the velocity block of `vec`.  face_table: int32 [n_cells, 2 dim, 1 + 2^(dim-1)] (the host
+        mirror's host.box_face_table / FluidSolver.face_table), None re-uses the table of the previous call.  host=False leaves the result on
+        the device and returns nothing."""
+        ft = None if face_table is None else np.ascontiguousarray(face_table, np.int32)
+        if ft is not None:
+            self._kelly_cells = ft.size // (2 * self.dim * (1 + 2 ** (self.dim - 1)))
+        out = np.zeros(getattr(self, "_kelly_cells", 0)) if host else None
+        self._chk(self.L.ifem_kelly_estimate(self.h, vec, _ptr(ft), _ptr(out), None))
+        return out
+
+    def transfer_solution(self, src, vec, u_cell, u_pos, p_cell, p_pos):
+        """ifem_transfer_solution: `vec` of this context := the finite-element function `vec` of Context `src` at this context's nodes; the
+        table (host.transfer_table): per velocity / pressure node of this context the cell of src and the packed position in it"""
+        t = [np.ascontiguousarray(a, np.int32) for a in (u_cell, u_pos, p_cell, p_pos)]
+        assert len(t[0]) == len(t[1]) == self.n_u // self.dim and len(t[2]) == len(t[3]) == self.n_local - self.n_u
+        self._chk(self.L.ifem_transfer_solution(src.h, self.h, vec, *[_ptr(a) for a in t]))
 
     def set_indicator(self, ind):
         ind = None if ind is None else np.ascontiguousarray(ind, np.int32)

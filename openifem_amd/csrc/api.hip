@@ -416,6 +416,29 @@ int ifem_set_hanging_constraints(ifem_ctx *ctx, int32_t n, const int32_t *dof, c
   IFEM_API_END
 }
 
+int ifem_kelly_estimate(ifem_ctx *ctx, int vec, const int32_t *face_table, double *eta_host, const double **eta_device) {
+  IFEM_API_BEGIN
+  if (!ctx) throw Error(IFEM_E_BADPARAM, "ifem_kelly_estimate: null context");
+  if (vec < 0 || vec >= IFEM_N_VECS) throw Error(IFEM_E_BADPARAM, "bad vector id");
+  IFEM_HIP_CHECK(hipSetDevice(ctx->device));
+  ifem::kelly_estimate(ctx, ctx->vec[vec].p, face_table);
+  if (eta_host && ctx->n_cells) {
+    IFEM_HIP_CHECK(hipMemcpyAsync(eta_host, ctx->kelly.eta.p, size_t(ctx->n_cells) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    IFEM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
+  if (eta_device) *eta_device = ctx->kelly.eta.p;
+  IFEM_API_END
+}
+
+int ifem_transfer_solution(ifem_ctx *src, ifem_ctx *dst, int vec, const int32_t *u_cell, const int32_t *u_pos, const int32_t *p_cell,
+                           const int32_t *p_pos) {
+  IFEM_API_BEGIN
+  if (vec < 0 || vec >= IFEM_N_VECS) throw Error(IFEM_E_BADPARAM, "bad vector id");
+  if (dst) IFEM_HIP_CHECK(hipSetDevice(dst->device));
+  ifem::transfer_solution(src, dst, vec, u_cell, u_pos, p_cell, p_pos);
+  IFEM_API_END
+}
+
 int ifem_mg_attach(ifem_ctx *fine, ifem_ctx *coarse, const ifem_mg_transfer *t) {
   IFEM_API_BEGIN
   if (!fine || !coarse || !t || fine == coarse) throw Error(IFEM_E_BADPARAM, "ifem_mg_attach: two contexts and a transfer table");
@@ -1758,7 +1781,7 @@ int ifem_kprof_end(ifem_ctx *ctx, ifem_kprof_entry *out, int32_t max_entries) {
 
 const char *ifem_kprof_family_name(int32_t family) {
   static const char *names[IFEM_KC_COUNT] = {"assemble_cells", "zero_fill", "spmv_uu", "spmv_b_bt", "mf_cell", "mf_gather", "spmv_sm", "spmv_mp",
-                                             "mdot", "maxpy", "vector_ops", "mg_transfer", "smoother_setup", "cg_recurrence", "schur_setup", "other", "tpp_ilu"};
+                                             "mdot", "maxpy", "vector_ops", "mg_transfer", "smoother_setup", "cg_recurrence", "schur_setup", "other", "tpp_ilu", "refine"};
   return family >= 0 && family < IFEM_KC_COUNT ? names[family] : "?";
 }
 

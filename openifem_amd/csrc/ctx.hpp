@@ -149,6 +149,9 @@ struct FeTables {
   double fw[9];
 };
 void build_fe_tables(FeTables &t, int dim, int kv);
+// the 1D pieces the tables above are products of: the k + 1 Lagrange polynomials on the nodes j / k and their derivatives at x; QGauss(n) on [0, 1]
+void fe_lagrange_1d(int k, double x, double *N, double *dN);
+void fe_gauss01(int n, double *x, double *w);
 
 struct Halo {
   int rank = 0, nranks = 1;
@@ -367,6 +370,21 @@ struct GeoCache {
   }
 };
 
+} // namespace ifem
+
+namespace ifem {
+// Kelly error estimator (kelly.hip): 1D tables of the face integrals, the face table of the last call, the result
+struct KellyTabs {
+  double dn[2][3];    // [side][i]  derivative of the 1D Lagrange polynomial i at the cell's face 0 / 1
+  double tv[3][3][3]; // [set][q][j] value of polynomial j at Gauss point g_q (set 0), at g_q / 2 (1), at (1 + g_q) / 2 (2): a whole face, its lower / upper subface
+  double w[3];        // Gauss weights on [0, 1]
+};
+struct KellyState {
+  int boxes = 0; // 0: not looked at yet, 1: every cell is an axis-aligned box, -1: some cell is not
+  DBuf<KellyTabs> tabs;
+  DBuf<int32_t> faces; // [n_cells][2 dim][IFEM_FACE_STRIDE(dim)]
+  DBuf<double> eta;    // [n_cells]
+};
 } // namespace ifem
 
 namespace ifem {
@@ -604,6 +622,7 @@ struct ifem_ctx {
   ifem::FsiState fsi; // solid + scratch of the device-side FSI inputs (fsi.hip)
   ifem::SaState sa;   // Spalart-Allmaras turbulence model on the velocity nodes (sa.hip)
   ifem::ExState ex;   // Fluid::MPI::SCnsEX: scalar node matrices of the explicit split solver (scnsex.hip)
+  ifem::KellyState kelly; // error estimator of refine_mesh (kelly.hip)
   // multigrid (ifem_mg_attach): the next coarser level (not owned) and the pressure transfers to it; per-level state of
   // the S_m V-cycle: 1/diag(S_m), largest eigenvalue of D^-1 S_m, scratch vectors [nPl]
   ifem_ctx *mg_coarse = nullptr;

@@ -38,6 +38,10 @@ static void gauss01(int n, double *x, double *w) {
     throw Error(IFEM_E_BADPARAM, "QGauss order unsupported");
 }
 
+// the two 1D ingredients for the readers that keep the tensor structure (kelly.hip)
+void fe_lagrange_1d(int k, double x, double *N, double *dN) { lagrange(k, x, N, dN); }
+void fe_gauss01(int n, double *x, double *w) { gauss01(n, x, w); }
+
 // tensor-product shapes of degree k at reference point xi; local index x-fastest
 static void tensor_shapes(int dim, int k, const double *xi, double *N, double *dN /*[a][dim]*/) {
   double n1[3][3], d1[3][3];

@@ -5,6 +5,7 @@
 #include <sstream>
 #include "insim.hpp"
 #include "multigrid.hpp"
+#include "refine.hpp"
 
 using namespace ifem_host;
 
@@ -352,6 +353,101 @@ int ifemx_refine_band(void *hv, int dir, double lo, double hi, int64_t *n_flagge
     if (h->dim == 2) run(*h->t2); else run(*h->t3);
   });
 }
+// ---- adaptive refinement (refine.hpp, FluidSolver::refine_mesh).  The first functions need no device.
+// the face table of ifem_kelly_estimate for the solver's DoF tables (after ifemx_setup_host_only / ifemx_setup): [n_cells][2 dim][1 + 2^(dim-1)]
+int ifemx_face_table(void *hv, int32_t *out) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto run = [&](auto &s, auto dimtag) {
+      const auto t = make_face_table<decltype(dimtag)::value>(s.get_triangulation(), s.dof_tables());
+      std::memcpy(out, t.data(), t.size() * sizeof(int32_t));
+    };
+    if (h->dim == 2) run(*h->s2, std::integral_constant<int, 2>()); else run(*h->s3, std::integral_constant<int, 3>());
+  });
+}
+// the same for any cells of the box reps x [p0, p1] given by their vertices alone (vcoords [n_cells][2^dim][dim])
+int ifemx_box_face_table(int dim, const int *reps, const double *p0, const double *p1, int64_t n_cells, const double *vcoords, int32_t *out) {
+  return guard([&] {
+    auto run = [&](auto dimtag) {
+      constexpr int D = decltype(dimtag)::value;
+      Triangulation<D> t;
+      t.is_box = true;
+      DoFTables<D> d;
+      for (int k = 0; k < D; ++k) { t.reps[k] = reps[k]; t.p0[k] = p0[k]; t.p1[k] = p1[k]; }
+      d.vcoords.assign(vcoords, vcoords + n_cells * (1 << D) * D);
+      const auto tab = make_face_table<D>(t, d);
+      std::memcpy(out, tab.data(), tab.size() * sizeof(int32_t));
+    };
+    if (dim == 2) run(std::integral_constant<int, 2>()); else if (dim == 3) run(std::integral_constant<int, 3>());
+    else throw std::invalid_argument("ifemx_box_face_table: dim 2 or 3");
+  });
+}
+// refine.hpp::mark_fixed_fraction on n float criteria: refine / coarsen [n]
+int ifemx_mark_fixed_fraction(const float *criteria, int64_t n, double top, double bottom, uint8_t *refine, uint8_t *coarsen) {
+  return guard([&] {
+    std::vector<uint8_t> r, c;
+    mark_fixed_fraction(std::vector<float>(criteria, criteria + n), top, bottom, r, c);
+    if (n) { std::memcpy(refine, r.data(), (size_t)n); std::memcpy(coarsen, c.data(), (size_t)n); }
+  });
+}
+// flags per ACTIVE cell of the handle's triangulation (n of them, *n_active tells how many there are when refine is NULL): the level caps
+// of refine.hpp::apply_level_caps (coarse cells are level base_level), then set_active_flags + execute_coarsening_and_refinement.  refine /
+// coarsen come back capped; coarse_flags [coarse cells] receives the new refine_flags (all 0 on a uniform box), *locally_refined the state.
+// The DoF tables are those of the old mesh until the next ifemx_setup_host_only / ifemx_setup.
+int ifemx_set_active_flags(void *hv, int64_t n, uint8_t *refine, uint8_t *coarsen, int base_level, int min_level, int max_level,
+                           uint8_t *coarse_flags, int *locally_refined, int64_t *n_active) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto run = [&](auto &tria, auto dimtag) {
+      if (n_active) *n_active = (int64_t)tria.n_active_cells_with_children();
+      if (!refine || !coarsen) return;
+      std::vector<uint8_t> r(refine, refine + n), c(coarsen, coarsen + n);
+      apply_level_caps<decltype(dimtag)::value>(tria, base_level, min_level, max_level, r, c);
+      tria.set_active_flags(r, c);
+      tria.execute_coarsening_and_refinement();
+      if (n) { std::memcpy(refine, r.data(), (size_t)n); std::memcpy(coarsen, c.data(), (size_t)n); }
+      if (coarse_flags)
+        for (size_t k = 0; k < tria.n_active_cells(); ++k) coarse_flags[k] = tria.locally_refined ? tria.refine_flags[k] : 0;
+      if (locally_refined) *locally_refined = tria.locally_refined ? 1 : 0;
+      if (n_active) *n_active = (int64_t)tria.n_active_cells_with_children();
+    };
+    if (h->dim == 2) run(*h->t2, std::integral_constant<int, 2>()); else run(*h->t3, std::integral_constant<int, 3>());
+  });
+}
+// refine.hpp::make_transfer_table from the DoF tables of `old_h` to those of `new_h` (two solvers on the same box, both set up):
+// u_cell / u_pos [velocity nodes of new_h], p_cell / p_pos [pressure nodes of new_h]
+int ifemx_transfer_table(void *old_hv, void *new_hv, int32_t *u_cell, int32_t *u_pos, int32_t *p_cell, int32_t *p_pos) {
+  auto *ho = static_cast<Handle *>(old_hv), *hn = static_cast<Handle *>(new_hv);
+  return guard([&] {
+    if (ho->dim != hn->dim) throw std::invalid_argument("ifemx_transfer_table: the solvers differ in dimension");
+    auto run = [&](auto &so, auto &sn, auto dimtag) {
+      TransferTable T;
+      make_transfer_table<decltype(dimtag)::value>(sn.get_triangulation(), so.dof_tables(), sn.dof_tables(), T);
+      auto cp = [](const std::vector<int32_t> &v, int32_t *dst) { if (!v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(int32_t)); };
+      cp(T.u_cell, u_cell); cp(T.u_pos, u_pos); cp(T.p_cell, p_cell); cp(T.p_pos, p_pos);
+    };
+    if (ho->dim == 2) run(*ho->s2, *hn->s2, std::integral_constant<int, 2>()); else run(*ho->s3, *hn->s3, std::integral_constant<int, 3>());
+  });
+}
+// FluidSolver::refine_mesh(min_grid_level, max_grid_level).  indicators / refine / coarsen (each may be NULL): per active cell of the
+// mesh BEFORE the call (ifemx_sizes gives their number), in the triangulation's active order; counts [4]: coarse cells refined, parents
+// un-refined, active cells afterwards, 1 when the mesh changed (the context was then re-created: ifemx_ctx gives the new one)
+int ifemx_refine_mesh(void *hv, unsigned min_grid_level, unsigned max_grid_level, double *indicators, uint8_t *refine, uint8_t *coarsen,
+                      int64_t *counts) {
+  auto *h = static_cast<Handle *>(hv);
+  return guard([&] {
+    auto run = [&](auto &s) {
+      s.refine_mesh(min_grid_level, max_grid_level);
+      const auto &R = s.last_refine;
+      if (indicators) std::memcpy(indicators, R.indicators.data(), R.indicators.size() * sizeof(double));
+      if (refine) std::memcpy(refine, R.refine_flags.data(), R.refine_flags.size());
+      if (coarsen) std::memcpy(coarsen, R.coarsen_flags.data(), R.coarsen_flags.size());
+      if (counts) { counts[0] = R.n_refined; counts[1] = R.n_coarsened; counts[2] = R.n_active_cells; counts[3] = R.changed ? 1 : 0; }
+    };
+    if (h->dim == 2) run(*h->s2); else run(*h->s3);
+  });
+}
+
 // hanging-node lines of the solver's DoF tables: sizes = [n_lines, n_entries]; then the arrays (dof [n], ptr [n + 1],
 // master / weight [n_entries]); any output may be NULL
 int ifemx_hanging_lines(void *hv, int64_t *sizes, int32_t *dof, int32_t *ptr, int32_t *master, double *weight) {

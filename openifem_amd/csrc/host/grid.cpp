@@ -97,8 +97,43 @@ std::array<double, dim> Triangulation<dim>::cell_center(size_t c) const {
   return x;
 }
 template <int dim>
+size_t Triangulation<dim>::n_active_cells_with_children() const {
+  size_t n = n_active_cells();
+  if (is_box && locally_refined)
+    for (uint8_t f : refine_flags) n += f ? size_t(NV - 1) : 0;
+  return n;
+}
+template <int dim>
+void Triangulation<dim>::set_active_flags(const std::vector<uint8_t> &refine, const std::vector<uint8_t> &coarsen) {
+  if (!is_box) throw std::runtime_error("set_active_flags: box triangulations only");
+  const size_t n = n_active_cells_with_children();
+  if (refine.size() != n || coarsen.size() != n) throw std::invalid_argument("set_active_flags: one flag per active cell");
+  active_refine_flags = refine;
+  active_coarsen_flags = coarsen;
+}
+template <int dim>
 void Triangulation<dim>::execute_coarsening_and_refinement() {
   if (!is_box) throw std::runtime_error("execute_coarsening_and_refinement: box triangulations only");
+  if (!active_refine_flags.empty()) { // flags per active cell -> flags per coarse cell
+    const size_t nc = n_active_cells();
+    const bool was = locally_refined && refine_flags.size() == nc;
+    std::vector<uint8_t> next(nc, 0);
+    size_t a = 0;
+    for (size_t c = 0; c < nc; ++c) {
+      if (was && refine_flags[c]) {
+        bool all = true;
+        for (int ch = 0; ch < NV; ++ch) all = all && active_coarsen_flags[a + ch] && !active_refine_flags[a + ch];
+        next[c] = all ? 0 : 1;
+        a += NV;
+      } else {
+        next[c] = active_refine_flags[a] ? 1 : 0;
+        a += 1;
+      }
+    }
+    refine_flags = next;
+    active_refine_flags.clear();
+    active_coarsen_flags.clear();
+  }
   bool any = false;
   for (uint8_t f : refine_flags) any = any || f;
   locally_refined = any;

@@ -46,6 +46,16 @@ struct Triangulation {
   void set_refine_flag(size_t coarse_cell);
   std::array<double, dim> cell_center(size_t coarse_cell) const;
   void execute_coarsening_and_refinement();
+  // Re-flagging a box that may already be refined (FluidSolver::refine_mesh, mpi_fluid_solver.cpp:431-468): what the reference's active
+  // cell iterators give -- cell->set_refine_flag() / set_coarsen_flag() per ACTIVE cell, in the order of distribute_dofs_refined_box
+  // (coarse cells x fastest, the 2^dim children of a refined cell in its place, x fastest).  execute_coarsening_and_refinement() then
+  // turns them into the new per-coarse-cell refine_flags: an unrefined coarse cell is refined when it carries the refine flag, a
+  // refined one is un-refined only when ALL its children carry the coarsen flag (prepare_coarsening_and_refinement); refine flags on
+  // children and coarsen flags on coarse cells have no effect (one level).  A mesh without any refined cell left is a uniform box
+  // again: locally_refined = false, refine_flags cleared.
+  std::vector<uint8_t> active_refine_flags, active_coarsen_flags; // empty: none set
+  size_t n_active_cells_with_children() const; // n_active_cells() counts coarse cells only
+  void set_active_flags(const std::vector<uint8_t> &refine, const std::vector<uint8_t> &coarsen);
 };
 
 // hanging-node lines x[dof] = sum_k weight[k] x[master[k]], k in [ptr[i], ptr[i+1]), in the block numbering

@@ -135,6 +135,20 @@ public:
   void setup_dofs();
   void make_constraints();
   virtual void initialize_system();
+  // FluidSolver::refine_mesh (mpi_fluid_solver.cpp:416-488; protected there, public here for the tests): Kelly estimator on the
+  // velocity of present_solution (ifem_kelly_estimate), the fixed-fraction marking rule and level caps of refine.hpp, the new flags, then
+  // setup_dofs / make_constraints / initialize_system and the transfer of present_solution (ifem_transfer_solution).  Box
+  // triangulations on one rank, ONE level of local refinement (children are never refined again: the reference's cap is g + 3).
+  // New flags equal to the old ones: returns before setup_dofs and leaves the context untouched.
+  void refine_mesh(const unsigned int min_grid_level, const unsigned int max_grid_level);
+  // why this solver does not refine (non-box mesh, several ranks, turbulence model, SCnsEX, InsIMEX), or nullptr
+  virtual const char *refine_mesh_refusal() const;
+  struct RefineReport {
+    std::vector<double> indicators;                 // eta_K per active cell of the mesh BEFORE the call, in the triangulation's active order
+    std::vector<uint8_t> refine_flags, coarsen_flags; // per active cell, after the level caps
+    int64_t n_refined = 0, n_coarsened = 0, n_active_cells = 0; // coarse cells refined / un-refined; active cells afterwards
+    bool changed = false;
+  } last_refine;
   // counters of the most recent run_one_step (the reference prints them per iteration: " ITR = .. GMRES_ITR = ..")
   unsigned int last_newton_iterations = 0, last_fgmres_iterations = 0;
 
@@ -152,9 +166,11 @@ protected:
   bool attach_nested_levels(); // unstructured meshes with a refinement history (cylinder under refine_global), single rank
   std::unique_ptr<Triangulation<dim>> mg_tria;        // declared before mg_coarse: destroyed after it
   std::unique_ptr<FluidSolver<dim>> mg_coarse;        // the next coarser level (its context borrows this one's stream)
-  // refine_mesh (mpi_fluid_solver.cpp:418-488, called from run_one_step when time_to_refine() fires in a pure-fluid run,
-  // mpi_insim.cpp:485-489) is not part of the host mirror: stop with a message instead of computing on another mesh
-  void refine_mesh_not_supported() const;
+  // `if (simulation_type == "Fluid" && time.time_to_refine()) refine_mesh(g, g + 3)` at the end of run_one_step (mpi_insim.cpp:485-489,
+  // mpi_supg_solver.cpp:420-424) with g = global_refinements[0]; the cases the mirror does not refine (refine_mesh_refusal) stop with
+  // a message instead of computing on another mesh than the reference
+  void refine_mesh_on_schedule();
+  void refine_mesh_not_supported(const char *why = nullptr) const;
   Triangulation<dim> &triangulation;
   Parameters::AllParameters parameters;
   DoFTables<dim> dofs;
@@ -199,6 +215,11 @@ protected:
   }
 
 private:
+  // initialize_system replaced these solver_opts by the multigrid defaults when levels attached; a later initialize_system without
+  // levels (refine_mesh) puts them back
+  bool mg_defaults_taken = false;
+  int saved_ainv_kind = 0, saved_inner_restart = 0;
+  double saved_inner_rel_first = 0;
   using FluidSolver<dim>::parameters;
   using FluidSolver<dim>::time;
   using FluidSolver<dim>::ctx;
@@ -214,6 +235,7 @@ public:
   void run() override;
   void run_one_step(bool apply_nonzero_constraints, bool assemble_system = true) override;
   void initialize_system() override;
+  const char *refine_mesh_refusal() const override;
   void assemble(bool use_nonzero_constraints, bool assemble_system);
   std::pair<unsigned int, double> solve(bool use_nonzero_constraints, bool assemble_system);
   void assemble(bool use_nonzero_constraints) { assemble(use_nonzero_constraints, true); }
@@ -294,6 +316,7 @@ public:
   void run() override;
   void run_one_step(bool apply_nonzero_constraints, bool assemble_system = true) override;
   void initialize_system() override;
+  const char *refine_mesh_refusal() const override;
   // the time after which the hard coded values of boundary `id` are no longer re-evaluated (mpi_scnsex.cpp:84-97)
   void set_hard_coded_boundary_condition_time(const unsigned int id, const double time);
   ifem_scns_params scns_params() const;

@@ -79,8 +79,11 @@ void SCnsEX<dim>::run_one_step(bool apply_nonzero_constraints, bool assemble_sys
   check(ifem_update_stress(ctx, parameters.viscosity, nullptr), "update_stress"); // (:505)
   if (this->output_enabled && time.time_to_output()) this->output_results(time.get_timestep());                      // (:507-510)
   if (parameters.simulation_type == "Fluid" && time.time_to_save()) this->save_checkpoint((int)time.get_timestep()); // (:512-515)
-  this->refine_mesh_not_supported();                                                                                 // (:516-520)
+  this->refine_mesh_on_schedule(); // (:516-520; SCnsEX keeps the refusal: refine_mesh_refusal)
 }
+
+template <int dim>
+const char *SCnsEX<dim>::refine_mesh_refusal() const { return "the SCnsEX entry points refuse hanging nodes"; }
 
 template <int dim>
 void SCnsEX<dim>::run() {

@@ -68,7 +68,7 @@ void SUPGFluidSolver<dim>::run_one_step(bool apply_nonzero_constraints, bool ass
   check(ifem_update_stress(ctx, parameters.viscosity, nullptr), "update_stress");
   if (parameters.simulation_type == "Fluid" && time.time_to_save()) this->save_checkpoint((int)time.get_timestep()); // (:416-419)
   if (this->output_enabled && time.time_to_output()) this->output_results(time.get_timestep());
-  this->refine_mesh_not_supported(); // (mpi_supg_solver.cpp:420-424)
+  this->refine_mesh_on_schedule(); // (mpi_supg_solver.cpp:420-424)
 }
 
 template <int dim>

@@ -267,6 +267,10 @@ void bilu_apply(ifem_ctx *ctx, BIlu &I, int sweeps, const double *x, double *y);
 void rowsum_abs_inv(ifem_ctx *ctx, double *out);
 void scns_refpc_setup(ifem_ctx *ctx, int verbose, bool *pvv_ok, bool *b2_ok);
 void scns_pc_probe(ifem_ctx *ctx, int which, const double *x, double *y);
+// kelly.hip, transfer.hip -- the two device passes of FluidSolver::refine_mesh (ifem_hip.h: ifem_kelly_estimate, ifem_transfer_solution)
+void kelly_estimate(ifem_ctx *ctx, const double *x, const int32_t *face_table); // result in ctx->kelly.eta
+void transfer_solution(ifem_ctx *src, ifem_ctx *dst, int vec, const int32_t *u_cell, const int32_t *u_pos, const int32_t *p_cell,
+                       const int32_t *p_pos);
 // hanging-node lines (hanging.hip): C x on a copy of x, C^T and the hanging rows on y, distribute, set-up
 void hanging_set(ifem_ctx *ctx, int32_t n, const int32_t *dof, const int32_t *ptr, const int32_t *master, const double *weight);
 const double *hanging_input(ifem_ctx *ctx, const double *x); // ghost-extended [u_l | p_l] copy of x with C applied

@@ -84,6 +84,13 @@ def _lib():
     L.ifemx_turbulence_update_moving_wall_distance.argtypes = [C.c_void_p, C.POINTER(capi.FsiSolid), C.POINTER(capi.SaWall), C.c_void_p]
     L.ifemx_turbulence_update_boundary_condition.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.ifemx_turbulence_get_shear_velocity.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    L.ifemx_face_table.argtypes = [C.c_void_p, C.c_void_p]
+    L.ifemx_box_face_table.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.ifemx_mark_fixed_fraction.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    L.ifemx_set_active_flags.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.ifemx_transfer_table.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 4
+    L.ifemx_refine_mesh.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifemx_channel_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_double]
     L._ifemx_bound = True
     return L
@@ -255,6 +262,41 @@ class FluidSolver:
         n = C.c_int64(0)
         self._chk(self.L.ifemx_refine_band(self.h, int(direction), float(lo), float(hi), C.byref(n)))
         return n.value
+
+    # ---- adaptive refinement (csrc/host/refine.hpp)
+    def face_table(self):
+        """the face table of ifem_kelly_estimate for this solver's cells, int32 [n_cells, 2 dim, 1 + 2^(dim-1)] (after setup_host_only())"""
+        out = np.zeros((self.sizes()[0], 2 * self.dim, 1 + 2 ** (self.dim - 1)), np.int32)
+        self._chk(self.L.ifemx_face_table(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def n_active_cells(self):
+        """active cells of the triangulation (children counted), before or after setup"""
+        n = C.c_int64(0)
+        self._chk(self.L.ifemx_set_active_flags(self.h, 0, None, None, 0, 0, 0, None, None, C.byref(n)))
+        return n.value
+
+    def set_active_flags(self, refine, coarsen, base_level=0, min_level=0, max_level=1 << 20):
+        """cell->set_refine_flag() / set_coarsen_flag() per ACTIVE cell (coarse cells x fastest, children in place), the level caps of
+        refine_mesh (coarse cells are level base_level) and execute_coarsening_and_refinement.  Returns (refine, coarsen) as capped, the
+        new per-coarse-cell refine flags and whether the mesh is locally refined; call setup_host_only() / setup() afterwards."""
+        r, c = np.array(refine, np.uint8), np.array(coarsen, np.uint8)
+        assert len(r) == len(c)
+        coarse = np.zeros(int(np.prod(self.reps)), np.uint8)
+        lr, n = C.c_int(0), C.c_int64(0)
+        self._chk(self.L.ifemx_set_active_flags(self.h, len(r), r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), base_level,
+                                                min_level, max_level, coarse.ctypes.data_as(C.c_void_p), C.byref(lr), C.byref(n)))
+        return r, c, coarse, bool(lr.value)
+
+    def refine_mesh(self, min_grid_level, max_grid_level):
+        """FluidSolver::refine_mesh: dict(indicators, refine, coarsen: per active cell of the mesh before the call, in the triangulation's
+        active order; n_refined, n_coarsened, n_active_cells, changed).  A changed mesh re-creates the context: self.ctx follows."""
+        n = self.sizes()[0]
+        eta, r, c = np.zeros(n), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        counts = np.zeros(4, np.int64)
+        self._chk(self.L.ifemx_refine_mesh(self.h, int(min_grid_level), int(max_grid_level), *[a.ctypes.data_as(C.c_void_p) for a in (eta, r, c, counts)]))
+        return dict(indicators=eta, refine=r, coarsen=c, n_refined=int(counts[0]), n_coarsened=int(counts[1]), n_active_cells=int(counts[2]),
+                    changed=bool(counts[3]))
 
     def hanging_lines(self):
         """(dof, ptr, master, weight) of the hanging-node lines the host mirror made for a locally refined mesh"""
@@ -447,6 +489,43 @@ class FluidSolver:
         if rc < 0:
             raise HostError(rc, self.L.ifem_last_error().decode())
         return t
+
+
+def box_face_table(reps, p0, p1, vcoords):
+    """refine.hpp::make_face_table for any cells of the box reps x [p0, p1] given by their vertices [n_cells, 2^dim, dim] (no solver, no
+    device): int32 [n_cells, 2 dim, 1 + 2^(dim-1)], the layout of ifem_kelly_estimate"""
+    L = _lib()
+    dim = len(reps)
+    vc = np.ascontiguousarray(vcoords, float)
+    n = vc.size // (2 ** dim * dim)
+    r, a, b = np.ascontiguousarray(reps, np.int32), np.ascontiguousarray(p0, float), np.ascontiguousarray(p1, float)
+    out = np.zeros((n, 2 * dim, 1 + 2 ** (dim - 1)), np.int32)
+    rc = L.ifemx_box_face_table(dim, *[x.ctypes.data_as(C.c_void_p) for x in (r, a, b)], n, vc.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise HostError(rc, L.ifemx_last_error().decode())
+    return out
+
+
+def mark_fixed_fraction(criteria, top=0.6, bottom=0.4):
+    """refine.hpp::mark_fixed_fraction on the criteria rounded to float: (refine, coarsen) flags"""
+    L = _lib()
+    cr = np.ascontiguousarray(criteria, np.float32)
+    r, c = np.zeros(len(cr), np.uint8), np.zeros(len(cr), np.uint8)
+    rc = L.ifemx_mark_fixed_fraction(cr.ctypes.data_as(C.c_void_p), len(cr), top, bottom, r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise HostError(rc, L.ifemx_last_error().decode())
+    return r, c
+
+
+def transfer_table(old, new):
+    """refine.hpp::make_transfer_table between two set-up solvers on the same box: (u_cell, u_pos, p_cell, p_pos) per node of `new`"""
+    L = _lib()
+    _, n_u, n_p = new.sizes()
+    t = [np.zeros(n_u // new.dim, np.int32), np.zeros(n_u // new.dim, np.int32), np.zeros(n_p, np.int32), np.zeros(n_p, np.int32)]
+    rc = L.ifemx_transfer_table(old.h, new.h, *[a.ctypes.data_as(C.c_void_p) for a in t])
+    if rc < 0:
+        raise HostError(rc, L.ifemx_last_error().decode())
+    return tuple(t)
 
 
 def coarse_level_chain(cells_per_rank, P, extent, min_cells=4):
