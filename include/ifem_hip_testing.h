@@ -44,6 +44,12 @@ int ifem_test_mf_uniform(ifem_ctx *ctx, double *h);
  * a refusal is named in one line on stderr. */
 int ifem_test_asm_rows(ifem_ctx *ctx, int verbose, int32_t *state);
 
+/* The cell-independent terms of the element matrix that the row owners take from a table instead of contracting them (csrc/assemble_rows.hip,
+ * k_rows_const): runs the table kernel for the context's box and the parameters p and returns the table without its MFMA padding,
+ *   out[(a * 27 + b) * 9 + 3 c + d] = sum_q w_q (gamma rho d_c N_a d_d N_b + delta_cd mu grad N_a . grad N_b), imex != 0: + delta_cd rho/dt N_a N_b,
+ * a, b = local velocity nodes a_x + 3 a_y + 9 a_z.  Needs a created context of a uniform 3D Q2 box (IFEM_E_BADPARAM elsewhere), no assembly. */
+int ifem_test_rows_const(ifem_ctx *ctx, const ifem_ins_params *p, int imex, double *out /* 27*27*9 */);
+
 /* y_u = A_uu x_u on the velocity part of two context vectors as the single-precision inner solver of IFEM_AINV_MG forms the product
  * (ifem_tuning::inner_f32; solver.hip::uu_apply_f32col): x rounded to float, its ghost entries exchanged as float, single-precision
  * cell arithmetic, fp64 result.  After ifem_ins_assemble / ifem_imex_assemble.  Stages the column in a level vector of the A_uu V-cycle and

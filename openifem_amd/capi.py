@@ -185,6 +185,8 @@ FACE_BOUNDARY, FACE_EQUAL, FACE_COARSER, FACE_FINER = range(4)
 EXPORTS_SA_WALL = ["ifem_sa_set_moving_wall", "ifem_sa_set_shear_velocities", "ifem_sa_update_shear_velocity", "ifem_sa_get_shear_velocity", "ifem_sa_update_moving_wall_distance",
                    "ifem_sa_get_moving_wall", "ifem_sa_update_boundary_condition", "ifem_sa_get_constraints"]
 SA_NO_MOVING_WALL = np.finfo(float).max  # IFEM_SA_NO_MOVING_WALL
+# test aid of the row-owner assembly (csrc/assemble_rows.hip): the table of the cell-independent terms
+EXPORTS_ROWS_CONST = ["ifem_test_rows_const"]
 
 # ifem_solver_opts::sm_mg: plain CG | multigrid-preconditioned CG (the default) | the fast-diagonalisation solve where the level qualifies, SM_MG elsewhere
 SM_CG, SM_MG, SM_DIRECT = 0, 1, 2
@@ -283,6 +285,7 @@ def load():
     L.ifem_test_restart_fits.argtypes = [C.c_void_p, C.c_int]
     L.ifem_test_mf_uniform.argtypes = [C.c_void_p, C.c_void_p]
     L.ifem_test_asm_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.ifem_test_rows_const.argtypes = [C.c_void_p, C.POINTER(InsParams), C.c_int, C.c_void_p]
     L.ifem_test_uu_vmult_f32col.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_vmult.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ifem_test_uu_patch_info.argtypes = [C.c_void_p, C.c_void_p]
@@ -641,6 +644,12 @@ class Context:
         st = C.c_int32(0)
         self._chk(self.L.ifem_test_asm_rows(self.h, int(verbose), C.byref(st)))
         return int(st.value)
+
+    def rows_const(self, params, imex=False):
+        """the cell-independent terms of the element matrix as the row owners tabulate them, [a 27][b 27][c 3][d 3] -- ifem_test_rows_const"""
+        out = np.zeros(27 * 27 * 9)
+        self._chk(self.L.ifem_test_rows_const(self.h, C.byref(params), int(imex), _ptr(out)))
+        return out.reshape(27, 27, 3, 3)
 
     def uu_stored_bytes(self):
         """device bytes currently allocated for A_uu values (0: ifem_tuning::stored_uu = 0 has kept no block CSR)"""

@@ -1737,6 +1737,13 @@ int ifem_test_asm_rows(ifem_ctx *ctx, int verbose, int32_t *state) {
   return IFEM_OK;
 }
 
+int ifem_test_rows_const(ifem_ctx *ctx, const ifem_ins_params *p, int imex, double *out) {
+  IFEM_API_BEGIN
+  if (!p || !out) throw Error(IFEM_E_BADPARAM, "ifem_test_rows_const: null argument");
+  ifem::rows_const_table(ctx, p, imex, out);
+  IFEM_API_END
+}
+
 int ifem_inner_restart_length(ifem_ctx *ctx) { return ctx ? ctx->inner_restart_eff : IFEM_E_BADPARAM; }
 
 int ifem_vcycle_graph_stats(ifem_ctx *ctx, uint64_t *captures, uint64_t *launches) {

@@ -129,7 +129,8 @@ static void run_cell_kernel(ifem_ctx *ctx, const ifem_ins_params *p, CellWork w,
   // written once, the right-hand side, per cell the mesh tables and the three nodal vectors it gathers; flops of the
   // component-block form: per (node pair, point) dim^2 (2 FMA) + dim (2 FMA) + 5 products (53 flop in 3D), per (velocity
   // node, pressure node, point) 2 (1 + dim) when B / B^T / M_p are integrated.  MFMA padding is not counted.  Row owners: the same
-  // values and flops from two launches, plus the point data written once by the cells and read once by its owners.
+  // values and flops from two launches, plus the point data written once by the cells and read once by its owners.  (The flops stay the
+  // algorithmic ones: the row owners no longer execute the cell-independent terms, which they take from a table, assemble_rows.hip.)
   const int nd = ctx->nu * dim + ctx->np, npc = 1 << dim;
   const double pair = 2.0 * (2 * dim * dim + 2 * dim) + 5.0; // 24 FMA + 5 products in 3D
   KScope ks_asm(ctx, IFEM_KC_ASSEMBLE, 8.0 * (nuu + 2.0 * (npd + (rows_uu ? 96.0 * double(ctx->n_cells) : 0.0)) + ngeo + double(ctx->nUo) * dim + double(ctx->nPo)) + double(ctx->n_cells) * (npc * dim * 8.0 + (ctx->nu + ctx->np) * 4.0 + 3.0 * nd * 8.0),

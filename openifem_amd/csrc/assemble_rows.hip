@@ -3,16 +3,24 @@
 // assemble3.hip lets one wavefront integrate one cell and add its 27 x 27 blocks to rows it shares with up to 7 other cells: 871 atomic
 // requests per cell on an array that has to be zero before.  Here one wavefront owns the at most 8 lattice nodes of an owner
 // (assemble_rows.hpp) and integrates, for each of their rows, the contribution of every cell that touches the row: 27 (row node, cell) pairs
-// with the 27 column nodes of the pair's cell -- the shape of the one-cell contraction, 588 MFMAs.  Nobody else writes these rows: each
-// one is summed in an LDS image of its memory and leaves once, complete, as plain contiguous stores.  No atomics on A_uu, no zero fill,
-// and the same bits on every run.
+// with the 27 column nodes of the pair's cell -- the shape of the one-cell contraction.  Nobody else writes these rows: each one is summed
+// in an LDS image of its memory and leaves once, complete, as plain contiguous stores.  No atomics on A_uu, no zero fill, and the same
+// bits on every run.
 //
 // What makes the 16 rows of one MFMA come from different cells: on a uniform box (ifem_ctx::mf_uniform) J^-1 = diag(1 / h) and
 // JxW = prod(h) w_q are launch constants, so the B operand (gradient or value of the column node) is the same for every cell; only the
-// point data rho JxW u (3) and rho JxW grad u + rho/dt JxW (9) differ per row, and lane l reads them from the cell of ITS row.  The cell
-// kernel computes them anyway in the launch that integrates the right-hand side (AsmArgs::pd, 27 x 12 doubles per cell, one definition of
-// their scaling); lanes read them from there in every K-step (L2: the 8 cells of an owner are 21 KB, shared with the neighbouring owners --
-// staging them in LDS beside the row image would cost the second wavefront per SIMD).
+// point data rho JxW u (3) and rho JxW grad u + rho/dt JxW (9) differ per row.  The cell kernel computes them anyway in the launch that
+// integrates the right-hand side (AsmArgs::pd, 27 x 12 doubles per cell, one definition of their scaling).
+//
+// For the same reason the viscous and the grad-div term (and the mass term of the IMEX matrix) are the same 27 x 27 x 9 numbers in every
+// cell: a small kernel tabulates them ahead of every launch (k_rows_const, 64.5 KB, L2) and the accumulators of a contraction start
+// from the table rows of their pairs.  What is left to contract is the convective and the Newton term: 336 of the 588 MFMAs of the
+// one-cell contraction, and nothing at all for the IMEX matrix.
+//
+// The point data of a K-step (4 points of the owner's 8 cells, 3 KB) are loaded once by the wave, one K-step ahead, and handed to the
+// lanes through LDS, in the room of the row image, which is dead while a contraction runs; the local right-hand sides of the owner's
+// cells come into LDS with the block positions in the round of loads before the first contraction.  (Handing every XCD one contiguous
+// range of owners, ctx.hpp::xcd_swizzle, measured 0.4 ms of 70 at 128^3, inside the run-to-run spread: the owners keep the block order.)
 //
 // Constraints: distribute_local_to_global(..., true) as assemble3.hip::row_tile applies it, per (row, cell) contribution BEFORE it is
 // added to the image.  The right-hand side entries of an owned node belong to this wavefront: the terms of its constrained rows and
@@ -43,16 +51,25 @@ struct RowArgs {
   const int32_t *pnode_of_lattice; // PLattice: the pressure node of owner (i, j, k)
   int64_t p_off_c, p_off_rhs;     // first pressure entry of the constraint arrays / of rhs
   const Tabs3 *tabs3;
+  const double *k0;               // the constant terms of the element matrix, [a 28][e 9][b 32] (k_rows_const)
   double ih[3], vol;
   double mu, rho, gamma, inv_dt;
   int use_inhom, imex;
 };
 
 // per-owner LDS of one wavefront
-struct RowWave {
+struct alignas(16) RowWave {
   static constexpr int IMG = 1128; // the longest row (125 blocks of 9) + its alignment double, rounded to 16 bytes
-  double img[IMG];
-  double wq[28];       // JxW of the points, 0 for the padding point
+  // The staged point data of a contraction share the room of the row image: the image is dead while a contraction runs (every node_rows
+  // ends behind a wsync2 after its stores have read the image, contract<1> starts after that, and contract<0> before the first image).
+  // The other way round nothing stands between the last reads of pq in K-step 6 and the zeroing of the next image but program order:
+  // the LDS operations of one wave execute in order, and both go through this union, so the compiler cannot tell them apart and move
+  // one past the other.  Whoever gives the two members separate, restrict-qualified paths owes the end of contract a wsync2.
+  union {
+    double img[IMG];
+    d2 pq[2][8][24];   // [K-step parity][cell slot = cell bits][points 4 ks .. 4 ks + 3][rwu 3 | gqs 9], in pairs of doubles
+  };
+  double fe[27 * 3 + 8]; // local right-hand sides of the pairs' cells: velocity [pair][c], then the vertex's pressure entry of cell slot 0..7
   double part[4 * 3];  // right-hand side terms of the row groups of one node
   int64_t rs[8];       // first block of the rows of the owner's nodes (index: node bits), and their lengths in blocks
   int32_t len[8];
@@ -61,6 +78,7 @@ struct RowWave {
   uint8_t cm[128];     // constraint flags of the neighbourhood's nodes, bit c = component c
   uint16_t pos[27 * 27 + 7]; // [pair][column]: position of the block in its row (ifem_ctx::posUU of the pair's cell and local row)
   uint8_t pa[32];      // local index of the pair's row node in its cell, 27 (a zero row of the tile) without a cell
+  uint8_t pcb[32];     // cell bits of pair p = its cell slot: the pair's cell is pcell[pcb[p]], the cell of the vertex pair with these bits
 };
 
 struct RowAcc {
@@ -181,7 +199,7 @@ __device__ __forceinline__ void node_rows(const RowArgs &A, RowWave &S, const Ro
         for (int gg = G0; gg < G0 + NG; ++gg) {
           const int p = 16 * TI + gg + 4 * r;
           const int cell = S.pcell[p];
-          if (cell >= 0) v += A.fe[int64_t(cell) * 96 + lane * 27 + S.pa[p]];
+          if (cell >= 0) v += S.fe[p * 3 + lane];
         }
     }
     if (inh)
@@ -192,75 +210,136 @@ __device__ __forceinline__ void node_rows(const RowArgs &A, RowWave &S, const Ro
   wsync2();
 }
 
-// the contraction of row tile TI over the 27 points for both column tiles (assemble3.hip::row_tile with constant geometry and per-row point data)
+// The terms of the element matrix that do not depend on the cell: on a uniform box the viscous term w mu ga . gb, the grad-div term
+// gamma rho w ga_c gb_d and, in the IMEX matrix, the mass term rho/dt w N_a N_b are the same 27 x 27 x 9 numbers in every cell (in the
+// Newton matrix the mass term stays in the point data, where the Newton MFMAs carry it).  One lane per entry sums them over the 27 points
+// in point order, with the factors of the contraction (shape_ref4's products), into K0[a][e = 3 c + d][b]; row a = 27 and the columns
+// b >= 27 are zero, so that the padding rows and columns of an MFMA tile need no branch.  Runs ahead of every row launch: no state
+// (one workgroup of 1024 took 0.27 ms per launch, 32 of 256 take 0.012 ms: profiles/r18_assemble_rows.txt).
+constexpr int kK0Rows = 28, kK0Cols = 32, kK0 = kK0Rows * 9 * kK0Cols;
+
+__global__ __launch_bounds__(256) void k_rows_const(double *__restrict__ K0, Tab1D t, double ih0, double ih1, double ih2, double vol, double mu, double wgam,
+                                                     double rdt, int imex) {
+  const double ih[3] = {ih0, ih1, ih2};
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kK0; i += gridDim.x * blockDim.x) {
+    const int b = i % kK0Cols, e = (i / kK0Cols) % 9, a = i / (9 * kK0Cols);
+    const int c = e / 3, d = e - 3 * c;
+    double v = 0.0;
+    if (a < 27 && b < 27) {
+      const int ai[3] = {a % 3, (a / 3) % 3, a / 9}, bi[3] = {b % 3, (b / 3) % 3, b / 9};
+      for (int q = 0; q < 27; ++q) {
+        const int qi[3] = {q % 3, (q / 3) % 3, q / 9};
+        double w = vol;
+        for (int k = 0; k < 3; ++k) w *= t.w[qi[k]];
+        double ga[3], gb[3];
+        const double na2 = t.N[qi[0] * 3 + ai[0]] * t.N[qi[1] * 3 + ai[1]], nb2 = t.N[qi[0] * 3 + bi[0]] * t.N[qi[1] * 3 + bi[1]];
+        const double naz = t.N[qi[2] * 3 + ai[2]], nbz = t.N[qi[2] * 3 + bi[2]];
+        ga[0] = t.dN[qi[0] * 3 + ai[0]] * t.N[qi[1] * 3 + ai[1]] * naz * ih[0];
+        ga[1] = t.N[qi[0] * 3 + ai[0]] * t.dN[qi[1] * 3 + ai[1]] * naz * ih[1];
+        ga[2] = na2 * t.dN[qi[2] * 3 + ai[2]] * ih[2];
+        gb[0] = t.dN[qi[0] * 3 + bi[0]] * t.N[qi[1] * 3 + bi[1]] * nbz * ih[0];
+        gb[1] = t.N[qi[0] * 3 + bi[0]] * t.dN[qi[1] * 3 + bi[1]] * nbz * ih[1];
+        gb[2] = nb2 * t.dN[qi[2] * 3 + bi[2]] * ih[2];
+        double s = (w * wgam) * ga[c] * gb[d];
+        if (c == d) {
+          s += (w * mu) * (ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2]);
+          if (imex) s += (rdt * w) * (na2 * naz) * (nb2 * nbz);
+        }
+        v += s;
+      }
+    }
+    K0[i] = v;
+  }
+}
+
+static void rows_const_ensure(ifem_ctx *ctx) {
+  if (ctx->rows_k0.n != size_t(kK0)) ctx->rows_k0.alloc(size_t(kK0), "the constant terms of the row-owner assembly");
+}
+
+static void launch_rows_const(ifem_ctx *ctx, const double ih[3], double vol, double mu, double rho, double gamma, double inv_dt, int imex) {
+  Tab1D t;
+  tab1d(t, 2);
+  hipLaunchKernelGGL(k_rows_const, dim3(grid_for(kK0)), dim3(256), 0, ctx->stream, ctx->rows_k0.p, t, ih[0], ih[1], ih[2], vol, mu, gamma * rho, rho * inv_dt, imex);
+  IFEM_HIP_CHECK(hipGetLastError());
+}
+
+// The contraction of row tile TI over the 27 points for both column tiles (assemble3.hip::row_tile with constant geometry and per-row point
+// data).  The accumulators start from the constant terms K0 of their rows' local nodes; the K-loop adds what depends on the cell: the
+// convective term on the scalar part, the Newton term (with the mass term on its diagonal blocks) on the nine blocks.  The IMEX matrix has
+// neither: its blocks are the table.
 template <int TI>
-__device__ __forceinline__ void contract(const RowArgs &A, const Tabs3 &T, const RowWave &S, RowAcc &R, const int lane) {
+__device__ __forceinline__ void contract(const RowArgs &A, const Tabs3 &T, RowWave &S, RowAcc &R, const int lane) {
   constexpr int BS = 9;
   const int l15 = lane & 15, g = lane >> 4;
   const int b9_0 = l15 % 9, b3_0 = l15 / 9, b9_1 = (16 + l15) % 9, b3_1 = (16 + l15) / 9; // my column nodes (27..31: zero through the z factor)
   const int al = S.pa[16 * TI + l15];
   const int a9 = al % 9, a3 = al / 9;
-  const int cell = S.pcell[16 * TI + l15];
-  const double *const pd = A.pd + int64_t(cell < 0 ? 0 : cell) * (27 * 12);
-  const double wgam = A.gamma * A.rho, rdt = A.rho * A.inv_dt;
   R.sac0 = d4{0, 0, 0, 0}; R.sac1 = d4{0, 0, 0, 0};
 #pragma unroll
-  for (int e = 0; e < BS; ++e) { R.acc0[e] = d4{0, 0, 0, 0}; R.acc1[e] = d4{0, 0, 0, 0}; }
+  for (int r = 0; r < 4; ++r) { // rows g + 4 r of the tile: 128 contiguous bytes along l15
+    const double *const k = A.k0 + int(S.pa[16 * TI + g + 4 * r]) * (9 * kK0Cols) + l15;
+#pragma unroll
+    for (int e = 0; e < BS; ++e) { R.acc0[e][r] = k[e * kK0Cols]; R.acc1[e][r] = k[e * kK0Cols + 16]; }
+  }
+  if (A.imex) return;
+  // The point data of a K-step, 4 points of the owner's 8 cells, are loaded once by the wave: lane -> (cell slot, 48 of the slot's 384
+  // contiguous bytes), requested one K-step ahead and handed over through LDS; lane (g, l15) reads point g of the slot of row l15's cell.
+  // Cells the owner lacks and the padding point 27 give zeros (their rows / that point have N_a = 0: the values must only be finite).
+  const int lslot = lane >> 3, lch = lane & 7;
+  const int lcell = S.pcell[lslot]; // vertex pair s has cell bits s
+  const d2 *const src = reinterpret_cast<const d2 *>(A.pd + int64_t(lcell < 0 ? 0 : lcell) * (27 * 12)) + 3 * lch;
+  const int myslot = S.pcb[16 * TI + l15];
+  d2 nx[3];
+  auto request = [&](int ks) {
+    const bool on = lcell >= 0 && (ks < 6 || lch < 6); // K-step 6 holds the points 24, 25, 26: 36 of the 48 doubles
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nx[i] = on ? src[24 * ks + i] : d2{0, 0};
+  };
+  auto hand_over = [&](int half) {
+    d2 *const dst = &S.pq[half][lslot][3 * lch];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dst[i] = nx[i];
+    wsync2();
+  };
+  request(0);
+  hand_over(0);
 #pragma unroll 1
   for (int ks = 0; ks < 7; ++ks) {
     const int q = 4 * ks + g; // 27: the zero point
     const int q3 = q / 9, q9 = (q - q3 * 9) * 9, q4 = q3 * 4;
-    const double w = S.wq[q];
+    if (ks < 6) request(ks + 1);
     double pq[12];
+    {
+      const d2 *const mine = &S.pq[ks & 1][myslot][6 * g];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) pq[i] = 0.0;
-    if (!A.imex) { // (requesting all twelve one K-step ahead spills; four of them ahead measured no faster)
-      const d2 *src = reinterpret_cast<const d2 *>(pd + (q < 27 ? q : 26) * 12);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) { const d2 v = src[i]; pq[2 * i] = v.x; pq[2 * i + 1] = v.y; }
+      for (int i = 0; i < 6; ++i) { const d2 v = mine[i]; pq[2 * i] = v.x; pq[2 * i + 1] = v.y; }
     }
-    double Na, Nb0, Nb1, ga[3], gb0[3], gb1[3];
-    shape_ref4(T, q9, q4, a9, a3, Na, ga);
+    double Nb0, Nb1, gb0[3], gb1[3];
+    const double Na = T.N2[q9 + a9] * T.Nz[q4 + a3]; // zero for the padding point and the padding rows
     shape_ref4(T, q9, q4, b9_0, b3_0, Nb0, gb0);
     shape_ref4(T, q9, q4, b9_1, b3_1, Nb1, gb1);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) { ga[d] *= A.ih[d]; gb0[d] *= A.ih[d]; gb1[d] *= A.ih[d]; }
-    const double wmu = w * A.mu, wg = w * wgam;
-    // viscous + convective: sum_e (w mu ga_e + rho w u_e N_a) gb_e
+    for (int d = 0; d < 3; ++d) { gb0[d] *= A.ih[d]; gb1[d] *= A.ih[d]; }
+    // convective: sum_e rho w u_e N_a gb_e
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
-      const double av = pq[e] * Na + wmu * ga[e];
+      const double av = pq[e] * Na;
       R.sac0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, gb0[e], R.sac0, 0, 0, 0);
       R.sac1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, gb1[e], R.sac1, 0, 0, 0);
     }
-    // grad-div part of the nine blocks
+    // Newton term rho N_a N_b d_d u_c with the mass term on its diagonal blocks
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double wga = wg * ga[c];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        R.acc0[c * 3 + d] = __builtin_amdgcn_mfma_f64_16x16x4f64(wga, gb0[d], R.acc0[c * 3 + d], 0, 0, 0);
-        R.acc1[c * 3 + d] = __builtin_amdgcn_mfma_f64_16x16x4f64(wga, gb1[d], R.acc1[c * 3 + d], 0, 0, 0);
-      }
+    for (int e = 0; e < BS; ++e) {
+      const double an = Na * pq[3 + e];
+      R.acc0[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, Nb0, R.acc0[e], 0, 0, 0);
+      R.acc1[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, Nb1, R.acc1[e], 0, 0, 0);
     }
-    // Newton term rho N_a N_b d_d u_c with the mass term on its diagonal blocks; IMEX: the mass term alone, on the scalar part
-    if (!A.imex) {
-#pragma unroll
-      for (int e = 0; e < BS; ++e) {
-        const double an = Na * pq[3 + e];
-        R.acc0[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, Nb0, R.acc0[e], 0, 0, 0);
-        R.acc1[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, Nb1, R.acc1[e], 0, 0, 0);
-      }
-    } else {
-      const double am = rdt * w * Na;
-      R.sac0 = __builtin_amdgcn_mfma_f64_16x16x4f64(am, Nb0, R.sac0, 0, 0, 0);
-      R.sac1 = __builtin_amdgcn_mfma_f64_16x16x4f64(am, Nb1, R.sac1, 0, 0, 0);
-    }
+    if (ks < 6) hand_over((ks + 1) & 1); // the half that K-step ks - 1 read
   }
 }
 
 template <int WPB>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ins_assemble_rows(RowArgs A, Tab1D t1) {
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ins_assemble_rows(RowArgs A) {
   __shared__ Tabs3 T;
   __shared__ __align__(16) RowWave SW[WPB];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -275,57 +354,91 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
   RowWave &S = SW[wave];
   int ijk[3];
   rows::owner_ijk(owner, A.n, ijk);
+  // The set-up loads in batches: (1) the lattice nodes of the neighbourhood, the cells of the pairs, the pressure node; (2) what hangs
+  // on them -- constraint flags and row starts of the nodes, then block positions and local right-hand sides of the cells (as compiled
+  // the flags and row starts are waited for at the exchange of the cells through LDS: three rounds, where a loop per table made about 16).
+  // Every load of a batch is requested before the first one is used: straight-line code, the addresses of absent nodes and cells are
+  // clamped to entry 0 and the value is dropped.
+  int64_t at[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) at[u] = lane + 64 * u < 125 ? rows::nb_point(ijk, A.n, lane + 64 * u) : -1;
+  const rows::Pair P = rows::pair_of(lane < rows::kPairs ? lane : 0);
+  const int64_t cat = lane < rows::kPairs && rows::row_point(ijk, A.n, P.nd) >= 0 ? rows::pair_cell(ijk, A.n, P) : -1;
+  int32_t node[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) node[u] = A.node_of_lattice[at[u] < 0 ? 0 : at[u]];
+  int32_t mycell = A.cell_at[cat < 0 ? 0 : cat];
+  const int64_t pn = A.pnode_of_lattice[owner];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) if (at[u] < 0) node[u] = -1;
+  if (cat < 0) mycell = -1;
+  if (lane < 32) {
+    S.pcell[lane] = mycell;
+    S.pa[lane] = uint8_t(mycell >= 0 ? P.a : 27);
+    S.pcb[lane] = uint8_t(lane < rows::kPairs ? P.cb : 0);
+  }
+  uint8_t fl[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  uint8_t pfl = 0;
+  int64_t r0[2], r1[2];
+  if (A.is_c) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) fl[u][c] = A.is_c[int64_t(3) * (node[u] < 0 ? 0 : node[u]) + c];
+    pfl = A.is_c[A.p_off_c + pn];
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) { r0[u] = A.rp_uu[node[u] < 0 ? 0 : node[u]]; r1[u] = A.rp_uu[(node[u] < 0 ? 0 : node[u]) + 1]; }
+  wsync2();
+  constexpr int NPOS = (rows::kPairs * 27 + 63) / 64;
+  uint16_t pv[NPOS];
+#pragma unroll
+  for (int u = 0; u < NPOS; ++u) {
+    const int i = lane + 64 * u < rows::kPairs * 27 ? lane + 64 * u : rows::kPairs * 27 - 1;
+    const int p = i / 27;
+    const int cell = S.pcell[p];
+    pv[u] = A.posUU[(int64_t(cell < 0 ? 0 : cell) * 27 + (cell < 0 ? 0 : S.pa[p])) * 27 + (i - p * 27)];
+  }
+  double fv[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int i = lane + 64 * u < 27 * 3 + 8 ? lane + 64 * u : 27 * 3 + 7;
+    const int p = i < 81 ? i / 3 : i - 81; // velocity [pair][c]; pressure: vertex i - 81 of the cell of vertex pair i - 81
+    const int cell = S.pcell[p];
+    const double v = A.fe[int64_t(cell < 0 ? 0 : cell) * 96 + (i < 81 ? (i - 3 * p) * 27 + (cell < 0 ? 0 : S.pa[p]) : i)];
+    fv[u] = cell >= 0 ? v : 0.0;
+  }
   bool cmine = false;
-  for (int t = lane; t < 125; t += 64) {
-    const int64_t at = rows::nb_point(ijk, A.n, t);
-    const int32_t node = at >= 0 ? A.node_of_lattice[at] : -1;
-    unsigned mk = 0;
-    if (node >= 0 && A.is_c) mk = unsigned(A.is_c[int64_t(3) * node] != 0) | unsigned(A.is_c[int64_t(3) * node + 1] != 0) << 1 | unsigned(A.is_c[int64_t(3) * node + 2] != 0) << 2;
-    S.nb[t] = node;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int t = lane + 64 * u;
+    if (t >= 125) continue;
+    const unsigned mk = node[u] < 0 ? 0u : unsigned(fl[u][0] != 0) | unsigned(fl[u][1] != 0) << 1 | unsigned(fl[u][2] != 0) << 2;
+    S.nb[t] = node[u];
     S.cm[t] = uint8_t(mk);
     const int tx = t % 5 - 2, ty = (t / 5) % 5 - 2, tz = t / 25 - 2;
-    if (node >= 0 && (tx | ty | tz) >= 0 && tx < 2 && ty < 2 && tz < 2) { // one of the owner's own nodes: its row
-      const int64_t r0 = A.rp_uu[node];
-      S.rs[tx | ty << 1 | tz << 2] = r0;
-      S.len[tx | ty << 1 | tz << 2] = int32_t(A.rp_uu[node + 1] - r0);
+    if (node[u] >= 0 && (tx | ty | tz) >= 0 && tx < 2 && ty < 2 && tz < 2) { // one of the owner's own nodes: its row
+      S.rs[tx | ty << 1 | tz << 2] = r0[u];
+      S.len[tx | ty << 1 | tz << 2] = int32_t(r1[u] - r0[u]);
     }
     cmine = cmine || mk != 0;
   }
   const bool any_c = __any(cmine);
-  if (lane < 32) {
-    int64_t cell = -1;
-    int a = 27;
-    if (lane < rows::kPairs) {
-      const rows::Pair P = rows::pair_of(lane);
-      const int64_t at = rows::row_point(ijk, A.n, P.nd) >= 0 ? rows::pair_cell(ijk, A.n, P) : -1;
-      if (at >= 0) { cell = A.cell_at[at]; a = P.a; }
-    }
-    S.pcell[lane] = int32_t(cell);
-    S.pa[lane] = uint8_t(a);
-  } else if (lane < 32 + 28) {
-    const int q = lane - 32;
-    const int qi[3] = {q % 3, (q / 3) % 3, q / 9};
-    double wq = A.vol;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) wq *= t1.w[0] * (qi[d] == 0) + t1.w[1] * (qi[d] == 1) + t1.w[2] * (qi[d] == 2);
-    S.wq[q] = q < 27 ? wq : 0.0;
-  }
-  wsync2();
-  for (int i = lane; i < rows::kPairs * 27; i += 64) { // all positions in one round of loads, before the first contraction
-    const int p = i / 27;
-    const int cell = S.pcell[p];
-    if (cell >= 0) S.pos[i] = A.posUU[(int64_t(cell) * 27 + S.pa[p]) * 27 + (i - p * 27)];
-  }
+  for (int u = 0; u < NPOS; ++u)
+    if (lane + 64 * u < rows::kPairs * 27) S.pos[lane + 64 * u] = pv[u]; // (of a pair without a cell: never read)
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (lane + 64 * u < 27 * 3 + 8) S.fe[lane + 64 * u] = fv[u];
   RowAcc R;
   contract<0>(A, T, S, R, lane);
   node_rows<0, 0, 2, 0, 4>(A, S, R, lane, any_c); // vertex node: 8 cells
   if (lane == 0) { // the pressure row of the owner's vertex: vertex b of cell pair p, b = the pair's cell bits = p
-    const int64_t pn = A.pnode_of_lattice[owner];
-    if (!(A.is_c && A.is_c[A.p_off_c + pn])) {
+    if (!pfl) {
       double v = 0;
       for (int p = 0; p < 8; ++p) {
         const int cell = S.pcell[p];
-        if (cell >= 0) v += A.fe[int64_t(cell) * 96 + 81 + p];
+        if (cell >= 0) v += S.fe[81 + p];
       }
       A.rhs[A.p_off_rhs + pn] = v;
     }
@@ -365,7 +478,8 @@ const char *assemble_rows_refusal(const ifem_ctx &c) {
 #endif
 }
 
-// The tables of the path, once per context: the lattice (setup.hip::u_lattice_ensure) and the cell of every lattice cell.  false: no full lattice.
+// The tables of the path, once per context: the lattice (setup.hip::u_lattice_ensure), the cell of every lattice cell and the room of the
+// constant terms (filled by every launch).  false: no full lattice.
 bool assemble_rows_ensure(ifem_ctx *ctx) {
   if (!u_lattice_ensure(ctx)) return false;
   const ULattice &L = ctx->u_lattice;
@@ -378,6 +492,7 @@ bool assemble_rows_ensure(ifem_ctx *ctx) {
                        ctx->rows_cell_at.p);
     IFEM_HIP_CHECK(hipGetLastError());
   }
+  rows_const_ensure(ctx);
   return true;
 }
 
@@ -395,11 +510,24 @@ void launch_ins_assemble_rows(ifem_ctx *ctx, const AsmArgs &C) {
   A.pd = C.pd; A.fe = C.fe_out; A.tabs3 = ctx->tabs3.p;
   A.pnode_of_lattice = ctx->p_lattice.node_of_lattice.p; A.p_off_c = int64_t(3) * ctx->nUl; A.p_off_rhs = int64_t(3) * ctx->nUo;
   A.mu = C.mu; A.rho = C.rho; A.gamma = C.gamma; A.inv_dt = C.inv_dt; A.imex = C.imex;
-  if (!A.pd || !A.fe || !A.tabs3 || !A.cell_at || !A.pnode_of_lattice) throw Error(IFEM_E_BADPARAM, "row-owner assembly before its cell launch");
-  Tab1D t;
-  tab1d(t, 2);
-  hipLaunchKernelGGL((k_ins_assemble_rows<WPB>), dim3(unsigned((A.n_owners + WPB - 1) / WPB)), dim3(64 * WPB), 0, ctx->stream, A, t);
+  if (!A.pd || !A.fe || !A.tabs3 || !A.cell_at || !A.pnode_of_lattice || !ctx->rows_k0.p) throw Error(IFEM_E_BADPARAM, "row-owner assembly before its cell launch");
+  launch_rows_const(ctx, A.ih, A.vol, A.mu, A.rho, A.gamma, A.inv_dt, A.imex);
+  A.k0 = ctx->rows_k0.p;
+  hipLaunchKernelGGL((k_ins_assemble_rows<WPB>), dim3(unsigned((A.n_owners + WPB - 1) / WPB)), dim3(64 * WPB), 0, ctx->stream, A);
   IFEM_HIP_CHECK(hipGetLastError());
+}
+
+// test aid (ifem_test_rows_const): the table of the context's box for these parameters, without its padding, [a 27][b 27][e 9]
+void rows_const_table(ifem_ctx *ctx, const ifem_ins_params *p, int imex, double *out) {
+  if (ctx->dim != 3 || ctx->kv != 2 || !ctx->mf_uniform) throw Error(IFEM_E_BADPARAM, "ifem_test_rows_const: the context is no uniform 3D Q2 box");
+  double ih[3];
+  for (int d = 0; d < 3; ++d) ih[d] = 1.0 / ctx->mf_h[d];
+  rows_const_ensure(ctx);
+  launch_rows_const(ctx, ih, ctx->mf_h[0] * ctx->mf_h[1] * ctx->mf_h[2], p->viscosity, p->rho, p->grad_div, 1.0 / p->dt, imex);
+  const std::vector<double> k = ctx->rows_k0.download(ctx->stream);
+  for (int a = 0; a < 27; ++a)
+    for (int b = 0; b < 27; ++b)
+      for (int e = 0; e < 9; ++e) out[(a * 27 + b) * 9 + e] = k[(a * 9 + e) * kK0Cols + b];
 }
 
 } // namespace ifem

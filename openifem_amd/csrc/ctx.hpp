@@ -693,6 +693,7 @@ struct ifem_ctx {
   // assembly (1: row owners ran, -1: refused, 0: none yet)
   ifem::DBuf<int32_t> rows_cell_at;
   ifem::DBuf<double> rows_pd, rows_fe; // (rows_fe: the cells' local right-hand sides [cell][96], summed by the owners in a fixed order)
+  ifem::DBuf<double> rows_k0;          // the cell-independent terms of the element matrix, [a 28][e 9][b 32]; refilled by every row launch
   int rows_state = 0;
   const char *rows_why = nullptr; // the reason of a refusal
   // constraints (local dof numbering), sets 0 = zero, 1 = nonzero

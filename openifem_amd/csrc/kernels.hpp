@@ -33,6 +33,7 @@ struct AsmArgs;
 const char *assemble_rows_refusal(const ifem_ctx &c);
 bool assemble_rows_ensure(ifem_ctx *ctx);
 void launch_ins_assemble_rows(ifem_ctx *ctx, const AsmArgs &A);
+void rows_const_table(ifem_ctx *ctx, const ifem_ins_params *p, int imex, double *out); // test aid: the constant terms, [a 27][b 27][e 9]
 void launch_ins_assemble_ex(ifem_ctx *ctx, const ifem_ins_params *p, int use_nonzero, int imex, AsmMode mode);
 // the part of the argument block that the INS and the SCnsIM cell kernels share (AsmArgs, ScnsArgs: the same field names);
 // `cset`: the constraint object the scatter applies (0 / 1), -1: none
